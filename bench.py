@@ -8,7 +8,10 @@ frame; 30 frames played forwards and backwards), every child inheriting from a d
 parent slot (permutation: no occlusion plane is read twice, the worst case for HBM traffic).
 
 `value` (the contract's number): inputs (frames, poses, parent indices, occlusion planes) resident
-in HBM before the timed region, device-pointer API.  The same JSON line carries, as flat keys,
+in HBM before the timed region, device-pointer API.  `--steps K` is the number of timed steps in all
+(up to REPEATS regions, median region -> `ms_per_step`); `--dump-outputs DIR` writes the last timed
+step's log-likelihoods as DIR/loglikes.npy (seeded inputs: the same for the same arguments, run after
+run).  The same JSON line carries, as flat keys,
 
   host_api_*      the SAME steps through the host-pointer API the reference's filter would call:
                   frame upload, pose upload and log-likelihood download inside the clock
@@ -76,7 +79,11 @@ VALU_PEAK_TRANS_F64_GINST = 151.0
 GUIDE_PEAK_F32_GINST = 1024 * 2.4 / 2.0      # 1 228.8
 GUIDE_PEAK_F64_GINST = 1024 * 2.4 / 4.0      # 614.4
 GUIDE_PEAK_TRANS_F64_GINST = 1024 * 2.4 / 16.0   # 153.6
-REPEATS = 5                   # the headline is the median of this many timed regions of --steps steps each
+REPEATS = 5                   # the headline is the median of up to this many timed regions, --steps steps in all
+MIN_REGION_STEPS = 20         # ... of at least this many steps each (fewer steps in all: one region)
+MIN_WARMUP_STEPS = 100        # the headline's untimed steps at the least, whatever --warmup says: the first ~50 steps after a
+                              # short warm-up run ~4 % slow (a fixed count, not a time: the dumped outputs stay reproducible)
+DUMP_BYTES = 64 << 20         # --dump-outputs: at most this many bytes in all (a fixed, seeded sample beyond)
 WORKLOAD_FLAGS = ("particles", "cols", "rows", "mesh", "parents", "update", "sequence", "precision", "layout", "slab_px")
 
 
@@ -91,8 +98,13 @@ PRESETS = {"c1": {}, "c1_readonly": {"update": 0},
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=500)
-    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=None,
+                    help="timed steps of the headline in all (default 500, or the --config preset's), split into up to "
+                         f"{REPEATS} timed regions of at least {MIN_REGION_STEPS} steps")
+    ap.add_argument("--warmup", type=int, default=None,
+                    help=f"untimed steps before the first timed region (default 20, or the preset's; at least {MIN_WARMUP_STEPS} are run)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy")
     ap.add_argument("--particles", type=int, default=2000, help="particles per GPU")
     ap.add_argument("--cols", type=int, default=640)
     ap.add_argument("--rows", type=int, default=480)
@@ -134,8 +146,14 @@ def parse():
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)   # the process rocprofv3 wraps
     ap.add_argument("--sharded-tracker-child", action="store_true", help=argparse.SUPPRESS)   # one handle over --device-ids: tracker frames/s
     a = ap.parse_args()
+    explicit = {k: getattr(a, k) for k in ("steps", "warmup") if getattr(a, k) is not None}   # (win over a preset)
+    a.steps, a.warmup = 500, 20
     for k, v in PRESETS.get(a.config, {}).items():
         setattr(a, k, v)
+    for k, v in explicit.items():
+        setattr(a, k, v)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if a.quick or a.config not in (None, "c1"):
         a.no_dense_leg = a.no_f32_leg = a.no_host_leg = a.no_tracker_fps = a.no_cpu_baseline = a.no_configs_leg = a.no_sweep_leg = True
         a.no_pmc = a.no_pmc or a.quick
@@ -1224,17 +1242,19 @@ def in_process_multi_device(a):
             g.set_observation(W.frames[k])
             return g.loglikes_poses(poses[k], parents.copy(), update=bool(a.update))
 
-        for i in range(a.warmup):
+        for i in range(max(a.warmup, MIN_WARMUP_STEPS)):
             step(i)
-        regions = []
-        for rep in range(REPEATS):
+        region_ms = []
+        for k_steps in region_steps(a.steps):
             t0 = time.perf_counter()
-            for i in range(a.steps):
+            for i in range(k_steps):
                 ll = step(i)
-            regions.append(time.perf_counter() - t0)
-        elapsed = float(np.median(regions))
+            region_ms.append((time.perf_counter() - t0) / k_steps * 1e3)
+        ms = float(np.median(region_ms))
         if not np.isfinite(ll).all():
             raise SystemExit("non-finite log-likelihoods in the timed run")
+        if a.dump_outputs:             # the last timed step's log-likelihoods
+            dump_outputs(a.dump_outputs, {"loglikes": ll})
         # the dominant kernel on the handle's first device (every device runs the same launch on its shard)
         g.set_timing_every(2)
         for i in range(64):
@@ -1270,8 +1290,8 @@ def in_process_multi_device(a):
                  "call_ms_launch_stream": call_ms, "per_device": True, "algorithmic_bytes_per_launch": alg_bytes})
     line = {
         "metric": "particle-likelihoods/sec @640x480" if (a.cols, a.rows) == (640, 480) else f"particle-likelihoods/sec @{a.cols}x{a.rows}",
-        "value": n * a.steps / elapsed, "unit": "particle-likelihoods/s", "n_gpus": a.gpus, "steps": a.steps, "warmup": a.warmup,
-        "ms_per_step": elapsed / a.steps * 1e3, "timed_regions": REPEATS, "timed_regions_ms_per_step": [e / a.steps * 1e3 for e in regions],
+        "value": n / (ms * 1e-3), "unit": "particle-likelihoods/s", "n_gpus": a.gpus, "steps": a.steps, "warmup": a.warmup,
+        "warmup_steps_run": max(a.warmup, MIN_WARMUP_STEPS), "ms_per_step": ms, "timed_regions": len(region_ms), "timed_regions_ms_per_step": region_ms,
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": "f64 geometry + f32 likelihood (precision F32, opt-in)" if a.precision == "f32" else "f64", "data": "synthetic",
         "config": {"workload": f"C1 x {a.gpus}: ONE process, one handle over devices {ids} (rbs_config.n_devices), {a.particles} particles per "
@@ -1412,17 +1432,38 @@ class LineGuard:
         os._exit(0)
 
 
-def headline(a, world, n, n_tri, elapsed, regions, peer):
-    """The contract's keys of the line for `elapsed` seconds of a.steps steps (peer: 'ipc' = global parents over attached handles,
-    'local' = shards with local parents + the all-gather, None = one rank)."""
+def region_steps(steps):
+    """--steps split into the headline's timed regions: as many as REPEATS allows with MIN_REGION_STEPS each, sizes within one."""
+    r = max(1, min(REPEATS, steps // MIN_REGION_STEPS))
+    return [steps // r + (1 if i < steps % r else 0) for i in range(r)]
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each array as path/<name>.npy (float64 stays float64, anything else float32); an array beyond its share of
+    DUMP_BYTES is replaced by a fixed, seeded sample of its elements (same indices for the same size, run after run)."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // max(1, len(arrays))
+    for name, x in arrays.items():
+        x = np.asarray(x)
+        x = np.ascontiguousarray(x, dtype=np.float64 if x.dtype == np.float64 else np.float32).ravel()
+        if x.nbytes > share:
+            keep = share // x.itemsize
+            x = x[np.sort(np.random.default_rng(12345).choice(x.size, keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), x)
+
+
+def headline(a, world, n, n_tri, region_ms, peer):
+    """The contract's keys of the line; region_ms: ms per step of each timed region, the median of which is the line's ms_per_step
+    (peer: 'ipc' = global parents over attached handles, 'local' = shards with local parents + the all-gather, None = one rank)."""
+    ms = float(np.median(region_ms))
     out = {
         "metric": "particle-likelihoods/sec @640x480" if (a.cols, a.rows) == (640, 480)
                   else f"particle-likelihoods/sec @{a.cols}x{a.rows}",
-        "value": n * world * a.steps / elapsed,
+        "value": n * world / (ms * 1e-3),
         "unit": "particle-likelihoods/s",
         "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-        "ms_per_step": elapsed / a.steps * 1e3,
-        "timed_regions": REPEATS, "timed_regions_ms_per_step": [e / a.steps * 1e3 for e in regions],
+        "warmup_steps_run": max(a.warmup, MIN_WARMUP_STEPS), "ms_per_step": ms,
+        "timed_regions": len(region_ms), "timed_regions_ms_per_step": list(region_ms),
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": "f64 geometry + f32 likelihood (precision F32, opt-in)" if a.precision == "f32" else "f64",
         "data": "synthetic",
@@ -1520,18 +1561,17 @@ def main():
                 out_t.copy_(torch.cat(host))
 
         fb_run = LocalShardRun(a, W, fb_sensor, stream, d_out, d_all, fb_gather)
-        fb_regions = []
-        for rep in range(3):
-            el = fb_run.timed(a.steps, a.warmup if rep == 0 else 0, barrier=dist.barrier)
+        fb_region_ms = []
+        for rep, k_steps in enumerate(region_steps(a.steps)):
+            el = fb_run.timed(k_steps, max(a.warmup, MIN_WARMUP_STEPS) if rep == 0 else 0, barrier=dist.barrier)
             t = torch.tensor([el], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
-            fb_regions.append(float(t.item()))
+            fb_region_ms.append(float(t.item()) / k_steps * 1e3)
         torch.cuda.synchronize()
         dist.barrier()
         fb_sensor.close()
         del fb_run
-        fb_line = headline(a, world, n, n_tri, float(np.median(fb_regions)), fb_regions, "local")
-        fb_line["timed_regions"] = 3
+        fb_line = headline(a, world, n, n_tri, fb_region_ms, "local")
         guard.best = fb_line
         guard.arm(float(os.environ.get("RBS_BENCH_ATTACH_TIMEOUT", "240")), "rbs_ipc_attach / the multi-GPU self-check / the attached step")
     if world > 1:
@@ -1568,18 +1608,17 @@ def main():
         sensor.close()
         return
 
-    # REPEATS timed regions of exactly --steps steps each (every one bracketed by barrier +
+    # --steps timed steps in all, in up to REPEATS regions (every one bracketed by barrier +
     # synchronize on both sides, the MAX over ranks taken per region); the headline is the MEDIAN
-    # region -- a 20-step region is 4 ms, and one region alone moved by 7 % between runs
-    regions = []
-    for rep in range(REPEATS):
-        el = run.timed(a.steps, a.warmup if rep == 0 else 0, barrier=dist.barrier if world > 1 else None)
+    # region's ms per step -- a 20-step region is 4 ms, and one region alone moved by 7 % between runs
+    region_ms = []
+    for rep, k_steps in enumerate(region_steps(a.steps)):
+        el = run.timed(k_steps, max(a.warmup, MIN_WARMUP_STEPS) if rep == 0 else 0, barrier=dist.barrier if world > 1 else None)
         if world > 1:
             t = torch.tensor([el], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             el = float(t.item())
-        regions.append(el)
-    elapsed = float(np.median(regions))
+        region_ms.append(el / k_steps * 1e3)
     if world > 1:
         # every rank must hold every rank's log-likelihoods after the exchange
         ref = d_all.view(world, n)[rank].cpu().numpy()
@@ -1588,6 +1627,8 @@ def main():
     ll = d_out.cpu().numpy()
     if not np.isfinite(ll).all():
         raise SystemExit("non-finite log-likelihoods in the timed run")
+    if a.dump_outputs and rank == 0:   # the last timed step's log-likelihoods (several ranks: every rank's, gathered)
+        dump_outputs(a.dump_outputs, {"loglikes": d_all.cpu().numpy() if world > 1 else ll})
     # dominant-kernel durations: a separate pass of 512 launches, 256 of them bracketed by events
     raster_ms, copy_ms, call_ms, n_used = run.kernel_times(512)
     windows = np.array([sensor.get_window(s_) for s_ in range(0, n, max(1, n // 64))])
@@ -1595,7 +1636,7 @@ def main():
     peer_stats, peer_legs = None, {}
     if world > 1:
         # the headline is measured: from here on the watchdog would print IT (without the legs that follow)
-        best = headline(a, world, n, n_tri, elapsed, regions, "ipc" if peer_ok else "local")
+        best = headline(a, world, n, n_tri, region_ms, "ipc" if peer_ok else "local")
         best.update(selfcheck)
         best["peer_step"] = "ok" if peer_ok else "FAILED, local parents only: " + (peer_msg or "")
         guard.best = best
@@ -1654,7 +1695,7 @@ def main():
     # (the windowed copy kernel runs BESIDE it and moves ~1 % of the algorithmic bytes: pricing it with
     # them would report several times the HBM peak)
     copy_dominant = bool(a.update) and a.layout == "dense" and copy_ms > raster_ms
-    out = headline(a, world, n, n_tri, elapsed, regions, None if world == 1 else ("ipc" if peer_ok else "local"))
+    out = headline(a, world, n, n_tri, region_ms, None if world == 1 else ("ipc" if peer_ok else "local"))
     if world > 1:
         if not peer_ok:
             out["config"]["workload"] += " -- the ranks' handles could not be attached to each other, see peer_step"
