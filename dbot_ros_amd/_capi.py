@@ -44,6 +44,8 @@ EXPORTS = (
     "rbs_tracker_create", "rbs_tracker_destroy", "rbs_tracker_initialize", "rbs_tracker_track",
     "rbs_tracker_submit", "rbs_tracker_result", "rbs_tracker_track_f64", "rbs_tracker_submit_f64",
     "rbs_tracker_get",
+    "rbs_gauss_create", "rbs_gauss_destroy", "rbs_gauss_initialize", "rbs_gauss_track", "rbs_gauss_track_f64",
+    "rbs_gauss_get_prior", "rbs_gauss_get_sigma_poses", "rbs_gauss_get_render", "rbs_gauss_kernel_ms",
 )
 
 
@@ -54,6 +56,21 @@ class RbsTrackerParams(C.Structure):
         ("velocity_factor", C.c_double),
         ("max_kl_divergence", C.c_double),
         ("n_particles", C.c_int32),
+    ]
+
+
+class RbsGaussParams(C.Structure):
+    _fields_ = [
+        ("linear_sigma", C.c_double * 3),
+        ("angular_sigma", C.c_double * 3),
+        ("velocity_factor", C.c_double),
+        ("ut_alpha", C.c_double),
+        ("fg_noise_std", C.c_double),
+        ("bg_depth", C.c_double),
+        ("bg_noise_std", C.c_double),
+        ("tail_weight", C.c_double),
+        ("uniform_tail_min", C.c_double),
+        ("uniform_tail_max", C.c_double),
     ]
 
 
@@ -224,5 +241,23 @@ def load():
     lib.rbs_tracker_result.argtypes = [H, dp, ip]
     lib.rbs_tracker_get.restype = C.c_int32
     lib.rbs_tracker_get.argtypes = [H, dp, dp, ip]
+    lib.rbs_gauss_create.restype = C.c_int32
+    lib.rbs_gauss_create.argtypes = [H, C.POINTER(RbsGaussParams), C.POINTER(H)]
+    lib.rbs_gauss_destroy.restype = None
+    lib.rbs_gauss_destroy.argtypes = [H]
+    lib.rbs_gauss_initialize.restype = C.c_int32
+    lib.rbs_gauss_initialize.argtypes = [H, dp, dp]
+    lib.rbs_gauss_track.restype = C.c_int32
+    lib.rbs_gauss_track.argtypes = [H, fp, dp, dp]
+    lib.rbs_gauss_track_f64.restype = C.c_int32
+    lib.rbs_gauss_track_f64.argtypes = [H, dp, dp, dp]
+    lib.rbs_gauss_get_prior.restype = C.c_int32
+    lib.rbs_gauss_get_prior.argtypes = [H, dp, dp, dp]
+    lib.rbs_gauss_get_sigma_poses.restype = C.c_int32
+    lib.rbs_gauss_get_sigma_poses.argtypes = [H, dp, ip]
+    lib.rbs_gauss_get_render.restype = C.c_int32
+    lib.rbs_gauss_get_render.argtypes = [H, C.c_int32, fp]
+    lib.rbs_gauss_kernel_ms.restype = C.c_int32
+    lib.rbs_gauss_kernel_ms.argtypes = [H, fp]
     _lib = lib
     return lib

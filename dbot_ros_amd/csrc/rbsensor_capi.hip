@@ -4466,3 +4466,6 @@ int32_t rbs_tracker_get(rbs_tracker* t, double* particles, double* log_weights, 
 }
 
 }  // extern "C"
+
+// The robust Gaussian tracker (rbs_gauss_*): its kernels and host side.
+#include "rbsensor_gauss.hip"

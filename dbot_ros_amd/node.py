@@ -12,7 +12,7 @@ import numpy as np
 import yaml
 
 from .objloader import ObjectResourceIdentifier, SimpleWavefrontObjectModelLoader
-from .sensor import CameraData, ObjectModel, RbSensorBuilder
+from .sensor import CameraData, ObjectModel, RbSensor, RbSensorBuilder
 from .tracker import DeviceParticleTracker, ObjectTransitionBuilder, ParticleTracker, ParticleTrackerBuilder
 
 
@@ -50,6 +50,34 @@ def build_particle_tracker(params, native_camera_matrix, mesh_package_path, devi
                                         device_rng=rng is None, seed=seed)
     else:
         tracker = ParticleTracker(transition, sensor, object_model, params_tracker, rng)
+    return tracker, object_model, camera_data, ori
+
+
+def build_gaussian_tracker(params, native_camera_matrix, mesh_package_path, device_id=0):
+    """The robust Gaussian tracker as R:source/dbot_ros/tracker/gaussian_tracker_node.cpp assembles it
+    (R:launch/gaussian_tracker.launch -> R:config/gaussian_tracker.yaml, camera.yaml, object.yaml), in the
+    node's order: parameters (:71-116), camera data (:118-133), object model, tracker.  params: merged
+    rosparam tree.  Returns (tracker, object_model, camera_data, ori); tracker.sensor is the device handle
+    it renders with (close the tracker, then the sensor)."""
+    from .gaussian import GaussianTracker, GaussianTrackerBuilder
+    pre = params["gaussian_filter"]
+    # ---- parameters (node :71-116)
+    obj = params["object"]
+    ori = ObjectResourceIdentifier(mesh_package_path, obj["directory"], obj["meshes"])
+    # ---- camera data (node :118-133)
+    camera_data = CameraData.from_native(native_camera_matrix, int(params["resolution"]["width"]),
+                                         int(params["resolution"]["height"]), int(params["downsampling_factor"]))
+    params_tracker = GaussianTrackerBuilder.Parameters.from_rosparam(params, ori.count_meshes(),
+                                                                     sensors=camera_data.rows * camera_data.cols)
+    # ---- object model and the device renderer of the sigma poses
+    vs, ts = SimpleWavefrontObjectModelLoader(ori).load()
+    object_model = ObjectModel(vs, ts, center=bool(pre["center_object_frame"]))
+    sensor = RbSensor(object_model, camera_data, RbSensorBuilder.Parameters(sample_count=1), device_id=device_id)
+    try:
+        tracker = GaussianTracker(sensor, object_model, params_tracker)
+    except Exception:
+        sensor.close()
+        raise
     return tracker, object_model, camera_data, ori
 
 

@@ -561,6 +561,56 @@ int32_t rbs_tracker_submit_f64(rbs_tracker* t, const double* frame, const double
  * (any pointer may be NULL). */
 int32_t rbs_tracker_get(rbs_tracker* t, double* particles, double* log_weights, int32_t* indices);
 
+/* ------------------------------------------------------------------------------------------
+ * Robust Gaussian tracker (the reference's second tracker, R:source/dbot_ros/tracker/gaussian_tracker_node.cpp):
+ * an unscented-transform Gaussian filter over the object state with pixels as conditionally independent
+ * sensors and a per-pixel robust body weight -- DESIGN.md Appendix G states the arithmetic.  On the
+ * sensor's device: the 1 + 12 n_objects distinct sigma poses are rendered (the particle path's binary64
+ * rasterizer, depths bit-identical to the oracle's) and the per-pixel moments reduced in a fixed order
+ * (deterministic: no floating-point atomics); on the host, in binary64: predict, Cholesky, sigma poses,
+ * the 6 n_objects x 6 n_objects solve and the re-centring -- one host synchronisation per frame.
+ * States are in MODEL coordinates like rbs_tracker_*; D = 12 n_objects.
+ * Limits: n_objects <= 3; single-device handles only (several devices or an attached rank:
+ * RBS_ERR_UNSUPPORTED).  A sensor handle drives ONE tracker at a time -- particle or Gaussian -- since
+ * both set its observation. */
+typedef struct rbs_gauss rbs_gauss;
+
+typedef struct rbs_gauss_params {
+    double linear_sigma[3];      /* gaussian_filter/object_transition/linear_sigma_{x,y,z}  (>= 0) */
+    double angular_sigma[3];     /* gaussian_filter/object_transition/angular_sigma_{x,y,z} (>= 0) */
+    double velocity_factor;      /* gaussian_filter/object_transition/velocity_factor */
+    double ut_alpha;             /* gaussian_filter/unscented_transform/alpha (> 0; beta = 2, kappa = 0) */
+    double fg_noise_std;         /* gaussian_filter/observation/fg_noise_std (> 0) */
+    double bg_depth;             /* gaussian_filter/observation/bg_depth */
+    double bg_noise_std;         /* gaussian_filter/observation/bg_noise_std (>= 0) */
+    double tail_weight;          /* gaussian_filter/observation/tail_weight, in [0, 1) */
+    double uniform_tail_min;     /* gaussian_filter/observation/uniform_tail_{min,max}: max > min */
+    double uniform_tail_max;
+} rbs_gauss_params;
+
+/* The tracker borrows `sensor` (must outlive it) and runs on the sensor's own stream.  Invalid
+ * parameters: RBS_ERR_INVALID_ARGUMENT (message via rbs_last_error(NULL) when sensor is NULL). */
+int32_t rbs_gauss_create(rbs_handle* sensor, const rbs_gauss_params* params, rbs_gauss** out);
+void rbs_gauss_destroy(rbs_gauss* g);
+/* default_state [D]: the default pose z (velocities as given); mean delta := 0; covariance := cov0
+ * [D][D] (symmetric positive definite), or NULL: per body diag(lin^2, ang^2, lin^2, ang^2). */
+int32_t rbs_gauss_initialize(rbs_gauss* g, const double* default_state, const double* cov0);
+/* One frame.  frame: float32[rows*cols] (NULL: already set through an rbs_set_observation* call).
+ * out_state [D]: the re-centred default state (pose, and the mean's velocities); out_cov [D][D] or NULL. */
+int32_t rbs_gauss_track(rbs_gauss* g, const float* frame, double* out_state, double* out_cov);
+/* The same with rows*cols DOUBLES (dbot's Obsrv): rounded to float while staged, as rbs_set_observation. */
+int32_t rbs_gauss_track_f64(rbs_gauss* g, const double* frame, double* out_state, double* out_cov);
+/* Inspection, for the parity tests: the last frame's default state z [D], predicted mean [D] and
+ * covariance [D][D] (any pointer may be NULL) ... */
+int32_t rbs_gauss_get_prior(rbs_gauss* g, double* default_state, double* mean, double* cov);
+/* ... its distinct sigma poses [n][n_objects][12] (R row-major | t), n = 1 + 12 n_objects: the centre,
+ * then + and - of every pose column of the Cholesky factor (pose-first order) ... */
+int32_t rbs_gauss_get_sigma_poses(rbs_gauss* g, double* out, int32_t* n);
+/* ... the depth image of sigma pose k (+inf where nothing is covered) ... */
+int32_t rbs_gauss_get_render(rbs_gauss* g, int32_t k, float* out);
+/* ... and its device time in ms: [0] render, [1] moments, [2] reduction (HIP events). */
+int32_t rbs_gauss_kernel_ms(rbs_gauss* g, float* out3);
+
 #ifdef __cplusplus
 }
 #endif
