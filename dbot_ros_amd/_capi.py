@@ -45,7 +45,8 @@ EXPORTS = (
     "rbs_tracker_submit", "rbs_tracker_result", "rbs_tracker_track_f64", "rbs_tracker_submit_f64",
     "rbs_tracker_get",
     "rbs_gauss_create", "rbs_gauss_destroy", "rbs_gauss_initialize", "rbs_gauss_track", "rbs_gauss_track_f64",
-    "rbs_gauss_get_prior", "rbs_gauss_get_sigma_poses", "rbs_gauss_get_render", "rbs_gauss_kernel_ms",
+    "rbs_gauss_get_prior", "rbs_gauss_get_sigma_poses", "rbs_gauss_get_render", "rbs_gauss_get_moments",
+    "rbs_gauss_kernel_ms",
 )
 
 
@@ -257,6 +258,8 @@ def load():
     lib.rbs_gauss_get_sigma_poses.argtypes = [H, dp, ip]
     lib.rbs_gauss_get_render.restype = C.c_int32
     lib.rbs_gauss_get_render.argtypes = [H, C.c_int32, fp]
+    lib.rbs_gauss_get_moments.restype = C.c_int32
+    lib.rbs_gauss_get_moments.argtypes = [H, dp, ip]
     lib.rbs_gauss_kernel_ms.restype = C.c_int32
     lib.rbs_gauss_kernel_ms.argtypes = [H, fp]
     _lib = lib

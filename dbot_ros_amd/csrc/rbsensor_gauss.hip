@@ -619,6 +619,16 @@ int32_t rbs_gauss_get_render(rbs_gauss* g, int32_t k, float* out)
     return RBS_OK;
 }
 
+int32_t rbs_gauss_get_moments(rbs_gauss* g, double* out, int32_t* n)
+{
+    if (!g) return RBS_ERR_INVALID_ARGUMENT;
+    if (!out || !n) return gauss::gfail(g, RBS_ERR_INVALID_ARGUMENT, "gauss_get_moments: null pointer");
+    if (!g->tracked) return gauss::gfail(g, RBS_ERR_INVALID_ARGUMENT, "gauss_get_moments: no frame tracked yet");
+    *n = g->NE;
+    std::memcpy(out, g->h_out, sizeof(double) * g->NE);   // (track_impl synchronised before it read them)
+    return RBS_OK;
+}
+
 int32_t rbs_gauss_kernel_ms(rbs_gauss* g, float* out3)
 {
     if (!g) return RBS_ERR_INVALID_ARGUMENT;

@@ -130,16 +130,20 @@ class GaussianTracker:
         self.moving_average = None
 
     def track(self, image):
-        """One depth frame (float32 or float64, rows*cols metres, NaN = no reading) -> State."""
+        """One depth frame (float32 or float64, rows*cols metres, NaN = no reading) -> State.  image=None: the frame
+        an earlier sensor.set_observation* call staged."""
         self._live()
         f64 = isinstance(image, np.ndarray) and image.dtype == np.float64
-        img = np.ascontiguousarray(image, dtype=np.float64 if f64 else np.float32).ravel()
         out = np.empty(self.D)
         cov = np.empty((self.D, self.D))
         dp = C.POINTER(C.c_double)
-        if f64:
+        if image is None:
+            rc = self._lib.rbs_gauss_track(self._g, None, out.ctypes.data_as(dp), cov.ctypes.data_as(dp))
+        elif f64:
+            img = np.ascontiguousarray(image, dtype=np.float64).ravel()
             rc = self._lib.rbs_gauss_track_f64(self._g, img.ctypes.data_as(dp), out.ctypes.data_as(dp), cov.ctypes.data_as(dp))
         else:
+            img = np.ascontiguousarray(image, dtype=np.float32).ravel()
             rc = self._lib.rbs_gauss_track(self._g, img.ctypes.data_as(C.POINTER(C.c_float)), out.ctypes.data_as(dp),
                                            cov.ctypes.data_as(dp))
         self.sensor._check(rc)
@@ -179,6 +183,25 @@ class GaussianTracker:
         out = np.empty(self.sensor.rows * self.sensor.cols, dtype=np.float32)
         self.sensor._check(self._lib.rbs_gauss_get_render(self._g, int(k), out.ctypes.data_as(C.POINTER(C.c_float))))
         return out
+
+    def moments(self, raw=False):
+        """The last frame's reduced moments in the whitened space: (Lambda [6 parts, 6 parts] with the identity added,
+        eta [6 parts]), GaussTwin.whitened_update's convention.  raw=True: the entries exactly as the library read
+        them from the device, [6p(6p+1)/2 + 6p] -- the upper triangle of Lambda - I row-major, then eta."""
+        self._live()
+        NP = 6 * self.parts
+        out = np.empty(NP * (NP + 1) // 2 + NP)
+        n = C.c_int32()
+        self.sensor._check(self._lib.rbs_gauss_get_moments(self._g, out.ctypes.data_as(C.POINTER(C.c_double)), C.byref(n)))
+        if n.value != out.size:
+            raise RbSensorError(_capi.RBS_ERR_INVALID_ARGUMENT, f"gauss_get_moments: {n.value} entries, expected {out.size}")
+        if raw:
+            return out
+        iu = np.triu_indices(NP)
+        lam = np.zeros((NP, NP))
+        lam[iu] = out[:iu[0].size]
+        lam = lam + np.triu(lam, 1).T + np.eye(NP)
+        return lam, out[iu[0].size:].copy()
 
     def kernel_ms(self):
         """Device ms of the last frame: (render, moments, reduction)."""

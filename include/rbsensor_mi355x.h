@@ -608,6 +608,10 @@ int32_t rbs_gauss_get_prior(rbs_gauss* g, double* default_state, double* mean, d
 int32_t rbs_gauss_get_sigma_poses(rbs_gauss* g, double* out, int32_t* n);
 /* ... the depth image of sigma pose k (+inf where nothing is covered) ... */
 int32_t rbs_gauss_get_render(rbs_gauss* g, int32_t k, float* out);
+/* ... the reduced moments exactly as the host read them: out [NE], NE = 6B(6B+1)/2 + 6B (B = n_objects), the
+ * upper triangle of Lambda - I row-major (a <= b), then eta; *n := NE.  RBS_ERR_INVALID_ARGUMENT before the
+ * first frame or for a NULL pointer ... */
+int32_t rbs_gauss_get_moments(rbs_gauss* g, double* out, int32_t* n);
 /* ... and its device time in ms: [0] render, [1] moments, [2] reduction (HIP events). */
 int32_t rbs_gauss_kernel_ms(rbs_gauss* g, float* out3);
 

@@ -17,7 +17,8 @@ from dbot_ros_amd.gaussian import GaussianTrackerBuilder
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REFERENCE_CONFIG = os.path.join(ROOT, "tests", "golden", "reference_config")
 GAUSS_SYMBOLS = ("rbs_gauss_create", "rbs_gauss_destroy", "rbs_gauss_initialize", "rbs_gauss_track", "rbs_gauss_track_f64",
-                 "rbs_gauss_get_prior", "rbs_gauss_get_sigma_poses", "rbs_gauss_get_render", "rbs_gauss_kernel_ms")
+                 "rbs_gauss_get_prior", "rbs_gauss_get_sigma_poses", "rbs_gauss_get_render", "rbs_gauss_get_moments",
+                 "rbs_gauss_kernel_ms")
 
 
 def _random_spd(rng, n, scale):
@@ -165,6 +166,9 @@ def test_calls_fail_loudly_without_a_tracker_or_device():
     assert lib.rbs_gauss_get_sigma_poses(None, None, None) == _capi.RBS_ERR_INVALID_ARGUMENT
     assert lib.rbs_gauss_get_render(None, 0, None) == _capi.RBS_ERR_INVALID_ARGUMENT
     assert lib.rbs_gauss_kernel_ms(None, None) == _capi.RBS_ERR_INVALID_ARGUMENT
+    out_e, n = (C.c_double * 27)(), C.c_int32(-1)
+    assert lib.rbs_gauss_get_moments(None, out_e, C.byref(n)) == _capi.RBS_ERR_INVALID_ARGUMENT and n.value == -1
+    assert lib.rbs_gauss_get_moments(None, None, None) == _capi.RBS_ERR_INVALID_ARGUMENT
     lib.rbs_gauss_destroy(None)   # no-op
 
 
