@@ -172,6 +172,7 @@ struct rbs_handle {
     // Stamped planes (rbs_config.occlusion_mode = RBS_OCC_REFERENCE; DevParams::exact): a slot is plane_px floats + plane_px
     // 16-bit ages, plane_stride floats in all.
     bool one_body_kernel = true;    // single-body models take rbs_raster_kernel_one_f64 (RBS_ONE_BODY=0, tooling: the general kernel)
+    bool fused_copy = true;         // windowed copy inside the raster kernel where it applies (RBS_FUSED_COPY=0, tooling / A-B: the side-stream kernel)
     bool exact = false;
     int age_max = 0;            // ages beyond it are background
     double* d_ptab = nullptr;   // [age_max + 1][2] the propagation table
@@ -777,6 +778,14 @@ int32_t enqueue_loglikes(rbs_handle* h, const double* d_poses, const int* d_indi
     }
     P.area_sum = sample_area ? h->d_area : nullptr;
     const bool wide = h->windowed && update && h->wide;
+    // wide windows: two raster blocks per CU leave the streaming copy its registers
+    const bool mid = h->windowed && update && !wide && h->area_frac > h->mid_enter;
+    // the windowed copy done by the raster kernel's own blocks (rbs_raster_kernel_wcopy_*: one body, one rectangle, scalar
+    // background, whole planes, one device): the call is then prep + raster on this stream -- no fork, no second queue, no join
+    const bool fused = h->fused_copy && update && h->windowed && !wide && !mid && !split && !h->exact && !h->slab_px && !P.bgp_src &&
+                       !P.groups && h->n_bodies == 1 && !h->many_clusters && !h->group && h->peer_world <= 1 && !h->ipc_exported &&
+                       (h->precision == RBS_PRECISION_F32 || h->one_body_kernel);
+    if (timed && fused) h->ring_update[tslot] = false;   // (no copy kernel to time: timing_summary's copy_kernel_ms is 0)
     if (h->lazy_frame && h->lazy_stream == s) {
         constexpr int ptb = 64 * rbs::kPrepPerBlock;
         const int aux_blocks = (h->d_aux || h->lazy_frame != h->d_frame) ? (h->npx + ptb - 1) / ptb : 0;
@@ -797,7 +806,7 @@ int32_t enqueue_loglikes(rbs_handle* h, const double* d_poses, const int* d_indi
         h->area_pending = true;
         h->area_n = (n + 7) / 8;    // (the rectangles kernel adds every 8th particle's region)
     }
-    if (update) {
+    if (update && !fused) {
         // fork: the copy kernel runs on the handle's second stream, concurrently with the
         // persistent raster kernel; it needs this call's rectangles only
         RBS_HIP(h, hipEventRecord(h->ev_fork, s));
@@ -813,9 +822,7 @@ int32_t enqueue_loglikes(rbs_handle* h, const double* d_poses, const int* d_indi
         RBS_HIP(h, hipStreamWaitEvent(s, h->ev_join[h->join_pending], 0));
         h->join_pending = -1;
     }
-    // wide windows: two raster blocks per CU leave the streaming copy its registers
-    const bool mid = h->windowed && update && !wide && h->area_frac > h->mid_enter;
-    if (h->balance && h->windowed && update && !wide && !mid && h->timed_calls > h->balance_seen && h->raster_blocks == 3 * h->cu_count) {
+    if (h->balance && h->windowed && update && !wide && !mid && !fused && h->timed_calls > h->balance_seen && h->raster_blocks == 3 * h->cu_count) {
         const int last = (int)((h->timed_calls - 1) % rbs_handle::kRing);
         if (h->ring_update[last] && hipEventQuery(h->ev_raster_stop[last]) == hipSuccess && hipEventQuery(h->ev_copy_stop[last]) == hipSuccess) {
             float r_ms = 0.f, c_ms = 0.f;
@@ -832,7 +839,7 @@ int32_t enqueue_loglikes(rbs_handle* h, const double* d_poses, const int* d_indi
             h->balance_seen = h->timed_calls;
         }
     }
-    const int full_grid = h->balance && h->balance_blocks && h->windowed && update ? h->balance_blocks : h->raster_blocks;
+    const int full_grid = h->balance && h->balance_blocks && h->windowed && update && !fused ? h->balance_blocks : h->raster_blocks;
     const dim3 rgrid((unsigned)(wide || mid ? std::min(h->raster_blocks, 2 * h->cu_count) : full_grid));
     // a host frame that is read where it was uploaded: only now does the stream wait for the upload
     // (split launch: the geometry kernel needs no frame -- the wait sits between the two kernels, and a host frame
@@ -920,12 +927,17 @@ int32_t enqueue_loglikes(rbs_handle* h, const double* d_poses, const int* d_indi
         RBS_HIP(h, hipGetLastError());
     }
     if (update) {
-        if (!split) launch_raster(h, true, rgrid, block, rbs::smem_bytes(P.tile_px, f64, h->many_clusters, h->exact), s, P);
+        const size_t rsm = rbs::smem_bytes(P.tile_px, f64, h->many_clusters, h->exact);
+        if (fused && f64) hipLaunchKernelGGL(rbs::rbs_raster_kernel_wcopy_one_f64, rgrid, block, rsm, s, P);
+        else if (fused) hipLaunchKernelGGL(rbs::rbs_raster_kernel_wcopy_f32, rgrid, block, rsm, s, P);
+        else if (!split) launch_raster(h, true, rgrid, block, rsm, s, P);
         RBS_HIP(h, hipGetLastError());
         if (timed) RBS_HIP(h, hipEventRecord(h->ev_raster_stop[tslot], s));
         const dim3 cgrid((unsigned)std::min<long>((long)h->copy_blocks, (long)n * P.bands));
         if (timed && (!h->windowed || wide)) RBS_HIP(h, hipEventRecord(h->ev_copy_start[tslot], h->copy_stream));
-        if (h->windowed && !wide) {
+        if (fused) {
+            // (done: the raster kernel wrote the particles' cells outside their rectangles)
+        } else if (h->windowed && !wide) {
             if (!window_copy_launched) if (int32_t rc = launch_window_copy()) return rc;
         } else if (wide) {
             const int W4 = P.cols >> 2;
@@ -978,7 +990,7 @@ int32_t enqueue_loglikes(rbs_handle* h, const double* d_poses, const int* d_indi
         h->area_frac = 1.0;   // (what the last sample said: the next calls take the whole-plane machinery at once)
         h->wide = !h->slab_px && !h->exact;
     }
-    if (update) h->join_pending = slot;   // joined lazily: by the next call, or by drain()
+    if (update && !fused) h->join_pending = slot;   // joined lazily: by the next call, or by drain()
     if (h->group) {
         // other shards read this shard's planes: one event that covers both streams of this call
         if (h->join_pending >= 0) {
@@ -1897,6 +1909,7 @@ int32_t create_impl(const rbs_config* cfg, rbs_handle* h)
         if (const char* m = std::getenv("RBS_RASTER_BLOCKS")) h->raster_blocks = std::max(1, std::atoi(m));
         if (const char* m = std::getenv("RBS_SHARED_TRAIL")) h->stp_allowed = std::atoi(m) != 0;
         if (const char* m = std::getenv("RBS_ONE_BODY")) h->one_body_kernel = std::atoi(m) != 0;
+        if (const char* m = std::getenv("RBS_FUSED_COPY")) h->fused_copy = std::atoi(m) != 0;
         if (const char* m = std::getenv("RBS_TRACKER_SPLIT_MAX")) h->tracker_split_max = std::atoi(m);
         if (const char* m = std::getenv("RBS_STP_ENTER")) h->stp_enter = std::atof(m);
         if (const char* m = std::getenv("RBS_STP_EVERY")) h->stp_every = std::max(1, std::atoi(m));

@@ -1901,6 +1901,91 @@ __global__ __launch_bounds__(64 * kPrepPerBlock) void rbs_frame_prep_kernel(cons
     }
 }
 
+// The windowed copy INSIDE the persistent raster kernel (FCOPY: updating call, windowed whole planes, one rectangle per particle,
+// scalar background): the block that ran a particle's first work item writes the particle's cells outside its rectangle right
+// after the pixel pass, while the rectangle, the parent and the window are at hand.  The cells, their arithmetic and the
+// re-tightening of the child's window are those of rbs_copy_window_kernel<false, 1, false, false> (below), so the planes, the
+// windows and the log-likelihoods are the same bits; only the schedule differs: 256 lanes of one block walk the particle's cells
+// instead of one-wave blocks on a second stream.  Cell = one float4 of u = bbox(parent window, rectangle) outside the rectangle:
+// the band of rows above it, the two strips beside it, the band below (an empty rectangle: all of u).
+#ifndef RBS_FCOPY_UNROLL
+#define RBS_FCOPY_UNROLL 2     // cells in flight per lane (three or more: 2 VGPRs spilled in the binary64 kernel)
+#endif
+__device__ __forceinline__ void fused_window_copy(const DevParams& P, int particle)
+{
+    constexpr int kU = RBS_FCOPY_UNROLL;
+    const int parent = P.parents[particle];
+    if ((unsigned)parent >= (unsigned)P.slots) return;
+    const int4 u = P.win_used[particle];
+    if (u.z <= u.x || u.w <= u.y) return;
+    const int4 q = reinterpret_cast<const int4*>(P.rects)[particle];
+    const bool has = q.z > q.x;
+    const int w4 = (u.z - u.x) >> 2, ux4 = u.x >> 2, W4 = P.cols >> 2;
+    const int ty1 = has ? q.y : u.w, tby0 = has ? q.w : u.w;
+    const int left4 = has ? (q.x - u.x) >> 2 : 0, right4 = has ? (u.z - q.z) >> 2 : 0, m = left4 + right4;
+    const int rjump = has ? (q.z - u.x) >> 2 : 0;
+    const int n_top = (ty1 - u.y) * w4, n_mid = (tby0 - ty1) * m, L = n_top + n_mid + (u.w - tby0) * w4;
+    if (L == 0) return;   // all raster's
+    const float rw4 = 1.0f / (float)w4, rm = 1.0f / (float)max(m, 1);
+    const int4 pw = parent_window(P, parent);
+    const floatx4* __restrict__ s4 = reinterpret_cast<const floatx4*>(parent_plane(P, parent));
+    floatx4* __restrict__ d4 = reinterpret_cast<floatx4*>(P.occ_dst + (size_t)particle * P.plane_stride);
+    const float alpha = P.alpha, beta = P.beta, bg_new = P.bg_new;
+    int bx0 = P.cols, by0 = P.rows, bx1 = 0, by1 = 0;
+    for (int base = 0; base < L; base += kBlock * kU) {
+        floatx4 v[kU];
+        int pk[kU];    // state << 28 | row << 14 | float4 column (rows and columns <= 8 192: create refuses more)
+#pragma unroll
+        for (int k = 0; k < kU; ++k) {
+            const int idx = base + k * kBlock + (int)threadIdx.x;
+            const bool live = idx < L;
+            // (the three bands' row = cell / width through one division: a float quotient, corrected to the exact integer one --
+            // the integer division of each band kept the loop from holding more than one cell in flight within the budget)
+            const bool top = idx < n_top, mid = !top && idx < n_top + n_mid;
+            const int j = top ? idx : mid ? idx - n_top : idx - n_top - n_mid, d = mid ? m : w4;
+            int r = (int)((float)j * (mid ? rm : rw4));
+            r += (r + 1) * d <= j ? 1 : 0;
+            r -= r * d > j ? 1 : 0;
+            const int kk = j - r * d;
+            const int row = (top ? u.y : mid ? ty1 : tby0) + r, c4 = mid ? (kk < left4 ? kk : kk - left4 + rjump) : kk;
+            const int col = (ux4 + c4) << 2;
+            const bool stored = live && col >= pw.x && col < pw.z && row >= pw.y && row < pw.w;
+            pk[k] = ((live ? (stored ? 2 : 1) : 0) << 28) | (row << 14) | (ux4 + c4);
+            if (stored) v[k] = __builtin_nontemporal_load(&s4[row * W4 + (ux4 + c4)]);
+        }
+#pragma unroll
+        for (int k = 0; k < kU; ++k) {
+            const int st_ = pk[k] >> 28, row_ = (pk[k] >> 14) & 0x3fff, at_ = pk[k] & 0x3fff;
+            if (!st_) continue;
+            floatx4 w;
+            if (st_ == 2) {
+                w.x = occ_step(alpha, beta, v[k].x, bg_new);
+                w.y = occ_step(alpha, beta, v[k].y, bg_new);
+                w.z = occ_step(alpha, beta, v[k].z, bg_new);
+                w.w = occ_step(alpha, beta, v[k].w, bg_new);
+            } else {
+                w.x = w.y = w.z = w.w = bg_new;
+            }
+            __builtin_nontemporal_store(w, &d4[row_ * W4 + at_]);
+            if (w.x != bg_new || w.y != bg_new || w.z != bg_new || w.w != bg_new) {
+                const int col = at_ << 2;
+                bx0 = min(bx0, col); bx1 = max(bx1, col + 4);
+                by0 = min(by0, row_); by1 = max(by1, row_ + 1);
+            }
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        bx0 = min(bx0, __shfl_xor(bx0, off)); by0 = min(by0, __shfl_xor(by0, off));
+        bx1 = max(bx1, __shfl_xor(bx1, off)); by1 = max(by1, __shfl_xor(by1, off));
+    }
+    if ((threadIdx.x & 63) == 0 && bx1 > bx0) {   // (once per wave, like the copy kernel's waves: min / max in any order)
+        int* wd = reinterpret_cast<int*>(&P.win_dst[particle]);
+        atomicMin(wd + 0, bx0); atomicMin(wd + 1, by0);
+        atomicMax(wd + 2, bx1); atomicMax(wd + 3, by1);
+    }
+}
+
 // Three 4-wave blocks per CU = 3 waves/SIMD = 168 VGPRs (a few spilled dwords).
 #ifndef RBS_RASTER_MINWAVES_F64
 #define RBS_RASTER_MINWAVES_F64 3
@@ -1912,9 +1997,10 @@ __global__ __launch_bounds__(64 * kPrepPerBlock) void rbs_frame_prep_kernel(cons
 // launch (never starved by the many small copy blocks) and pulls (particle, tile) items from
 // an atomic queue.
 constexpr size_t smem_bytes(int tile_px, bool math_tables, bool many = false, bool exact = false);
-template <bool UPDATE, int PREC, bool SLAB, bool MANY = false, bool STP = false, bool EXACT = false, bool ONE = false>
+template <bool UPDATE, int PREC, bool SLAB, bool MANY = false, bool STP = false, bool EXACT = false, bool ONE = false, bool FCOPY = false>
 __device__ __forceinline__ void raster_kernel_body(const DevParams& P)
 {
+    static_assert(!FCOPY || (UPDATE && !SLAB && !MANY && !STP && !EXACT), "the fused copy serves windowed whole planes, scalar background");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     Smem m = carve(smem, P.tile_px, PREC == 0 && RBS_MATH_LDS);
     if (EXACT) {
@@ -1995,6 +2081,8 @@ __device__ __forceinline__ void raster_kernel_body(const DevParams& P)
                 }
             }
         }
+        // (behind the pixel pass: the next item's ticket, drawn at its end, travels meanwhile)
+        if (FCOPY && item == first) fused_window_copy(P, particle);
         if (draw) {
             if (threadIdx.x == 0) {
                 if (ticket < 0) ticket = atomicAdd(&P.ctr_this[1], 1);   // (an item that ended before its reduction)
@@ -2053,6 +2141,17 @@ template <bool UPDATE, bool SLAB>
 __global__ __launch_bounds__(kBlock, RBS_RASTER_MINWAVES_F64) RBS_F64_BUDGET void rbs_raster_kernel_one_f64(const DevParams P)
 {
     raster_kernel_body<UPDATE, 0, SLAB, false, false, false, true>(P);
+}
+// ... updating, windowed whole planes, one rectangle, scalar background: the windowed copy done by the same blocks (FCOPY, see
+// fused_window_copy); the call is then prep + this kernel on one stream, like a read-only call
+__global__ __launch_bounds__(kBlock, RBS_RASTER_MINWAVES_F64) RBS_F64_BUDGET void rbs_raster_kernel_wcopy_one_f64(const DevParams P)
+{
+    raster_kernel_body<true, 0, false, false, false, false, true, true>(P);
+}
+__global__ __launch_bounds__(kBlock, RBS_RASTER_MINWAVES) __attribute__((amdgpu_num_vgpr(RBS_RASTER_VGPRS)))
+void rbs_raster_kernel_wcopy_f32(const DevParams P)
+{
+    raster_kernel_body<true, 1, false, false, false, false, false, true>(P);
 }
 // ... with the shared background plane (STP: binary64; whole planes or slabs -- the shared plane itself is always a whole plane,
 // addressed by frame offsets), kernels of their own so that the others stay as they are
