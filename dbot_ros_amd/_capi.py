@@ -46,7 +46,7 @@ EXPORTS = (
     "rbs_tracker_get",
     "rbs_gauss_create", "rbs_gauss_destroy", "rbs_gauss_initialize", "rbs_gauss_track", "rbs_gauss_track_f64",
     "rbs_gauss_get_prior", "rbs_gauss_get_sigma_poses", "rbs_gauss_get_render", "rbs_gauss_get_moments",
-    "rbs_gauss_kernel_ms",
+    "rbs_gauss_kernel_ms", "rbs_gauss_submit", "rbs_gauss_submit_f64", "rbs_gauss_result",
 )
 
 
@@ -262,5 +262,11 @@ def load():
     lib.rbs_gauss_get_moments.argtypes = [H, dp, ip]
     lib.rbs_gauss_kernel_ms.restype = C.c_int32
     lib.rbs_gauss_kernel_ms.argtypes = [H, fp]
+    lib.rbs_gauss_submit.restype = C.c_int32
+    lib.rbs_gauss_submit.argtypes = [H, fp]
+    lib.rbs_gauss_submit_f64.restype = C.c_int32
+    lib.rbs_gauss_submit_f64.argtypes = [H, dp]
+    lib.rbs_gauss_result.restype = C.c_int32
+    lib.rbs_gauss_result.argtypes = [H, dp, dp]
     _lib = lib
     return lib

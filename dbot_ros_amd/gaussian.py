@@ -7,8 +7,9 @@
 The filter is this project's restatement (upstream's fl / dbot are not
 vendored, so parity with upstream is unpinned): an unscented-transform Gaussian filter whose
 sigma poses are rendered and reduced on the sensor's device (rbs_gauss_* in
-librbsensor_mi355x.so) with the D x D algebra on the host inside the library, one host
-synchronisation per frame.  Like DeviceParticleTracker, states cross the C-ABI in model
+librbsensor_mi355x.so).  track() does the D x D algebra on the host inside the library, one host
+synchronisation per frame; submit() / result() run the whole step on the device with up to two
+frames in flight.  Like DeviceParticleTracker, states cross the C-ABI in model
 coordinates; this class does the center_object_frame conversion and the moving average.
 """
 import ctypes as C
@@ -147,6 +148,32 @@ class GaussianTracker:
             rc = self._lib.rbs_gauss_track(self._g, img.ctypes.data_as(C.POINTER(C.c_float)), out.ctypes.data_as(dp),
                                            cov.ctypes.data_as(dp))
         self.sensor._check(rc)
+        return self._finish(out, cov)
+
+    def submit(self, image=None):
+        """Enqueue one frame (rbs_gauss_submit: the whole filter step on the device) and return at once; at most two
+        frames may be in flight.  result() hands out the estimates in submission order.  image: as track()."""
+        self._live()
+        if image is None:
+            rc = self._lib.rbs_gauss_submit(self._g, None)
+        elif isinstance(image, np.ndarray) and image.dtype == np.float64:
+            img = np.ascontiguousarray(image, dtype=np.float64).ravel()
+            rc = self._lib.rbs_gauss_submit_f64(self._g, img.ctypes.data_as(C.POINTER(C.c_double)))
+        else:
+            img = np.ascontiguousarray(image, dtype=np.float32).ravel()
+            rc = self._lib.rbs_gauss_submit(self._g, img.ctypes.data_as(C.POINTER(C.c_float)))
+        self.sensor._check(rc)   # (the library has staged the frame: the buffer is the caller's again)
+
+    def result(self):
+        """The moving-average estimate of the oldest submitted frame (rbs_gauss_result); covariance is updated here."""
+        self._live()
+        out = np.empty(self.D)
+        cov = np.empty((self.D, self.D))
+        dp = C.POINTER(C.c_double)
+        self.sensor._check(self._lib.rbs_gauss_result(self._g, out.ctypes.data_as(dp), cov.ctypes.data_as(dp)))
+        return self._finish(out, cov)
+
+    def _finish(self, out, cov):
         self.default, self._cov = out, cov
         est = self._from_model(out)
         rate = self.params.moving_average_update_rate
@@ -204,7 +231,7 @@ class GaussianTracker:
         return lam, out[iu[0].size:].copy()
 
     def kernel_ms(self):
-        """Device ms of the last frame: (render, moments, reduction)."""
+        """Device ms of the last frame: (render, moments, reduction; after submit / result: reduction + update)."""
         self._live()
         out = (C.c_float * 3)()
         self.sensor._check(self._lib.rbs_gauss_kernel_ms(self._g, out))

@@ -63,6 +63,27 @@ public:
         State model(parts_);
         covariance_.resize(static_cast<size_t>(12 * parts_) * static_cast<size_t>(12 * parts_));
         check(rbs_gauss_track_f64(g_, image.data(), model.data().data(), covariance_.data()));
+        return averaged(model);
+    }
+    /// The same frame in two halves (rbs_gauss_submit_f64 / rbs_gauss_result), the whole filter step on the
+    /// device: a caller that has the next image before it needs this estimate keeps up to two frames in flight.
+    void submit(const Obsrv& image)
+    {
+        check(rbs_gauss_submit_f64(g_, image.data()));
+    }
+    State result()
+    {
+        State model(parts_);
+        covariance_.resize(static_cast<size_t>(12 * parts_) * static_cast<size_t>(12 * parts_));
+        check(rbs_gauss_result(g_, model.data().data(), covariance_.data()));
+        return averaged(model);
+    }
+    /// The belief's covariance after the last frame: (12 parts)^2 reals, row-major, model coordinates.
+    const std::vector<Real>& covariance() const { return covariance_; }
+
+private:
+    State averaged(const State& model)
+    {
         State est = shift(model, -1.0);
         if (!have_average_) { average_ = est; have_average_ = true; }
         else
@@ -70,10 +91,6 @@ public:
                 average_.data()[k] = rate_ * est.data()[k] + (1.0 - rate_) * average_.data()[k];
         return average_;
     }
-    /// The belief's covariance after the last frame: (12 parts)^2 reals, row-major, model coordinates.
-    const std::vector<Real>& covariance() const { return covariance_; }
-
-private:
     void check(int32_t rc) const
     {
         if (rc != RBS_OK) throw std::runtime_error(std::string("GaussianTracker: ") + rbs_last_error(sensor_->handle()));

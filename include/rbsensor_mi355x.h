@@ -612,8 +612,25 @@ int32_t rbs_gauss_get_render(rbs_gauss* g, int32_t k, float* out);
  * upper triangle of Lambda - I row-major (a <= b), then eta; *n := NE.  RBS_ERR_INVALID_ARGUMENT before the
  * first frame or for a NULL pointer ... */
 int32_t rbs_gauss_get_moments(rbs_gauss* g, double* out, int32_t* n);
-/* ... and its device time in ms: [0] render, [1] moments, [2] reduction (HIP events). */
+/* ... and its device time in ms: [0] render, [1] moments, [2] reduction (HIP events); a frame of
+ * rbs_gauss_submit: [2] is the reduction + update kernel.  These five describe the last COMPLETED
+ * frame, whichever path ran it, and return RBS_ERR_INVALID_ARGUMENT while frames are in flight. */
 int32_t rbs_gauss_kernel_ms(rbs_gauss* g, float* out3);
+
+/* The same frame in two halves, with the whole filter step on the device (predict, Cholesky and sigma
+ * poses in one kernel, the update and re-centring in another; the belief stays in device memory):
+ * rbs_gauss_submit enqueues one frame and returns at once (the caller's buffer is free on return);
+ * rbs_gauss_result hands out the estimates in submission order, as rbs_gauss_track would have
+ * (out_cov may be NULL).  At most two frames in flight; a third submit, a result with nothing in
+ * flight, and rbs_gauss_track or inspection while frames are in flight: RBS_ERR_INVALID_ARGUMENT.
+ * A frame whose algebra fails returns from rbs_gauss_result with rbs_gauss_track's code and message
+ * for that condition, as does a frame in flight behind it; a failure half-way through submit drains
+ * the stream.  Either way the tracker refuses frames until rbs_gauss_initialize (which also drops
+ * frames still in flight).  At a frame boundary rbs_gauss_track and submit / result interleave: the
+ * belief carries over both ways. */
+int32_t rbs_gauss_submit(rbs_gauss* g, const float* frame);   /* NULL: a frame staged by rbs_set_observation* */
+int32_t rbs_gauss_submit_f64(rbs_gauss* g, const double* frame);
+int32_t rbs_gauss_result(rbs_gauss* g, double* out_state, double* out_cov);
 
 #ifdef __cplusplus
 }

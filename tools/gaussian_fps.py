@@ -2,11 +2,13 @@
 (tests/gauss_twin.py, numpy + the oracle's renderer, one core) beside it.  Prints ONE JSON line:
 
     {"tool": "gaussian_fps", "cases": [{"case", "size", "bodies", "sigma_poses", "fps", "ms_per_frame",
-      "device_ms": {"render", "moments", "reduce"}, "twin_fps"}, ...]}
+      "device_ms": {"render", "moments", "reduce"}, "submit_fps", "lookahead_fps", "twin_fps"}, ...]}
 
 Cases: M1 and [M1, M2, M3] at 640x480, M4 at 1280x960; synthetic frames of scenarios.make_frames
 (occluding slab, 5 % NaN).  device_ms: the library's HIP events around its three kernels, averaged
-over the timed frames.  Usage: python tools/gaussian_fps.py [--frames N] [--warmup W] [--twin-frames T]
+over the timed frames.  fps: rbs_gauss_track frame by frame (the D x D algebra on the host); submit_fps:
+rbs_gauss_submit + rbs_gauss_result frame by frame (the whole step on the device); lookahead_fps: submit k + 1
+before result k (two frames in flight).  Usage: python tools/gaussian_fps.py [--frames N] [--warmup W] [--twin-frames T]
 """
 import os
 
@@ -53,6 +55,25 @@ def run_case(name, meshes, cols, rows, n_frames, warmup, twin_frames):
             ms += tracker.kernel_ms()
         wall = time.perf_counter() - t0
         n_sigma = len(tracker.sigma_poses())
+        walls = {}
+        for mode in ("submit", "lookahead"):
+            tracker.initialize([tracker._from_model(gt.truth_state(frames[0][0]))])
+            for _, y in frames[:warmup]:
+                tracker.submit(y)
+                tracker.result()
+            ys = [y for _, y in frames[warmup:]]
+            t0 = time.perf_counter()
+            if mode == "submit":
+                for y in ys:
+                    tracker.submit(y)
+                    tracker.result()
+            else:
+                tracker.submit(ys[0])
+                for k in range(len(ys)):
+                    if k + 1 < len(ys):
+                        tracker.submit(ys[k + 1])
+                    tracker.result()
+            walls[mode] = time.perf_counter() - t0
     finally:
         tracker.close()
         sensor.close()
@@ -65,6 +86,7 @@ def run_case(name, meshes, cols, rows, n_frames, warmup, twin_frames):
     return {"case": name, "size": f"{cols}x{rows}", "bodies": len(meshes), "sigma_poses": n_sigma,
             "fps": round(n_frames / wall, 1), "ms_per_frame": round(1e3 * wall / n_frames, 4),
             "device_ms": {k: round(float(v) / n_frames, 4) for k, v in zip(("render", "moments", "reduce"), ms)},
+            "submit_fps": round(n_frames / walls["submit"], 1), "lookahead_fps": round(n_frames / walls["lookahead"], 1),
             "twin_fps": round(twin_frames / twin_wall, 3)}
 
 
