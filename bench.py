@@ -11,7 +11,11 @@ parent slot (permutation: no occlusion plane is read twice, the worst case for H
 in HBM before the timed region, device-pointer API.  `--steps K` is the number of timed steps in all
 (up to REPEATS regions, median region -> `ms_per_step`); `--dump-outputs DIR` writes the last timed
 step's log-likelihoods as DIR/loglikes.npy (seeded inputs: the same for the same arguments, run after
-run).  The same JSON line carries, as flat keys,
+run).
+
+A plain run does only what `value` needs: set-up, warm-up, the timed steps, --dump-outputs, one JSON
+line of the contract's keys.  Everything else the bench measures or checks runs with `--full` only,
+after the headline, and the same JSON line then carries, as flat keys,
 
   host_api_*      the SAME steps through the host-pointer API the reference's filter would call:
                   frame upload, pose upload and log-likelihood download inside the clock
@@ -29,20 +33,23 @@ run).  The same JSON line carries, as flat keys,
                   dominant and HBM bound: algorithmic bytes / its live duration vs 8 TB/s
   cpu_baseline    the CPU oracle (reference CPU-path semantics) on this host: 1 thread (as dbot's
                   CPU model runs) and all cores
+  configs / sweep / filter_step / exact_occlusion: the other BASELINE configurations, the moving-object
+                  legs, the multi-rank step on one rank, occlusion_mode REFERENCE
 
 With `torch.distributed.run` (--gpus N, one rank per GPU) a step is SURVEY 8(e)'s whole exchange: each rank's
 2 000-particle shard (weak scaling) evaluated with GLOBAL parent slots -- the ranks' handles are attached to each
 other over HIP IPC, a parent on another GPU is read in place over xGMI --, the RCCL all-gather of the
 log-likelihoods, multinomial resampling over all ranks' particles and this rank's plan in one library call
 (rbs_peer_resample), shared remote parents staged once; then the same step at C3 / C4's per-GPU sizes and the
-one-handle tracker over the job's devices (a time-limited child process).  Ranks that cannot attach fall back to
-shards with local parents + the all-gather, and the line says so (`peer_step`).
+one-handle tracker over the job's devices (a time-limited child process) -- with `--full`, which also runs the multi-GPU
+self-check before anything is timed.  Ranks that cannot attach fall back to shards with local parents + the all-gather,
+and the line says so (`peer_step`).
 
 `python bench.py --gpus N` WITHOUT torch.distributed.run (WORLD_SIZE unset) measures the other
 multi-GPU form: ONE process, one handle over N devices (rbs_config.n_devices; --device-ids to
 list them, an ordinal may repeat on a one-GPU box): N x 2 000 particles per step through
 rbs_loglikes from host memory (frame + pose upload and log-likelihood download inside the
-clock), plus the sharded device tracker's frames/s.
+clock), plus (`--full`) the sharded device tracker's frames/s.
 """
 import argparse
 import csv
@@ -126,7 +133,12 @@ def parse():
     ap.add_argument("--occlusion", default=None, choices=["reference", "device"],
                     help="rbs_config.occlusion_mode of the headline run (default: the library's)")
     ap.add_argument("--slab-px", type=int, default=0, help="floats per occlusion slot (rbs_config.state_slab_px; 0 = whole planes)")
-    ap.add_argument("--quick", action="store_true", help="headline only: no dense / f64 / host / tracker / cpu / pmc legs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else: its kernel times and roofline (live counters), the dense / other-precision / "
+                         "occlusion-mode / configuration / sweep / host / tracker legs, the CPU baseline; several ranks: the self-check and "
+                         "the multi-rank legs (without it: set-up, warm-up, the timed steps, --dump-outputs and the line, nothing else)")
+    ap.add_argument("--quick", action="store_true",
+                    help="with --full: the headline's kernel times and roofline (committed counters) only: no dense / f64 / host / tracker / cpu / pmc legs")
     ap.add_argument("--no-dense-leg", action="store_true", help="skip the whole-plane (state_layout=dense) comparison run")
     ap.add_argument("--no-f32-leg", action="store_true", help="skip the opt-in float32-likelihood comparison run")
     ap.add_argument("--no-host-leg", action="store_true")
@@ -154,9 +166,9 @@ def parse():
         setattr(a, k, v)
     if a.steps < 1 or a.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
-    if a.quick or a.config not in (None, "c1"):
+    if a.quick or a.config not in (None, "c1") or not a.full:
         a.no_dense_leg = a.no_f32_leg = a.no_host_leg = a.no_tracker_fps = a.no_cpu_baseline = a.no_configs_leg = a.no_sweep_leg = True
-        a.no_pmc = a.no_pmc or a.quick
+        a.no_pmc = a.no_pmc or a.quick or not a.full
     return a
 
 
@@ -1255,39 +1267,31 @@ def in_process_multi_device(a):
             raise SystemExit("non-finite log-likelihoods in the timed run")
         if a.dump_outputs:             # the last timed step's log-likelihoods
             dump_outputs(a.dump_outputs, {"loglikes": ll})
-        # the dominant kernel on the handle's first device (every device runs the same launch on its shard)
-        g.set_timing_every(2)
-        for i in range(64):
-            step(i)
-        g.synchronize()
-        call_ms, copy_ms, n_used = g.timing_summary(64)
-        raster_ms = g.raster_kernel_ms(64)
-        g.set_timing_every(8)
-        # the sharded device tracker on the same handle
-        trans = ObjectTransitionBuilder(ObjectTransitionBuilder.Parameters(part_count=nb)).build()
-        tr = DeviceParticleTracker(trans, g, om, ParticleTrackerBuilder.Parameters(evaluation_count=n * nb), device_rng=True, seed=1)
-        init = np.zeros(12 * nb)
-        for b in range(nb):
-            Rt = W.truths[0][b]
-            init[12 * b + 3:12 * b + 6] = pose.matrix_to_rotvec(Rt[:9].reshape(3, 3))
-            init[12 * b:12 * b + 3] = Rt[9:] - Rt[:9].reshape(3, 3) @ om.centers[b]
-        tr.initialize([init])
-        tr.track(W.frames[0])
-        nf = min(30, len(W.frames) - 1) or 1
-        t0 = time.perf_counter()
-        for k in range(1, nf + 1):
-            tr.track(W.frames[k % len(W.frames)])
-        fps = nf / (time.perf_counter() - t0)
-        tr.close()
-    alg_bytes = (2.0 if a.update else 1.0) * 4.0 * a.rows * a.cols * a.particles     # per device launch, SURVEY 8d
-    # whole planes: the copy kernel is the dominant one and HBM bound.  Windowed planes: the raster kernel
-    # (the windowed copy kernel runs BESIDE it and moves ~1 % of the algorithmic bytes: pricing it with
-    # them would report several times the HBM peak)
-    copy_dominant = bool(a.update) and a.layout == "dense" and copy_ms > raster_ms
-    roof, pmc_live, copy_traffic = roofline_for(a, a.particles, raster_ms, copy_ms, alg_bytes, copy_dominant, not a.no_pmc and not a.quick)
-    roof.update({"counters_live": bool(pmc_live), "counters_note": "instruction counts from a single-device pass of the same per-device launch",
-                 "kernel_launches_averaged": n_used, "raster_kernel_ms": raster_ms, "copy_kernel_ms": copy_ms,
-                 "call_ms_launch_stream": call_ms, "per_device": True, "algorithmic_bytes_per_launch": alg_bytes})
+        if a.full:
+            # the dominant kernel on the handle's first device (every device runs the same launch on its shard)
+            g.set_timing_every(2)
+            for i in range(64):
+                step(i)
+            g.synchronize()
+            call_ms, copy_ms, n_used = g.timing_summary(64)
+            raster_ms = g.raster_kernel_ms(64)
+            g.set_timing_every(8)
+            # the sharded device tracker on the same handle
+            trans = ObjectTransitionBuilder(ObjectTransitionBuilder.Parameters(part_count=nb)).build()
+            tr = DeviceParticleTracker(trans, g, om, ParticleTrackerBuilder.Parameters(evaluation_count=n * nb), device_rng=True, seed=1)
+            init = np.zeros(12 * nb)
+            for b in range(nb):
+                Rt = W.truths[0][b]
+                init[12 * b + 3:12 * b + 6] = pose.matrix_to_rotvec(Rt[:9].reshape(3, 3))
+                init[12 * b:12 * b + 3] = Rt[9:] - Rt[:9].reshape(3, 3) @ om.centers[b]
+            tr.initialize([init])
+            tr.track(W.frames[0])
+            nf = min(30, len(W.frames) - 1) or 1
+            t0 = time.perf_counter()
+            for k in range(1, nf + 1):
+                tr.track(W.frames[k % len(W.frames)])
+            fps = nf / (time.perf_counter() - t0)
+            tr.close()
     line = {
         "metric": "particle-likelihoods/sec @640x480" if (a.cols, a.rows) == (640, 480) else f"particle-likelihoods/sec @{a.cols}x{a.rows}",
         "value": n / (ms * 1e-3), "unit": "particle-likelihoods/s", "n_gpus": a.gpus, "steps": a.steps, "warmup": a.warmup,
@@ -1299,8 +1303,18 @@ def in_process_multi_device(a):
                                f"{a.cols}x{a.rows}, mesh {a.mesh} ({n_tri} triangles), precision {a.precision}",
                    "particles_per_gpu": a.particles, "resolution": [a.cols, a.rows], "triangles": int(n_tri),
                    "sharding": f"particles/{a.gpus} inside the handle: peer reads of remote parents, RCCL all-gather in the tracker"},
-        "tracker_fps_sharded": fps, "tracker_particles": n, "roofline": roof,
     }
+    if a.full:
+        alg_bytes = (2.0 if a.update else 1.0) * 4.0 * a.rows * a.cols * a.particles     # per device launch, SURVEY 8d
+        # whole planes: the copy kernel is the dominant one and HBM bound.  Windowed planes: the raster kernel
+        # (the windowed copy kernel runs BESIDE it and moves ~1 % of the algorithmic bytes: pricing it with
+        # them would report several times the HBM peak)
+        copy_dominant = bool(a.update) and a.layout == "dense" and copy_ms > raster_ms
+        roof, pmc_live, copy_traffic = roofline_for(a, a.particles, raster_ms, copy_ms, alg_bytes, copy_dominant, not a.no_pmc and not a.quick)
+        roof.update({"counters_live": bool(pmc_live), "counters_note": "instruction counts from a single-device pass of the same per-device launch",
+                     "kernel_launches_averaged": n_used, "raster_kernel_ms": raster_ms, "copy_kernel_ms": copy_ms,
+                     "call_ms_launch_stream": call_ms, "per_device": True, "algorithmic_bytes_per_launch": alg_bytes})
+        line.update({"tracker_fps_sharded": fps, "tracker_particles": n, "roofline": roof})
     if a.gpus == 1 and not a.no_cpu_baseline and not a.quick:
         line["cpu_baseline"] = cpu_baseline(om, cam, P, W.truths[0], W.frames[0], a.cpu_seconds)
     print(json.dumps(line), flush=True)
@@ -1575,10 +1589,11 @@ def main():
         guard.best = fb_line
         guard.arm(float(os.environ.get("RBS_BENCH_ATTACH_TIMEOUT", "240")), "rbs_ipc_attach / the multi-GPU self-check / the attached step")
     if world > 1:
-        try:
-            selfcheck = multi_gpu_selfcheck(a, dev, stream, dist, backend, world, rank)
-        except Exception as e:   # noqa: BLE001 -- the check must not take the headline down
-            selfcheck = {"multi_gpu_equals_single": False, "multi_gpu_check_diagnosis": f"self-check raised {e!r}"} if rank == 0 else {}
+        if a.full:
+            try:
+                selfcheck = multi_gpu_selfcheck(a, dev, stream, dist, backend, world, rank)
+            except Exception as e:   # noqa: BLE001 -- the check must not take the headline down
+                selfcheck = {"multi_gpu_equals_single": False, "multi_gpu_check_diagnosis": f"self-check raised {e!r}"} if rank == 0 else {}
         try:
             sensor, run = setup_peer_run(a, om, cam, P, W, dev, stream, dist, backend, world)
             d_out, d_all = run.step.d_out, run.step.d_all
@@ -1629,10 +1644,11 @@ def main():
         raise SystemExit("non-finite log-likelihoods in the timed run")
     if a.dump_outputs and rank == 0:   # the last timed step's log-likelihoods (several ranks: every rank's, gathered)
         dump_outputs(a.dump_outputs, {"loglikes": d_all.cpu().numpy() if world > 1 else ll})
-    # dominant-kernel durations: a separate pass of 512 launches, 256 of them bracketed by events
-    raster_ms, copy_ms, call_ms, n_used = run.kernel_times(512)
-    windows = np.array([sensor.get_window(s_) for s_ in range(0, n, max(1, n // 64))])
-    win_frac = float(np.mean(np.maximum(0, windows[:, 2] - windows[:, 0]) * np.maximum(0, windows[:, 3] - windows[:, 1]))) / (a.rows * a.cols)
+    if a.full:
+        # dominant-kernel durations: a separate pass of 512 launches, 256 of them bracketed by events
+        raster_ms, copy_ms, call_ms, n_used = run.kernel_times(512)
+        windows = np.array([sensor.get_window(s_) for s_ in range(0, n, max(1, n // 64))])
+        win_frac = float(np.mean(np.maximum(0, windows[:, 2] - windows[:, 0]) * np.maximum(0, windows[:, 3] - windows[:, 1]))) / (a.rows * a.cols)
     peer_stats, peer_legs = None, {}
     if world > 1:
         # the headline is measured: from here on the watchdog would print IT (without the legs that follow)
@@ -1649,19 +1665,20 @@ def main():
     if world > 1 and peer_ok:
         peer_stats = run.stats()
         peer_stats["peer_step"] = "ok"
-        # the same step with FLATTENED weights (temperature = the spread of the log-likelihoods): many distinct parents,
-        # a large share of them on other ranks and unshared -- the case that exercises the in-place reads over xGMI
-        # (the filter's own weights on these synthetic poses leave one or two survivors per step)
-        run.reset_stats()
-        run.step.temperature = max(1.0, float(d_all.std().item()))
-        run.timed(a.warmup + 3, 0, barrier=dist.barrier)
-        run.reset_stats()
-        el2 = run.timed(a.steps, 0, barrier=dist.barrier)
-        t2 = torch.tensor([el2], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
-        dist.all_reduce(t2, op=dist.ReduceOp.MAX)
-        peer_stats.update({"spread_parents_" + k_: v_ for k_, v_ in run.stats().items()})
-        peer_stats["spread_parents_value"] = n * world * a.steps / float(t2.item())
-        peer_stats["spread_parents_temperature"] = run.step.temperature
+        if a.full:
+            # the same step with FLATTENED weights (temperature = the spread of the log-likelihoods): many distinct parents,
+            # a large share of them on other ranks and unshared -- the case that exercises the in-place reads over xGMI
+            # (the filter's own weights on these synthetic poses leave one or two survivors per step)
+            run.reset_stats()
+            run.step.temperature = max(1.0, float(d_all.std().item()))
+            run.timed(a.warmup + 3, 0, barrier=dist.barrier)
+            run.reset_stats()
+            el2 = run.timed(a.steps, 0, barrier=dist.barrier)
+            t2 = torch.tensor([el2], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
+            dist.all_reduce(t2, op=dist.ReduceOp.MAX)
+            peer_stats.update({"spread_parents_" + k_: v_ for k_, v_ in run.stats().items()})
+            peer_stats["spread_parents_value"] = n * world * a.steps / float(t2.item())
+            peer_stats["spread_parents_temperature"] = run.step.temperature
         torch.cuda.synchronize()
         dist.barrier()                     # every rank is done reading its peers' planes: handles may go
         sensor.close()
@@ -1691,10 +1708,6 @@ def main():
         return
 
     alg_bytes = (2.0 if a.update else 1.0) * 4.0 * a.rows * a.cols * n  # per launch, SURVEY 8d
-    # whole planes: the copy kernel is the dominant one and HBM bound.  Windowed planes: the raster kernel
-    # (the windowed copy kernel runs BESIDE it and moves ~1 % of the algorithmic bytes: pricing it with
-    # them would report several times the HBM peak)
-    copy_dominant = bool(a.update) and a.layout == "dense" and copy_ms > raster_ms
     out = headline(a, world, n, n_tri, region_ms, None if world == 1 else ("ipc" if peer_ok else "local"))
     if world > 1:
         if not peer_ok:
@@ -1703,16 +1716,21 @@ def main():
         out.update(peer_stats)
         out.update(peer_legs)
     single = world == 1
-    # (several ranks: rank 0's device; live counter passes only on request -- the other ranks would
-    # wait minutes at the next collective -- otherwise the committed counters of the same launch)
-    roof, pmc_live, copy_traffic = roofline_for(a, n, raster_ms, copy_ms, alg_bytes, copy_dominant,
-                                                not a.no_pmc and (single or os.environ.get("RBS_BENCH_PMC_MULTI") == "1"))
-    roof.update({"counters_live": bool(pmc_live), "kernel_launches_averaged": n_used,
-                 "raster_kernel_ms": raster_ms, "copy_kernel_ms": copy_ms, "call_ms_launch_stream": call_ms,
-                 "copy_kernel_hbm_bytes_per_launch": copy_traffic,
-                 "state_layout": a.layout, "stored_window_fraction_of_plane": win_frac,
-                 "algorithmic_bytes_per_launch": alg_bytes})
-    out["roofline"] = roof
+    if a.full:
+        # whole planes: the copy kernel is the dominant one and HBM bound.  Windowed planes: the raster kernel
+        # (the windowed copy kernel runs BESIDE it and moves ~1 % of the algorithmic bytes: pricing it with
+        # them would report several times the HBM peak)
+        copy_dominant = bool(a.update) and a.layout == "dense" and copy_ms > raster_ms
+        # (several ranks: rank 0's device; live counter passes only on request -- the other ranks would
+        # wait minutes at the next collective -- otherwise the committed counters of the same launch)
+        roof, pmc_live, copy_traffic = roofline_for(a, n, raster_ms, copy_ms, alg_bytes, copy_dominant,
+                                                    not a.no_pmc and (single or os.environ.get("RBS_BENCH_PMC_MULTI") == "1"))
+        roof.update({"counters_live": bool(pmc_live), "kernel_launches_averaged": n_used,
+                     "raster_kernel_ms": raster_ms, "copy_kernel_ms": copy_ms, "call_ms_launch_stream": call_ms,
+                     "copy_kernel_hbm_bytes_per_launch": copy_traffic,
+                     "state_layout": a.layout, "stored_window_fraction_of_plane": win_frac,
+                     "algorithmic_bytes_per_launch": alg_bytes})
+        out["roofline"] = roof
     if world == 1:
         sensor.close()
 
@@ -1889,7 +1907,7 @@ def main():
     # ---- SURVEY 8(d)'s own figures first: `value` stays the bench contract's (inputs resident in HBM when the clock
     # starts); the metric as SURVEY 8(d) words it -- pose upload and log-likelihood download inside the clock -- is host_pointer_value,
     # and through the plugin surface the reference would call (the double image inside the clock as well) plugin_api_value
-    if single:
+    if single and a.full:
         lead = {"resident_value": out["value"],
                 "host_pointer_value": out.get("host_api_native_loglikes_only_value", out.get("host_api_loglikes_only_value")),
                 "plugin_api_value": out.get("plugin_api_value"), "plugin_api_borrowed_value": out.get("plugin_api_borrowed_value"),

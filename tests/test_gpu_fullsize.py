@@ -289,6 +289,31 @@ def test_samples_exactly_on_silhouette_edges(gpu_lib, variant):
                 f"{variant} shift {shift}: {(dg.view(np.uint32) != do.view(np.uint32)).sum()} depth pixels differ"
 
 
+def test_plain_bench_line_is_the_headline_alone(gpu_lib, tmp_path):
+    """bench.py without --full: set-up, warm-up, the timed steps, --dump-outputs and the contract's line -- no kernel-time
+    pass, roofline, leg or CPU baseline (those run with --full only)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "40", "--warmup", "5",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=300, cwd=root)
+    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, lines
+    line = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "config"):
+        assert key in line, key
+    assert line["n_gpus"] == 1 and line["steps"] == 40 and line["warmup"] == 5 and line["dtype"] == "f64"
+    assert line["timed_regions"] == 2 and abs(line["value"] - 2000 / (line["ms_per_step"] * 1e-3)) <= 1e-6 * line["value"]
+    for key in ("roofline", "survey_8d", "cpu_baseline", "host_api_value", "f32_value", "dense_value", "exact_occlusion_value",
+                "c2_value", "sweep_value", "filter_step_value", "tracker_fps_2000"):
+        assert key not in line, key
+    ll = np.load(tmp_path / "loglikes.npy")
+    assert ll.dtype == np.float64 and ll.shape == (2000,) and np.isfinite(ll).all()
+
+
 def test_nccl_all_gather_smoke(gpu_lib):
     """torch.distributed's nccl backend (= RCCL) all-gather of log-likelihood shards across the
     visible devices, as bench.py --gpus N runs it; needs two or more GPUs."""
@@ -322,7 +347,7 @@ def test_bench_line_of_two_ranks_on_one_gpu(gpu_lib):
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
                         "--master-addr", "127.0.0.1", "--master-port", str(29100 + os.getpid() % 800),
                         os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--particles", "256",
-                        "--no-configs-leg", "--resample-temperature", "40"],
+                        "--full", "--no-configs-leg", "--resample-temperature", "40"],
                        capture_output=True, text=True, timeout=900, cwd=root, env=env)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -355,7 +380,7 @@ def test_bench_line_when_the_ranks_cannot_attach(gpu_lib):
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
                         "--master-addr", "127.0.0.1", "--master-port", str(29950 + os.getpid() % 40),
                         os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--particles", "256",
-                        "--no-configs-leg"],
+                        "--full", "--no-configs-leg"],
                        capture_output=True, text=True, timeout=900, cwd=root, env=env)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

@@ -2,7 +2,7 @@
 # A/B of the two occlusion modes on one GPU (bench.py --quick): C1 twice ("all": + the other configurations);
 # further arguments: build_variants/<name>.so to run the reference mode with as well.
 one() {   # mode, bench args, library
-env ${3:+RBS_LIB_PATH=$PWD/build_variants/$3.so} python bench.py --quick $2 --occlusion $1 2>/dev/null | python -c "
+env ${3:+RBS_LIB_PATH=$PWD/build_variants/$3.so} python bench.py --full --quick $2 --occlusion $1 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     l=l.strip()

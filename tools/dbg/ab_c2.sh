@@ -1,6 +1,6 @@
 #!/bin/bash
 # round 6, VERDICT r5 #6: C2's windowed copy -- the strip list (default) against the walk over the whole region (RBS_COPY_WALK=1)
-one() { env $1 python bench.py --quick --config c2 2>/dev/null | python -c "
+one() { env $1 python bench.py --full --quick --config c2 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

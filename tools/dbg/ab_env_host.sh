@@ -1,7 +1,7 @@
 # A/B of environment settings on the host-pointer and tracker legs (run on the GPU box):
 #   bash tools/dbg/ab_env_host.sh "RBS_AUX_DEFER=0" "RBS_AUX_DEFER=1" ...
 for e in "$@"; do
-env $e python bench.py --no-dense-leg --no-f32-leg --no-configs-leg --no-pmc --no-cpu-baseline ${EXTRA:-} --steps 100 2>/dev/null | python -c "
+env $e python bench.py --full --no-dense-leg --no-f32-leg --no-configs-leg --no-pmc --no-cpu-baseline ${EXTRA:-} --steps 100 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -1,6 +1,6 @@
 #!/bin/bash
 # occlusion_mode REFERENCE on C1: whole planes against window-sized slabs (packed rows: the ages' cache lines are fully used)
-one() { python bench.py --quick --occlusion $1 --slab-px $2 2>/dev/null | python -c "
+one() { python bench.py --full --quick --occlusion $1 --slab-px $2 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     l=l.strip()

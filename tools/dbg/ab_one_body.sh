@@ -1,6 +1,6 @@
 #!/bin/bash
 # round 6, VERDICT r5 #7: the single-body specialisation of the raster kernel (RBS_ONE_BODY=1), scan unroll 2 / 3 / 4
-one() { env $1 python bench.py --quick 2>/dev/null | python -c "
+one() { env $1 python bench.py --full --quick 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

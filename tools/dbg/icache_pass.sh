@@ -2,8 +2,8 @@
 # instruction-cache counters of the raster kernel (run on the GPU box): bash tools/dbg/icache_pass.sh [bench args]
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 out=gpurun_out/icache; rm -rf $out; mkdir -p $out
-rocprofv3 --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE --kernel-trace --output-format csv -d $out/a -o a -- python bench.py --quick --steps 20 --warmup 3 "$@" > $out/a.log 2>&1
-rocprofv3 --pmc SQ_IFETCH SQ_WAIT_INST_ANY SQ_WAVE_CYCLES SQ_INSTS_VALU --kernel-trace --output-format csv -d $out/b -o b -- python bench.py --quick --steps 20 --warmup 3 "$@" > $out/b.log 2>&1
+rocprofv3 --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE --kernel-trace --output-format csv -d $out/a -o a -- python bench.py --full --quick --steps 20 --warmup 3 "$@" > $out/a.log 2>&1
+rocprofv3 --pmc SQ_IFETCH SQ_WAIT_INST_ANY SQ_WAVE_CYCLES SQ_INSTS_VALU --kernel-trace --output-format csv -d $out/b -o b -- python bench.py --full --quick --steps 20 --warmup 3 "$@" > $out/b.log 2>&1
 python - "$out" <<'PY'
 import csv, glob, sys, collections
 out = sys.argv[1]

@@ -10,10 +10,10 @@ for l in sys.stdin:
 "; }
 for p in f64 f32; do
   for c in c1 c1_readonly c2 c3_slice c4_slice default_res; do
-    python bench.py --config $c --quick --precision $p 2>/dev/null | row "$c $p"
+    python bench.py --full --config $c --quick --precision $p 2>/dev/null | row "$c $p"
   done
-  python bench.py --quick --layout dense --precision $p 2>/dev/null | row "c1 dense $p"
-  python bench.py --quick --particles 200000 --steps 10 --warmup 2 --precision $p 2>/dev/null | row "c3 200000 slabs $p"
+  python bench.py --full --quick --layout dense --precision $p 2>/dev/null | row "c1 dense $p"
+  python bench.py --full --quick --particles 200000 --steps 10 --warmup 2 --precision $p 2>/dev/null | row "c3 200000 slabs $p"
 done
 python tools/tracker_fps.py 200,2000,20000,100000 2>/dev/null | python -c "
 import sys, json

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Condense a rocprofv3 --kernel-trace --hip-runtime-trace run of bench.py into the headline step's timeline.
 
-    rocprofv3 --kernel-trace --hip-runtime-trace --stats --output-format csv -d OUT -o trace -- python bench.py --quick --steps 20
+    rocprofv3 --kernel-trace --hip-runtime-trace --stats --output-format csv -d OUT -o trace -- python bench.py --full --quick --steps 20
     python tools/step_timeline.py OUT/trace [--steps 4]
 
 A step is one rbs_frame_prep_kernel / rbs_prep_kernel dispatch and the raster and copy kernels after it.  Prints the medians
