@@ -47,7 +47,10 @@ EXPORTS = (
     "rbs_gauss_create", "rbs_gauss_destroy", "rbs_gauss_initialize", "rbs_gauss_track", "rbs_gauss_track_f64",
     "rbs_gauss_get_prior", "rbs_gauss_get_sigma_poses", "rbs_gauss_get_render", "rbs_gauss_get_moments",
     "rbs_gauss_kernel_ms", "rbs_gauss_submit", "rbs_gauss_submit_f64", "rbs_gauss_result",
+    "rbs_find_default_params", "rbs_find_create", "rbs_find_destroy", "rbs_find_run", "rbs_find_get_stage",
+    "rbs_find_stage_ms", "rbs_find_last_error",
 )
+RBS_FIND_SEEDS, RBS_FIND_COARSE, RBS_FIND_CANDIDATES, RBS_FIND_SURVIVORS, RBS_FIND_CHILDREN, RBS_FIND_RESULT = range(6)
 
 
 class RbsTrackerParams(C.Structure):
@@ -72,6 +75,30 @@ class RbsGaussParams(C.Structure):
         ("tail_weight", C.c_double),
         ("uniform_tail_min", C.c_double),
         ("uniform_tail_max", C.c_double),
+    ]
+
+
+class RbsFindParams(C.Structure):
+    _fields_ = [
+        ("coarse_downsampling", C.c_int32),
+        ("seed_stride", C.c_int32),
+        ("min_depth", C.c_double),
+        ("max_depth", C.c_double),
+        ("depth_offset", C.c_double),
+        ("max_seeds", C.c_int32),
+        ("n_rotations", C.c_int32),
+        ("n_candidates", C.c_int32),
+        ("nms_translation", C.c_double),
+        ("nms_angle", C.c_double),
+        ("n_survivors", C.c_int32),
+        ("rounds", C.c_int32),
+        ("children", C.c_int32),
+        ("sigma_translation", C.c_double),
+        ("sigma_angle", C.c_double),
+        ("decay", C.c_double),
+        ("batch", C.c_int32),
+        ("seed", C.c_uint64),
+        ("min_score", C.c_double),
     ]
 
 
@@ -268,5 +295,20 @@ def load():
     lib.rbs_gauss_submit_f64.argtypes = [H, dp]
     lib.rbs_gauss_result.restype = C.c_int32
     lib.rbs_gauss_result.argtypes = [H, dp, dp]
+    lp = C.POINTER(C.c_int64)
+    lib.rbs_find_default_params.restype = None
+    lib.rbs_find_default_params.argtypes = [C.POINTER(RbsFindParams)]
+    lib.rbs_find_create.restype = C.c_int32
+    lib.rbs_find_create.argtypes = [H, C.POINTER(RbsFindParams), C.POINTER(H)]
+    lib.rbs_find_destroy.restype = None
+    lib.rbs_find_destroy.argtypes = [H]
+    lib.rbs_find_run.restype = C.c_int32
+    lib.rbs_find_run.argtypes = [H, fp, C.c_int32, dp, dp, ip, ip]
+    lib.rbs_find_get_stage.restype = C.c_int32
+    lib.rbs_find_get_stage.argtypes = [H, C.c_int32, C.c_int32, dp, dp, lp, lp, dp]
+    lib.rbs_find_stage_ms.restype = C.c_int32
+    lib.rbs_find_stage_ms.argtypes = [H, fp]
+    lib.rbs_find_last_error.restype = C.c_char_p
+    lib.rbs_find_last_error.argtypes = [H]
     _lib = lib
     return lib

@@ -272,6 +272,12 @@ struct rbs_handle {
     const float* snap_occ[rbs::kMaxDevices] = {};   // group: every shard's CURRENT planes / windows as of the start
     const int4* snap_win[rbs::kMaxDevices] = {};    //   of the call being fanned out (shards flip buffers one by one)
     const int4* snap_reg[rbs::kMaxDevices] = {};
+    // ---- the object finder (rbsensor_find.hip) builds its scoring handles from the sensor's creation parameters
+    rbs_config cfg{};                               // as passed to rbs_create; its pointers point into the copies below
+    std::vector<double> cfg_vertices;
+    std::vector<int32_t> cfg_vertex_counts, cfg_triangles, cfg_triangle_counts;
+    int occ_slots = 0;          // occlusion slots allocated: 0 = max_particles; a finder's scoring handle keeps slot 0 only
+                                // (it is only ever called with update = 0 and every index 0)
 };
 
 // RCCL, bound at run time (dlopen): a single-device handle never needs it, and a process that
@@ -1647,6 +1653,21 @@ int32_t create_impl(const rbs_config* cfg, rbs_handle* h)
     }
     for (int b = h->n_bodies; b < rbs::kMaxBodies; ++b) B.tri_begin[b + 1] = (int)n_tri;
     for (int b = 0; b < rbs::kMaxBodies; ++b) B.tri_end[b] = B.tri_begin[b];
+    {   // (the object finder re-creates this configuration at other resolutions: keep it with copies of the mesh)
+        size_t nv = 0, nt = 0;
+        for (int b = 0; b < cfg->n_objects; ++b) { nv += (size_t)cfg->vertex_counts[b]; nt += (size_t)cfg->triangle_counts[b]; }
+        h->cfg = *cfg;
+        h->cfg_vertices.assign(cfg->vertices, cfg->vertices + 3 * nv);
+        h->cfg_vertex_counts.assign(cfg->vertex_counts, cfg->vertex_counts + cfg->n_objects);
+        h->cfg_triangles.assign(cfg->triangles, cfg->triangles + 3 * nt);
+        h->cfg_triangle_counts.assign(cfg->triangle_counts, cfg->triangle_counts + cfg->n_objects);
+        h->cfg.vertices = h->cfg_vertices.data();
+        h->cfg.vertex_counts = h->cfg_vertex_counts.data();
+        h->cfg.triangles = h->cfg_triangles.data();
+        h->cfg.triangle_counts = h->cfg_triangle_counts.data();
+        h->cfg.n_devices = 0;
+        h->cfg.device_ids = nullptr;
+    }
     for (int b = 0; b < h->n_bodies; ++b) {
         const int clusters = (B.tri_begin[b + 1] - B.tri_begin[b]) >> 6;
         h->many_clusters |= clusters > 64 * (rbs::kBlock / 64);   // (more steps of 64 clusters than the block has waves)
@@ -2006,8 +2027,9 @@ int32_t create_impl(const rbs_config* cfg, rbs_handle* h)
     if (h->slab_px >= h->npx) h->slab_px = 0;
     h->plane_stride = h->slab_px ? (size_t)h->slab_px : (size_t)h->npx;
     if (h->exact) h->plane_stride = exact_stride(h->plane_stride);   // (the slots' ages follow their values)
-    RBS_HIP(h, hipMalloc(&h->d_occ[0], occ_alloc_bytes(sizeof(float) * h->plane_stride * h->max_particles)));
-    RBS_HIP(h, hipMalloc(&h->d_occ[1], occ_alloc_bytes(sizeof(float) * h->plane_stride * h->max_particles)));
+    const size_t occ_slots = h->occ_slots > 0 ? (size_t)h->occ_slots : (size_t)h->max_particles;
+    RBS_HIP(h, hipMalloc(&h->d_occ[0], occ_alloc_bytes(sizeof(float) * h->plane_stride * occ_slots)));
+    RBS_HIP(h, hipMalloc(&h->d_occ[1], occ_alloc_bytes(sizeof(float) * h->plane_stride * occ_slots)));
     RBS_HIP(h, hipMalloc(&h->d_err, 2 * sizeof(int)));
     RBS_HIP(h, hipMemset(h->d_err, 0, 2 * sizeof(int)));
     RBS_HIP(h, hipHostMalloc(&h->h_err, 4 * sizeof(int), hipHostMallocDefault));
@@ -2835,7 +2857,7 @@ int32_t rbs_reset(rbs_handle* h)
     }
     RBS_HIP(h, hipMemsetAsync(h->d_err, 0, 2 * sizeof(int), h->stream));
     h->h_err[0] = h->h_err[1] = 0;
-    const size_t n = h->plane_stride * h->max_particles;
+    const size_t n = h->plane_stride * (h->occ_slots > 0 ? (size_t)h->occ_slots : (size_t)h->max_particles);
     hipLaunchKernelGGL(rbs::rbs_fill_kernel, dim3(2048), dim3(256), 0, h->stream, h->d_occ[0], n,
                        (float)h->init_occ);
     // the second buffer too: touches every page now instead of inside the first updating call
@@ -4482,3 +4504,4 @@ int32_t rbs_tracker_get(rbs_tracker* t, double* particles, double* log_weights, 
 
 // The robust Gaussian tracker (rbs_gauss_*): its kernels and host side.
 #include "rbsensor_gauss.hip"
+#include "rbsensor_find.hip"

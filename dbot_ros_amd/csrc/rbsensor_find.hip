@@ -1,0 +1,814 @@
+// rbsensor_find.hip -- the object finder (rbs_find_*, include/rbsensor_mi355x.h).  Included at the
+// end of rbsensor_capi.hip: it scores through handles of its own made from the sensor's configuration
+// (rbs_handle::cfg), so every score comes from the sensor's raster kernels.
+//
+// Per find, on the coarse scoring handle's stream:
+//   rbs_find_subsample_kernel   every f-th pixel of every f-th row of the frame already on the device
+//   rbs_find_seed_kernel        one block: valid seed-grid pixels compacted in row-major order, then thinned
+//   rbs_find_hyp_kernel         hypothesis h -> pose (Super-Fibonacci rotation, seed translation), binary64
+//   (rbs_loglikes_device)       coarse scores, `batch` hypotheses per launch
+//   rbs_find_topk_kernel        per 2 048-item chunk: bitonic sort in LDS, the best k written; repeated until one chunk
+//   rbs_find_nms_kernel         one wave: greedy suppression in candidate order
+//   rbs_find_children_kernel    a round's children (Philox4x32-10 normals), then (rbs_loglikes_device) their scores
+//   rbs_find_select_kernel      each survivor keeps its best child
+// Every order is fixed: the same frame gives the same bits, whatever `batch`.
+#include <climits>
+
+namespace rbf {
+
+constexpr int kTopC = 2048;        // items per top-k chunk (LDS: 16 bytes each; > kMaxCandidates, so every pass at least halves the items)
+constexpr int kTopThreads = 1024;
+constexpr int kMaxCandidates = 1024;
+constexpr int kMaxSurvivors = 64;  // one wave's lanes in the suppression
+constexpr int kSeedThreads = 1024;
+constexpr double kPsi = 1.533751168755204288118041;   // psi^4 = psi + 4 (Alexa 2022)
+constexpr double kTwoPi = 6.283185307179586;
+
+struct HypParams {
+    const double* seeds;   // [n_seeds][4] (u, v, d, pixel)
+    int n_rot;
+    double fx, fy, cx, cy; // coarse K
+    double offset;
+};
+
+// (x, y, z, w) unit quaternion of Super-Fibonacci point i of n, as a row-major rotation matrix
+__device__ __host__ inline void sf_rotation(long i, int n, double* R)
+{
+    const double s = (double)i + 0.5;
+    const double t = s / (double)n;
+    const double r = sqrt(t), Rr = sqrt(1.0 - t);
+    const double a = kTwoPi * s / 1.4142135623730951, b = kTwoPi * s / kPsi;
+    const double x = r * sin(a), y = r * cos(a), z = Rr * sin(b), w = Rr * cos(b);
+    R[0] = 1.0 - 2.0 * (y * y + z * z); R[1] = 2.0 * (x * y - w * z);       R[2] = 2.0 * (x * z + w * y);
+    R[3] = 2.0 * (x * y + w * z);       R[4] = 1.0 - 2.0 * (x * x + z * z); R[5] = 2.0 * (y * z - w * x);
+    R[6] = 2.0 * (x * z - w * y);       R[7] = 2.0 * (y * z + w * x);       R[8] = 1.0 - 2.0 * (x * x + y * y);
+}
+
+__device__ inline void hyp_pose(const HypParams& H, long h, double* __restrict__ out)
+{
+    const long s = h / H.n_rot;
+    const int r = (int)(h - s * H.n_rot);
+    sf_rotation(r, H.n_rot, out);
+    const double u = H.seeds[4 * s], v = H.seeds[4 * s + 1], d = H.seeds[4 * s + 2];
+    const double x = (u - H.cx) / H.fx, y = (v - H.cy) / H.fy;
+    const double nrm = sqrt(x * x + y * y + 1.0);
+    out[9] = d * x + H.offset * (x / nrm);
+    out[10] = d * y + H.offset * (y / nrm);
+    out[11] = d + H.offset * (1.0 / nrm);
+}
+
+__global__ __launch_bounds__(256) void rbs_find_subsample_kernel(const float* __restrict__ src, int src_cols, float* __restrict__ dst,
+                                                                 int rows, int cols, int f)
+{
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= rows * cols) return;
+    const int r = p / cols, c = p - r * cols;
+    dst[p] = src[(size_t)r * f * src_cols + (size_t)c * f];
+}
+
+// One block.  cells: [ceil(rows/s) * ceil(cols/s)] scratch of compacted pixel indices; info[0] := kept, info[1] := valid.
+__global__ __launch_bounds__(kSeedThreads) void rbs_find_seed_kernel(const float* __restrict__ frame, int rows, int cols, int stride,
+                                                                     double dmin, double dmax, int max_seeds, int* __restrict__ cells,
+                                                                     double* __restrict__ seeds, int* __restrict__ info)
+{
+    __shared__ int wave_sum[kSeedThreads / 64];
+    __shared__ int base;
+    const int gr = (rows + stride - 1) / stride, gc = (cols + stride - 1) / stride, ncell = gr * gc;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (threadIdx.x == 0) base = 0;
+    __syncthreads();
+    for (int c0 = 0; c0 < ncell; c0 += kSeedThreads) {
+        const int c = c0 + (int)threadIdx.x;
+        int px = -1;
+        if (c < ncell) {
+            const int i = c / gc, j = c - i * gc;
+            const int p = i * stride * cols + j * stride;
+            const double d = (double)frame[p];
+            if (d >= dmin && d <= dmax) px = p;   // (NaN and inf fail one of the two)
+        }
+        const unsigned long long m = __ballot(px >= 0);
+        const int before = __popcll(m & ((1ull << lane) - 1ull));
+        if (lane == 0) wave_sum[wv] = __popcll(m);
+        __syncthreads();
+        int off = base;
+        for (int w = 0; w < wv; ++w) off += wave_sum[w];
+        if (px >= 0) cells[off + before] = px;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            int tot = 0;
+            for (int w = 0; w < kSeedThreads / 64; ++w) tot += wave_sum[w];
+            base += tot;
+        }
+        __syncthreads();
+    }
+    const int n = base;
+    const int step = n > max_seeds ? (n + max_seeds - 1) / max_seeds : 1;
+    const int kept = (n + step - 1) / step;
+    for (int i = threadIdx.x; i < kept; i += kSeedThreads) {
+        const int p = cells[(size_t)i * step];
+        const int v = p / cols, u = p - v * cols;
+        seeds[4 * i] = (double)u;
+        seeds[4 * i + 1] = (double)v;
+        seeds[4 * i + 2] = (double)frame[p];
+        seeds[4 * i + 3] = (double)p;
+    }
+    if (threadIdx.x == 0) { info[0] = kept; info[1] = n; }
+}
+
+__global__ __launch_bounds__(256) void rbs_find_hyp_kernel(const HypParams H, long h0, int n, double* __restrict__ poses)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    double p[12];
+    hyp_pose(H, h0 + i, p);
+#pragma unroll
+    for (int k = 0; k < 12; ++k) poses[(size_t)i * 12 + k] = p[k];
+}
+
+// gather: poses of the listed hypotheses
+__global__ __launch_bounds__(256) void rbs_find_gather_kernel(const HypParams H, const long long* __restrict__ idx, int n,
+                                                              double* __restrict__ poses)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    double p[12];
+    hyp_pose(H, idx[i], p);
+#pragma unroll
+    for (int k = 0; k < 12; ++k) poses[(size_t)i * 12 + k] = p[k];
+}
+
+// a before b: larger score first, NaN last, then smaller index
+__device__ inline bool before(double sa, long long ia, double sb, long long ib)
+{
+    const bool na = sa != sa, nb = sb != sb;
+    if (na != nb) return nb;
+    if (!na && sa != sb) return sa > sb;
+    return ia < ib;
+}
+
+// Block b sorts items [b C, (b+1) C) of (score, idx) -- idx == nullptr: the item's own position -- and writes
+// its best k to out[b k ...].  Padding: (NaN, LLONG_MAX), which sorts after everything.
+__global__ __launch_bounds__(kTopThreads) void rbs_find_topk_kernel(const double* __restrict__ score, const long long* __restrict__ idx,
+                                                                    long n, int k, double* __restrict__ out_score,
+                                                                    long long* __restrict__ out_idx)
+{
+    __shared__ double ss[kTopC];
+    __shared__ long long si[kTopC];
+    const long b0 = (long)blockIdx.x * kTopC;
+    for (int i = threadIdx.x; i < kTopC; i += kTopThreads) {
+        const long g = b0 + i;
+        ss[i] = g < n ? score[g] : __builtin_nan("");
+        si[i] = g < n ? (idx ? idx[g] : (long long)g) : LLONG_MAX;
+    }
+    __syncthreads();
+    for (int size = 2; size <= kTopC; size <<= 1)
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int p = threadIdx.x; p < kTopC / 2; p += kTopThreads) {
+                const int i = 2 * stride * (p / stride) + (p % stride), j = i + stride;
+                const bool up = (i & size) == 0;
+                const bool sw = up ? before(ss[j], si[j], ss[i], si[i]) : before(ss[i], si[i], ss[j], si[j]);
+                if (sw) {
+                    const double t = ss[i]; ss[i] = ss[j]; ss[j] = t;
+                    const long long u = si[i]; si[i] = si[j]; si[j] = u;
+                }
+            }
+            __syncthreads();
+        }
+    for (int i = threadIdx.x; i < k; i += kTopThreads) {
+        out_score[(size_t)blockIdx.x * k + i] = ss[i];
+        out_idx[(size_t)blockIdx.x * k + i] = si[i];
+    }
+}
+
+// One wave.  Candidates [n] in order (poses [n][12]); kept: their positions, at most max_keep; out[0] := count.
+__global__ __launch_bounds__(64) void rbs_find_nms_kernel(const double* __restrict__ poses, const double* __restrict__ score, int n,
+                                                          double t2, double trace_min, int max_keep, int* __restrict__ kept,
+                                                          int* __restrict__ count)
+{
+    __shared__ int keep_pos[kMaxSurvivors];
+    const int lane = threadIdx.x;
+    int nk = 0;
+    for (int c = 0; c < n && nk < max_keep; ++c) {
+        if (score[c] != score[c]) break;   // (NaN sorts last: nothing after it is a candidate)
+        const double* P = poses + (size_t)c * 12;
+        bool near = false;
+        if (lane < nk) {
+            const double* Q = poses + (size_t)keep_pos[lane] * 12;
+            const double dx = P[9] - Q[9], dy = P[10] - Q[10], dz = P[11] - Q[11];
+            const double d2 = dx * dx + dy * dy + dz * dz;
+            double tr = P[0] * Q[0];
+            for (int e = 1; e < 9; ++e) tr = tr + P[e] * Q[e];
+            near = d2 <= t2 && tr >= trace_min;
+        }
+        const bool drop = __ballot(near) != 0ull;
+        if (!drop) {
+            if (lane == 0) keep_pos[nk] = c;
+            __syncthreads();
+            ++nk;
+        }
+    }
+    for (int i = lane; i < nk; i += 64) kept[i] = keep_pos[i];
+    if (lane == 0) *count = nk;
+}
+
+__device__ inline uint4 philox(unsigned long long seed, unsigned long long ctr_hi, unsigned long long ctr_lo)
+{
+    return rbt::philox(seed, ctr_hi, ctr_lo);
+}
+
+// rotation by the vector v (angle-axis via the unit quaternion, as dbot_ros_amd.pose.rotvec_to_matrix)
+__device__ inline void rotvec_matrix(const double* v, double* R)
+{
+    const double angle = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+    const double half = 0.5 * angle;
+    const double k = angle < 1e-9 ? 0.5 - angle * angle / 48.0 : sin(half) / angle;
+    const double w = cos(half), x = v[0] * k, y = v[1] * k, z = v[2] * k;
+    R[0] = 1.0 - 2.0 * (y * y + z * z); R[1] = 2.0 * (x * y - w * z);       R[2] = 2.0 * (x * z + w * y);
+    R[3] = 2.0 * (x * y + w * z);       R[4] = 1.0 - 2.0 * (x * x + z * z); R[5] = 2.0 * (y * z - w * x);
+    R[6] = 2.0 * (x * z - w * y);       R[7] = 2.0 * (y * z + w * x);       R[8] = 1.0 - 2.0 * (x * x + y * y);
+}
+
+// One thread per child of round r: [S][children][12].
+__global__ __launch_bounds__(256) void rbs_find_children_kernel(const double* __restrict__ surv, int S, int children, int round,
+                                                                unsigned long long seed, double st, double sa,
+                                                                double* __restrict__ out)
+{
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    if (g >= S * children) return;
+    const int k = g / children, j = g - k * children;
+    const double* P = surv + (size_t)k * 12;
+    double* o = out + (size_t)g * 12;
+    if (j == 0) {
+#pragma unroll
+        for (int e = 0; e < 12; ++e) o[e] = P[e];
+        return;
+    }
+    double nz[6];
+#pragma unroll
+    for (int pr = 0; pr < 3; ++pr) {
+        const uint4 r = philox(seed, ((unsigned long long)(unsigned)round << 32) | (unsigned)k, ((unsigned long long)(unsigned)j << 2) | pr);
+        const double u1 = 1.0 - rbt::u01(r.x, r.y), u2 = rbt::u01(r.z, r.w);
+        const double rad = sqrt(-2.0 * log(u1));
+        nz[2 * pr] = rad * cos(kTwoPi * u2);
+        nz[2 * pr + 1] = rad * sin(kTwoPi * u2);
+    }
+    const double v[3] = {sa * nz[0], sa * nz[1], sa * nz[2]};
+    double A[9];
+    rotvec_matrix(v, A);
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+            o[3 * r + c] = A[3 * r] * P[c] + A[3 * r + 1] * P[3 + c] + A[3 * r + 2] * P[6 + c];
+    o[9] = P[9] + st * nz[3];
+    o[10] = P[10] + st * nz[4];
+    o[11] = P[11] + st * nz[5];
+}
+
+// One thread per survivor: its best child (ties: lowest j; NaN never beats a number) becomes the survivor.
+__global__ __launch_bounds__(64) void rbs_find_select_kernel(const double* __restrict__ child, const double* __restrict__ child_score,
+                                                             int S, int children, double* __restrict__ surv, double* __restrict__ surv_score)
+{
+    const int k = blockIdx.x * 64 + threadIdx.x;
+    if (k >= S) return;
+    int best = 0;
+    double bs = child_score[(size_t)k * children];
+    for (int j = 1; j < children; ++j) {
+        const double s = child_score[(size_t)k * children + j];
+        if (s > bs || (bs != bs && s == s)) { bs = s; best = j; }
+    }
+    const double* P = child + ((size_t)k * children + best) * 12;
+#pragma unroll
+    for (int e = 0; e < 12; ++e) surv[(size_t)k * 12 + e] = P[e];
+    surv_score[k] = bs;
+}
+
+// survivors in the order of the final sort: poses and scores gathered by position
+__global__ __launch_bounds__(64) void rbs_find_order_kernel(const double* __restrict__ surv, const double* __restrict__ surv_score,
+                                                            const long long* __restrict__ order, int S, double* __restrict__ out_pose,
+                                                            double* __restrict__ out_score)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= S) return;
+    const long long k = order[i];
+#pragma unroll
+    for (int e = 0; e < 12; ++e) out_pose[(size_t)i * 12 + e] = surv[(size_t)k * 12 + e];
+    out_score[i] = surv_score[k];
+}
+
+// candidates -> survivors: the kept positions' poses, scores and hypothesis indices
+__global__ __launch_bounds__(64) void rbs_find_keep_kernel(const double* __restrict__ cand_pose, const double* __restrict__ cand_score,
+                                                           const long long* __restrict__ cand_idx, const int* __restrict__ kept,
+                                                           const int* __restrict__ count, double* __restrict__ surv,
+                                                           double* __restrict__ surv_coarse, long long* __restrict__ surv_idx)
+{
+    const int i = threadIdx.x;
+    if (i >= *count) return;
+    const int c = kept[i];
+#pragma unroll
+    for (int e = 0; e < 12; ++e) surv[(size_t)i * 12 + e] = cand_pose[(size_t)c * 12 + e];
+    surv_coarse[i] = cand_score[c];
+    surv_idx[i] = cand_idx[c];
+}
+
+}  // namespace rbf
+
+struct rbs_find {
+    rbs_handle* s = nullptr;          // the sensor (borrowed)
+    rbs_find_params p{};
+    rbs_handle* coarse = nullptr;     // scoring handles: coarse resolution (max_particles = batch) and the sensor's
+    rbs_handle* full = nullptr;       //   (max_particles = n_survivors * children); one occlusion slot each
+    int f = 1, crows = 0, ccols = 0;
+    double cK[9] = {};
+    double offset = 0.0;
+    double trace_min = 0.0;
+    hipStream_t st = nullptr;         // = coarse->stream: every kernel of a find
+    float* d_full = nullptr;          // [rows*cols] the frame
+    float* d_coarse = nullptr;        // [crows*ccols]
+    float* h_frame = nullptr;         // pinned staging of a host frame
+    int* d_cells = nullptr;           // seed-grid compaction
+    double* d_seeds = nullptr;        // [max_seeds][4]
+    int* d_info = nullptr;            // [2] kept, valid  (+ [2] suppression count)
+    int* h_info = nullptr;            // pinned
+    double* d_hyp = nullptr;          // [batch][12]
+    int* d_zero = nullptr;            // [max(batch, S*children)] parent indices: all 0
+    double* d_score = nullptr;        // [max_seeds * n_rotations] coarse scores
+    double* d_tk_s[2] = {};           // top-k ping-pong
+    long long* d_tk_i[2] = {};
+    size_t tk_cap = 0;
+    double* d_cand_pose = nullptr;    // [n_candidates][12]
+    double* d_cand_score = nullptr;
+    long long* d_cand_idx = nullptr;
+    int* d_kept = nullptr;
+    double* d_surv = nullptr;         // [S][12] current survivors
+    double* d_surv_score = nullptr;   // [S]
+    double* d_surv0 = nullptr;        // [S][12] after the suppression (coarse)
+    double* d_surv0_score = nullptr;
+    long long* d_surv0_idx = nullptr;
+    double* d_child = nullptr;        // [rounds][S*children][12]
+    double* d_child_score = nullptr;  // [rounds][S*children]
+    double* d_final = nullptr;        // [S][12]
+    double* d_final_score = nullptr;
+    long long* d_final_idx = nullptr;
+    hipEvent_t ev[5] = {};
+    // the last find
+    bool have = false;
+    int n_seeds = 0, n_valid = 0, n_cand = 0, n_surv = 0;
+    long n_hyp = 0;
+    float ms[5] = {};
+    std::string err;
+};
+
+namespace {
+
+int32_t ffail(rbs_find* f, int32_t code, const std::string& msg) { f->err = msg; return code; }
+
+#define RBF_HIP(f, call)                                                                                          \
+    do {                                                                                                          \
+        hipError_t e_ = (call);                                                                                   \
+        if (e_ != hipSuccess) {                                                                                   \
+            (void)hipGetLastError();                                                                              \
+            (f)->err = fmt("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__);            \
+            return e_ == hipErrorOutOfMemory ? RBS_ERR_OUT_OF_MEMORY : RBS_ERR_HIP;                               \
+        }                                                                                                         \
+    } while (0)
+#define RBF_RC(f, h, call)                                                                                        \
+    do {                                                                                                          \
+        const int32_t rc_ = (call);                                                                               \
+        if (rc_ != RBS_OK) { (f)->err = std::string("scoring handle: ") + (h)->err; return rc_; }                 \
+    } while (0)
+
+const char* find_check(const rbs_find_params* p)
+{
+    if (!(p->coarse_downsampling == 0 || p->coarse_downsampling == 1 || p->coarse_downsampling == 2 || p->coarse_downsampling == 4))
+        return "find: coarse_downsampling must be 0, 1, 2 or 4";
+    if (p->seed_stride < 1 || p->seed_stride > 4096) return "find: seed_stride outside 1..4096";
+    if (!(p->min_depth > 0.0) || !(p->max_depth >= p->min_depth) || !std::isfinite(p->max_depth)) return "find: need 0 < min_depth <= max_depth < inf";
+    if (!(p->depth_offset < 0.0 || (p->depth_offset >= 0.0 && std::isfinite(p->depth_offset)))) return "find: depth_offset must be finite (< 0: the default)";
+    if (p->max_seeds < 1 || p->max_seeds > (1 << 20)) return "find: max_seeds outside 1..2^20";
+    if (p->n_rotations < 1 || p->n_rotations > (1 << 20)) return "find: n_rotations outside 1..2^20";
+    if ((long long)p->max_seeds * p->n_rotations > (1LL << 31) - 1) return "find: max_seeds * n_rotations above 2^31 - 1";
+    if (p->n_candidates < 1 || p->n_candidates > rbf::kMaxCandidates) return "find: n_candidates outside 1..1024";
+    if (p->n_survivors < 1 || p->n_survivors > rbf::kMaxSurvivors || p->n_survivors > p->n_candidates)
+        return "find: n_survivors outside 1..min(64, n_candidates)";
+    if (!(p->nms_translation >= 0.0) || !std::isfinite(p->nms_translation) || !(p->nms_angle >= 0.0) || !std::isfinite(p->nms_angle))
+        return "find: nms_translation and nms_angle must be finite and >= 0";
+    if (p->rounds < 0 || p->rounds > 64) return "find: rounds outside 0..64";
+    if (p->children < 1 || p->children > 4096) return "find: children outside 1..4096";
+    if (!(p->sigma_translation >= 0.0) || !std::isfinite(p->sigma_translation) || !(p->sigma_angle >= 0.0) || !std::isfinite(p->sigma_angle))
+        return "find: sigma_translation and sigma_angle must be finite and >= 0";
+    if (!(p->decay > 0.0) || !(p->decay <= 1.0)) return "find: decay outside (0, 1]";
+    if (p->batch < 1 || p->batch > (1 << 20)) return "find: batch outside 1..2^20";
+    if (p->min_score != p->min_score) return "find: min_score is NaN";
+    return nullptr;
+}
+
+// a scoring handle: the sensor's configuration at (rows, cols, K), one occlusion slot, whole planes
+int32_t make_scorer(rbs_find* f, int rows, int cols, const double* K, int max_particles, rbs_handle** out)
+{
+    rbs_config c = f->s->cfg;
+    c.rows = rows;
+    c.cols = cols;
+    for (int i = 0; i < 9; ++i) c.K[i] = K[i];
+    c.max_particles = max_particles;
+    c.n_devices = 0;
+    c.device_ids = nullptr;
+    c.state_slab_px = RBS_SLAB_WHOLE_PLANES;
+    rbs_handle* h = new (std::nothrow) rbs_handle;
+    if (!h) return ffail(f, RBS_ERR_OUT_OF_MEMORY, "find_create: out of host memory");
+    h->occ_slots = 1;
+    int32_t rc;
+    try {
+        rc = create_impl(&c, h);
+    } catch (const std::exception& e) {
+        h->err = e.what();
+        rc = RBS_ERR_OUT_OF_MEMORY;
+    }
+    if (rc != RBS_OK) {
+        f->err = "find_create: scoring handle: " + h->err;
+        release(h);
+        return rc;
+    }
+    h->smalln_target = 1;   // one tile split whatever the call's size (that of calls of >= 2 x CUs poses)
+    *out = h;
+    return RBS_OK;
+}
+
+int32_t launch_topk(rbs_find* f, const double* score, const long long* idx, long n, int k, const double** out_s,
+                    const long long** out_i)
+{
+    int buf = 0;
+    while (true) {
+        const long blocks = (n + rbf::kTopC - 1) / rbf::kTopC;
+        hipLaunchKernelGGL(rbf::rbs_find_topk_kernel, dim3((unsigned)blocks), dim3(rbf::kTopThreads), 0, f->st, score, idx, n, k,
+                           f->d_tk_s[buf], f->d_tk_i[buf]);
+        RBF_HIP(f, hipGetLastError());
+        score = f->d_tk_s[buf];
+        idx = f->d_tk_i[buf];
+        buf ^= 1;
+        n = blocks * k;
+        if (blocks == 1) break;
+    }
+    *out_s = score;
+    *out_i = idx;
+    return RBS_OK;
+}
+
+rbf::HypParams hyp_params(const rbs_find* f)
+{
+    rbf::HypParams H;
+    H.seeds = f->d_seeds;
+    H.n_rot = f->p.n_rotations;
+    H.fx = f->cK[0]; H.fy = f->cK[4]; H.cx = f->cK[2]; H.cy = f->cK[5];
+    H.offset = f->offset;
+    return H;
+}
+
+}  // namespace
+
+extern "C" {
+
+void rbs_find_default_params(rbs_find_params* p)
+{
+    if (!p) return;
+    p->coarse_downsampling = 0;
+    p->seed_stride = 4;
+    p->min_depth = 0.2;
+    p->max_depth = 3.0;
+    p->depth_offset = -1.0;
+    p->max_seeds = 1024;
+    p->n_rotations = 1024;
+    p->n_candidates = 512;
+    p->nms_translation = 0.02;
+    p->nms_angle = 30.0 * M_PI / 180.0;
+    p->n_survivors = 32;
+    p->rounds = 8;
+    p->children = 64;
+    p->sigma_translation = 0.01;
+    p->sigma_angle = 10.0 * M_PI / 180.0;
+    p->decay = 0.6;
+    p->batch = 65536;
+    p->seed = 0;
+    p->min_score = -INFINITY;
+}
+
+const char* rbs_find_last_error(const rbs_find* f) { return f ? f->err.c_str() : "null finder"; }
+
+void rbs_find_destroy(rbs_find* f)
+{
+    if (!f) return;
+    if (f->coarse) (void)hipSetDevice(f->coarse->device);
+    if (f->st) (void)hipStreamSynchronize(f->st);
+    for (void* q : {(void*)f->d_full, (void*)f->d_coarse, (void*)f->d_cells, (void*)f->d_seeds, (void*)f->d_info, (void*)f->d_hyp,
+                    (void*)f->d_zero, (void*)f->d_score, (void*)f->d_tk_s[0], (void*)f->d_tk_s[1], (void*)f->d_tk_i[0],
+                    (void*)f->d_tk_i[1], (void*)f->d_cand_pose, (void*)f->d_cand_score, (void*)f->d_cand_idx, (void*)f->d_kept,
+                    (void*)f->d_surv, (void*)f->d_surv_score, (void*)f->d_surv0, (void*)f->d_surv0_score, (void*)f->d_surv0_idx,
+                    (void*)f->d_child, (void*)f->d_child_score, (void*)f->d_final, (void*)f->d_final_score, (void*)f->d_final_idx})
+        if (q) (void)hipFree(q);
+    if (f->h_frame) (void)hipHostFree(f->h_frame);
+    if (f->h_info) (void)hipHostFree(f->h_info);
+    for (hipEvent_t& e : f->ev)
+        if (e) (void)hipEventDestroy(e);
+    if (f->coarse) release(f->coarse);
+    if (f->full) release(f->full);
+    delete f;
+}
+
+int32_t rbs_find_create(rbs_handle* sensor, const rbs_find_params* p, rbs_find** out)
+{
+    if (out) *out = nullptr;
+    const char* bad = !p ? "find_create: params is NULL" : !out ? "find_create: out is NULL" : find_check(p);
+    if (!bad && !sensor) bad = "find_create: sensor is NULL";
+    if (bad) {
+        if (sensor) sensor->err = bad; else g_create_error = bad;
+        return RBS_ERR_INVALID_ARGUMENT;
+    }
+    if (!sensor->shards.empty() || sensor->group || sensor->peer_world > 1)
+        return fail(sensor, RBS_ERR_UNSUPPORTED, "find_create: the finder runs on single-device handles only");
+    if (sensor->n_bodies != 1)
+        return fail(sensor, RBS_ERR_UNSUPPORTED, "find_create: the finder searches for one object (n_objects = 1)");
+    rbs_find* f = new (std::nothrow) rbs_find;
+    if (!f) return fail(sensor, RBS_ERR_OUT_OF_MEMORY, "find_create: out of host memory");
+    f->s = sensor;
+    f->p = *p;
+    auto bail = [&](int32_t rc) { sensor->err = f->err; rbs_find_destroy(f); return rc; };
+    const int rows = sensor->rows, cols = sensor->cols;
+    f->f = p->coarse_downsampling;
+    if (f->f == 0) f->f = cols / 4 >= 160 ? 4 : cols / 2 >= 160 ? 2 : 1;
+    f->crows = rows / f->f;
+    f->ccols = cols / f->f;
+    if (f->crows < 1 || f->ccols < 1) { f->err = "find_create: the coarse frame would be empty"; return bail(RBS_ERR_INVALID_ARGUMENT); }
+    for (int i = 0; i < 9; ++i) f->cK[i] = sensor->cfg.K[i];
+    for (int i = 0; i < 6; ++i) f->cK[i] /= (double)f->f;
+    {   // depth offset: mean distance of the vertices from their mean
+        const std::vector<double>& V = sensor->cfg_vertices;
+        const size_t nv = V.size() / 3;
+        double c[3] = {0.0, 0.0, 0.0};
+        for (size_t i = 0; i < nv; ++i)
+            for (int k = 0; k < 3; ++k) c[k] += V[3 * i + k];
+        for (int k = 0; k < 3; ++k) c[k] /= (double)nv;
+        double m = 0.0;
+        for (size_t i = 0; i < nv; ++i) {
+            const double dx = V[3 * i] - c[0], dy = V[3 * i + 1] - c[1], dz = V[3 * i + 2] - c[2];
+            m += std::sqrt(dx * dx + dy * dy + dz * dz);
+        }
+        f->offset = p->depth_offset < 0.0 ? m / (double)nv : p->depth_offset;
+    }
+    f->trace_min = 1.0 + 2.0 * std::cos(p->nms_angle);
+    const int S = p->n_survivors, nch = S * p->children;
+    if (int32_t rc = make_scorer(f, f->crows, f->ccols, f->cK, p->batch, &f->coarse)) return bail(rc);
+    if (int32_t rc = make_scorer(f, rows, cols, sensor->cfg.K, nch, &f->full)) return bail(rc);
+    f->st = f->coarse->stream;
+    const long H = (long)p->max_seeds * p->n_rotations;
+    const int gr = (f->crows + p->seed_stride - 1) / p->seed_stride, gc = (f->ccols + p->seed_stride - 1) / p->seed_stride;
+    f->tk_cap = (size_t)((H + rbf::kTopC - 1) / rbf::kTopC) * p->n_candidates + rbf::kTopC;
+    const size_t R = (size_t)std::max(1, p->rounds);
+    if (hipSetDevice(sensor->device) != hipSuccess ||
+        hipMalloc(&f->d_full, sizeof(float) * (size_t)rows * cols) != hipSuccess ||
+        hipMalloc(&f->d_coarse, sizeof(float) * (size_t)f->crows * f->ccols) != hipSuccess ||
+        hipHostMalloc(&f->h_frame, sizeof(float) * (size_t)rows * cols, hipHostMallocDefault) != hipSuccess ||
+        hipMalloc(&f->d_cells, sizeof(int) * (size_t)gr * gc) != hipSuccess ||
+        hipMalloc(&f->d_seeds, sizeof(double) * 4 * (size_t)p->max_seeds) != hipSuccess ||
+        hipMalloc(&f->d_info, sizeof(int) * 4) != hipSuccess ||
+        hipHostMalloc(&f->h_info, sizeof(int) * 4, hipHostMallocDefault) != hipSuccess ||
+        hipMalloc(&f->d_hyp, sizeof(double) * 12 * (size_t)p->batch) != hipSuccess ||
+        hipMalloc(&f->d_zero, sizeof(int) * (size_t)std::max(p->batch, nch)) != hipSuccess ||
+        hipMemset(f->d_zero, 0, sizeof(int) * (size_t)std::max(p->batch, nch)) != hipSuccess ||
+        hipMalloc(&f->d_score, sizeof(double) * (size_t)H) != hipSuccess ||
+        hipMalloc(&f->d_tk_s[0], sizeof(double) * f->tk_cap) != hipSuccess ||
+        hipMalloc(&f->d_tk_s[1], sizeof(double) * f->tk_cap) != hipSuccess ||
+        hipMalloc(&f->d_tk_i[0], sizeof(long long) * f->tk_cap) != hipSuccess ||
+        hipMalloc(&f->d_tk_i[1], sizeof(long long) * f->tk_cap) != hipSuccess ||
+        hipMalloc(&f->d_cand_pose, sizeof(double) * 12 * (size_t)p->n_candidates) != hipSuccess ||
+        hipMalloc(&f->d_cand_score, sizeof(double) * (size_t)p->n_candidates) != hipSuccess ||
+        hipMalloc(&f->d_cand_idx, sizeof(long long) * (size_t)p->n_candidates) != hipSuccess ||
+        hipMalloc(&f->d_kept, sizeof(int) * rbf::kMaxSurvivors) != hipSuccess ||
+        hipMalloc(&f->d_surv, sizeof(double) * 12 * S) != hipSuccess ||
+        hipMalloc(&f->d_surv_score, sizeof(double) * S) != hipSuccess ||
+        hipMalloc(&f->d_surv0, sizeof(double) * 12 * S) != hipSuccess ||
+        hipMalloc(&f->d_surv0_score, sizeof(double) * S) != hipSuccess ||
+        hipMalloc(&f->d_surv0_idx, sizeof(long long) * S) != hipSuccess ||
+        hipMalloc(&f->d_child, sizeof(double) * 12 * (size_t)nch * R) != hipSuccess ||
+        hipMalloc(&f->d_child_score, sizeof(double) * (size_t)nch * R) != hipSuccess ||
+        hipMalloc(&f->d_final, sizeof(double) * 12 * S) != hipSuccess ||
+        hipMalloc(&f->d_final_score, sizeof(double) * S) != hipSuccess ||
+        hipMalloc(&f->d_final_idx, sizeof(long long) * S) != hipSuccess) {
+        (void)hipGetLastError();
+        f->err = "find_create: device or pinned memory";
+        return bail(RBS_ERR_OUT_OF_MEMORY);
+    }
+    for (hipEvent_t& e : f->ev)
+        if (hipEventCreate(&e) != hipSuccess) {
+            (void)hipGetLastError();
+            f->err = "find_create: events";
+            return bail(RBS_ERR_HIP);
+        }
+    *out = f;
+    return RBS_OK;
+}
+
+int32_t rbs_find_run(rbs_find* f, const float* frame, int32_t k, double* poses, double* scores, int32_t* n_out, int32_t* found)
+{
+    if (!f) return RBS_ERR_INVALID_ARGUMENT;
+    if (k < 0 || !n_out || !found) return ffail(f, RBS_ERR_INVALID_ARGUMENT, "find_run: k < 0 or a null n_out / found");
+    *n_out = 0;
+    *found = 0;
+    f->have = false;
+    rbs_handle* s = f->s;
+    const rbs_find_params& p = f->p;
+    const size_t npx = (size_t)s->npx;
+    RBF_HIP(f, hipSetDevice(s->device));
+    if (frame) {
+        std::memcpy(f->h_frame, frame, sizeof(float) * npx);
+    } else {   // the sensor's current observation, as rbs_get_observation reads it (waits for the sensor's queued work)
+        if (int32_t rc = rbs_get_observation(s, f->h_frame)) return ffail(f, rc, "find_run: sensor: " + s->err);
+    }
+    // fresh scoring state: the first frame after rbs_reset, every index 0
+    RBF_RC(f, f->coarse, rbs_reset(f->coarse));
+    RBF_RC(f, f->full, rbs_reset(f->full));
+    hipStream_t st = f->st;
+    RBF_HIP(f, hipEventRecord(f->ev[0], st));
+    RBF_HIP(f, hipMemcpyAsync(f->d_full, f->h_frame, sizeof(float) * npx, hipMemcpyHostToDevice, st));
+    const int cpx = f->crows * f->ccols;
+    hipLaunchKernelGGL(rbf::rbs_find_subsample_kernel, dim3((unsigned)((cpx + 255) / 256)), dim3(256), 0, st, f->d_full, s->cols,
+                       f->d_coarse, f->crows, f->ccols, f->f);
+    hipLaunchKernelGGL(rbf::rbs_find_seed_kernel, dim3(1), dim3(rbf::kSeedThreads), 0, st, f->d_coarse, f->crows, f->ccols,
+                       p.seed_stride, p.min_depth, p.max_depth, p.max_seeds, f->d_cells, f->d_seeds, f->d_info);
+    RBF_HIP(f, hipGetLastError());
+    RBF_RC(f, f->coarse, rbs_set_observation_device(f->coarse, f->d_coarse, st));
+    RBF_RC(f, f->full, rbs_set_observation_device(f->full, f->d_full, st));
+    RBF_HIP(f, hipMemcpyAsync(f->h_info, f->d_info, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+    RBF_HIP(f, hipEventRecord(f->ev[1], st));
+    RBF_HIP(f, hipStreamSynchronize(st));
+    f->n_seeds = f->h_info[0];
+    f->n_valid = f->h_info[1];
+    f->n_hyp = (long)f->n_seeds * p.n_rotations;
+    f->n_cand = f->n_surv = 0;
+    for (float& m : f->ms) m = 0.f;
+    if (f->n_seeds == 0) {
+        (void)hipEventElapsedTime(&f->ms[0], f->ev[0], f->ev[1]);
+        f->ms[4] = f->ms[0];
+        f->have = true;
+        return RBS_OK;
+    }
+    // coarse scores, `batch` hypotheses per launch
+    const rbf::HypParams HP = hyp_params(f);
+    for (long h0 = 0; h0 < f->n_hyp; h0 += p.batch) {
+        const int nb = (int)std::min<long>(p.batch, f->n_hyp - h0);
+        hipLaunchKernelGGL(rbf::rbs_find_hyp_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, HP, h0, nb, f->d_hyp);
+        RBF_HIP(f, hipGetLastError());
+        RBF_RC(f, f->coarse, rbs_loglikes_device(f->coarse, f->d_hyp, f->d_zero, nb, 0, f->d_score + h0, st));
+    }
+    RBF_HIP(f, hipEventRecord(f->ev[2], st));
+    // selection: top n_candidates, then the suppression
+    const int nc = (int)std::min<long>(p.n_candidates, f->n_hyp);
+    const double* ts;
+    const long long* ti;
+    if (int32_t rc = launch_topk(f, f->d_score, nullptr, f->n_hyp, nc, &ts, &ti)) return rc;
+    RBF_HIP(f, hipMemcpyAsync(f->d_cand_score, ts, sizeof(double) * nc, hipMemcpyDeviceToDevice, st));
+    RBF_HIP(f, hipMemcpyAsync(f->d_cand_idx, ti, sizeof(long long) * nc, hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(rbf::rbs_find_gather_kernel, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, st, HP, f->d_cand_idx, nc,
+                       f->d_cand_pose);
+    hipLaunchKernelGGL(rbf::rbs_find_nms_kernel, dim3(1), dim3(64), 0, st, f->d_cand_pose, f->d_cand_score, nc,
+                       p.nms_translation * p.nms_translation, f->trace_min, p.n_survivors, f->d_kept, f->d_info + 2);
+    hipLaunchKernelGGL(rbf::rbs_find_keep_kernel, dim3(1), dim3(64), 0, st, f->d_cand_pose, f->d_cand_score, f->d_cand_idx, f->d_kept,
+                       f->d_info + 2, f->d_surv0, f->d_surv0_score, f->d_surv0_idx);
+    RBF_HIP(f, hipGetLastError());
+    RBF_HIP(f, hipMemcpyAsync(f->h_info + 2, f->d_info + 2, sizeof(int), hipMemcpyDeviceToHost, st));
+    RBF_HIP(f, hipEventRecord(f->ev[3], st));
+    RBF_HIP(f, hipStreamSynchronize(st));
+    // candidates: those of a number (NaN sorts last)
+    {
+        std::vector<double> cs(nc);
+        RBF_HIP(f, hipMemcpy(cs.data(), f->d_cand_score, sizeof(double) * nc, hipMemcpyDeviceToHost));
+        int m = 0;
+        while (m < nc && cs[m] == cs[m]) ++m;
+        f->n_cand = m;
+    }
+    const int S = f->h_info[2];
+    f->n_surv = S;
+    if (S > 0) {
+        RBF_HIP(f, hipMemcpyAsync(f->d_surv, f->d_surv0, sizeof(double) * 12 * S, hipMemcpyDeviceToDevice, st));
+        // refinement at the sensor's resolution
+        const int nch = S * p.children;
+        double st_r = p.sigma_translation, sa_r = p.sigma_angle;
+        for (int r = 0; r < p.rounds; ++r) {
+            double* cp = f->d_child + (size_t)r * 12 * S * p.children;
+            double* cs = f->d_child_score + (size_t)r * S * p.children;
+            hipLaunchKernelGGL(rbf::rbs_find_children_kernel, dim3((unsigned)((nch + 255) / 256)), dim3(256), 0, st, f->d_surv, S,
+                               p.children, r, (unsigned long long)p.seed, st_r, sa_r, cp);
+            RBF_HIP(f, hipGetLastError());
+            RBF_RC(f, f->full, rbs_loglikes_device(f->full, cp, f->d_zero, nch, 0, cs, st));
+            hipLaunchKernelGGL(rbf::rbs_find_select_kernel, dim3((unsigned)((S + 63) / 64)), dim3(64), 0, st, cp, cs, S, p.children,
+                               f->d_surv, f->d_surv_score);
+            RBF_HIP(f, hipGetLastError());
+            st_r *= p.decay;
+            sa_r *= p.decay;
+        }
+        if (p.rounds == 0) {   // no refinement: the survivors are scored once at the sensor's resolution
+            RBF_RC(f, f->full, rbs_loglikes_device(f->full, f->d_surv, f->d_zero, S, 0, f->d_surv_score, st));
+        }
+        const double* fs;
+        const long long* fi;
+        if (int32_t rc = launch_topk(f, f->d_surv_score, nullptr, S, S, &fs, &fi)) return rc;
+        RBF_HIP(f, hipMemcpyAsync(f->d_final_idx, fi, sizeof(long long) * S, hipMemcpyDeviceToDevice, st));
+        hipLaunchKernelGGL(rbf::rbs_find_order_kernel, dim3(1), dim3(64), 0, st, f->d_surv, f->d_surv_score, f->d_final_idx, S,
+                           f->d_final, f->d_final_score);
+        RBF_HIP(f, hipGetLastError());
+    }
+    RBF_HIP(f, hipEventRecord(f->ev[4], st));
+    RBF_HIP(f, hipStreamSynchronize(st));
+    (void)hipEventElapsedTime(&f->ms[0], f->ev[0], f->ev[1]);
+    (void)hipEventElapsedTime(&f->ms[1], f->ev[1], f->ev[2]);
+    (void)hipEventElapsedTime(&f->ms[2], f->ev[2], f->ev[3]);
+    (void)hipEventElapsedTime(&f->ms[3], f->ev[3], f->ev[4]);
+    (void)hipEventElapsedTime(&f->ms[4], f->ev[0], f->ev[4]);
+    f->have = true;
+    const int K = std::min(k, S);
+    if (S > 0) {
+        double best = 0.0;
+        RBF_HIP(f, hipMemcpy(&best, f->d_final_score, sizeof(double), hipMemcpyDeviceToHost));
+        *found = best >= p.min_score ? 1 : 0;
+    }
+    if (K > 0 && poses) RBF_HIP(f, hipMemcpy(poses, f->d_final, sizeof(double) * 12 * K, hipMemcpyDeviceToHost));
+    if (K > 0 && scores) RBF_HIP(f, hipMemcpy(scores, f->d_final_score, sizeof(double) * K, hipMemcpyDeviceToHost));
+    *n_out = K;
+    return RBS_OK;
+}
+
+int32_t rbs_find_get_stage(rbs_find* f, int32_t stage, int32_t round, double* poses, double* scores, int64_t* indices, int64_t* n,
+                           double* info)
+{
+    if (!f) return RBS_ERR_INVALID_ARGUMENT;
+    if (!n) return ffail(f, RBS_ERR_INVALID_ARGUMENT, "find_get_stage: n is NULL");
+    if (!f->have) return ffail(f, RBS_ERR_INVALID_ARGUMENT, "find_get_stage: no find yet");
+    RBF_HIP(f, hipSetDevice(f->s->device));
+    if (info) {
+        info[0] = f->crows; info[1] = f->ccols; info[2] = f->f; info[3] = (double)f->n_hyp; info[4] = f->n_valid; info[5] = f->offset;
+    }
+    const int S = f->n_surv, nch = S * f->p.children;
+    auto fetch = [&](const void* d, void* hst, size_t bytes) -> int32_t {
+        if (hst && bytes) RBF_HIP(f, hipMemcpy(hst, d, bytes, hipMemcpyDeviceToHost));
+        return RBS_OK;
+    };
+    auto iota = [&](long m) { if (indices) for (long i = 0; i < m; ++i) indices[i] = i; };
+    switch (stage) {
+        case RBS_FIND_SEEDS:
+            *n = f->n_seeds;
+            iota(f->n_seeds);
+            return fetch(f->d_seeds, poses, sizeof(double) * 4 * f->n_seeds);
+        case RBS_FIND_COARSE: {
+            *n = f->n_hyp;
+            iota(f->n_hyp);
+            if (int32_t rc = fetch(f->d_score, scores, sizeof(double) * f->n_hyp)) return rc;
+            if (poses) {
+                const rbf::HypParams HP = hyp_params(f);
+                for (long h0 = 0; h0 < f->n_hyp; h0 += f->p.batch) {
+                    const int nb = (int)std::min<long>(f->p.batch, f->n_hyp - h0);
+                    hipLaunchKernelGGL(rbf::rbs_find_hyp_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, f->st, HP, h0, nb, f->d_hyp);
+                    RBF_HIP(f, hipGetLastError());
+                    RBF_HIP(f, hipMemcpyAsync(poses + (size_t)h0 * 12, f->d_hyp, sizeof(double) * 12 * nb, hipMemcpyDeviceToHost, f->st));
+                }
+                RBF_HIP(f, hipStreamSynchronize(f->st));
+            }
+            return RBS_OK;
+        }
+        case RBS_FIND_CANDIDATES: {
+            *n = f->n_cand;
+            if (int32_t rc = fetch(f->d_cand_pose, poses, sizeof(double) * 12 * f->n_cand)) return rc;
+            if (int32_t rc = fetch(f->d_cand_score, scores, sizeof(double) * f->n_cand)) return rc;
+            return fetch(f->d_cand_idx, indices, sizeof(long long) * f->n_cand);
+        }
+        case RBS_FIND_SURVIVORS: {
+            *n = S;
+            if (int32_t rc = fetch(f->d_surv0, poses, sizeof(double) * 12 * S)) return rc;
+            if (int32_t rc = fetch(f->d_surv0_score, scores, sizeof(double) * S)) return rc;
+            return fetch(f->d_surv0_idx, indices, sizeof(long long) * S);
+        }
+        case RBS_FIND_CHILDREN: {
+            if (round < 0 || round >= f->p.rounds) return ffail(f, RBS_ERR_INVALID_ARGUMENT, "find_get_stage: round outside 0..rounds-1");
+            *n = nch;
+            iota(nch);
+            if (int32_t rc = fetch(f->d_child + (size_t)round * 12 * nch, poses, sizeof(double) * 12 * nch)) return rc;
+            return fetch(f->d_child_score + (size_t)round * nch, scores, sizeof(double) * nch);
+        }
+        case RBS_FIND_RESULT: {
+            *n = S;
+            if (int32_t rc = fetch(f->d_final, poses, sizeof(double) * 12 * S)) return rc;
+            if (int32_t rc = fetch(f->d_final_score, scores, sizeof(double) * S)) return rc;
+            return fetch(f->d_final_idx, indices, sizeof(long long) * S);
+        }
+        default:
+            return ffail(f, RBS_ERR_INVALID_ARGUMENT, "find_get_stage: bad stage");
+    }
+}
+
+int32_t rbs_find_stage_ms(rbs_find* f, float* out5)
+{
+    if (!f) return RBS_ERR_INVALID_ARGUMENT;
+    if (!out5 || !f->have) return ffail(f, RBS_ERR_INVALID_ARGUMENT, "find_stage_ms: no find yet, or a null pointer");
+    for (int i = 0; i < 5; ++i) out5[i] = f->ms[i];
+    return RBS_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,155 @@
+"""Object finder: the object's initial pose from one depth frame, searched on the sensor's device
+(rbs_find_* in librbsensor_mi355x.so; the search: include/rbsensor_mi355x.h and DESIGN.md Appendix F).
+
+The reference starts a tracker from the pose an external FindObject service returns when a request
+has auto_detect set (R:source/dbot_ros/tracker/object_tracker_controller_service_node.cpp:143-167);
+ObjectFinder.find is that search.  Poses cross the C-ABI in the sensor's (centred) mesh frame; this
+class undoes center_object_frame, so its states go straight into tracker.initialize([states[0]]).
+"""
+import ctypes as C
+import math
+from dataclasses import dataclass, fields
+
+import numpy as np
+
+from . import _capi
+from .pose import matrix_to_rotvec
+from .sensor import RbSensorError
+
+
+@dataclass
+class FindResult:
+    found: bool
+    states: np.ndarray    # [K, 12] tracker states (position, rotation vector, zero velocities), caller's mesh frame
+    poses: np.ndarray     # [K, 12] R row-major | t of the sensor's (centred) mesh frame
+    scores: np.ndarray    # [K] log-likelihoods at the sensor's resolution
+
+
+class ObjectFinder:
+    """ObjectFinder(sensor, object_model, params).find(frame=None) -> FindResult."""
+
+    @dataclass
+    class Parameters:
+        coarse_downsampling: int = 0          # 0: the largest of {1, 2, 4} leaving >= 160 columns
+        seed_stride: int = 4
+        min_depth: float = 0.2
+        max_depth: float = 3.0
+        depth_offset: float = -1.0            # < 0: mean vertex distance from the mesh's centre
+        max_seeds: int = 1024
+        n_rotations: int = 1024
+        n_candidates: int = 512
+        nms_translation: float = 0.02
+        nms_angle: float = math.radians(30.0)
+        n_survivors: int = 32
+        rounds: int = 8
+        children: int = 64
+        sigma_translation: float = 0.01
+        sigma_angle: float = math.radians(10.0)
+        decay: float = 0.6
+        batch: int = 65536
+        seed: int = 0
+        min_score: float = -math.inf
+
+        @classmethod
+        def from_rosparam(cls, tree):
+            """From the optional `object_finder:` mapping of the merged rosparam tree; every key is
+            optional (angles in degrees: nms_angle_deg, sigma_angle_deg)."""
+            m = dict((tree or {}).get("object_finder") or {})
+            p = cls()
+            for k in ("nms_angle", "sigma_angle"):
+                if k + "_deg" in m:
+                    m[k] = math.radians(float(m.pop(k + "_deg")))
+            names = {f.name: f.type for f in fields(cls)}
+            for k, v in m.items():
+                if k not in names:
+                    raise ValueError(f"object_finder/{k}: unknown key (one of {sorted(names)})")
+                setattr(p, k, int(v) if isinstance(getattr(p, k), int) else float(v))
+            return p
+
+        def c_params(self):
+            p = _capi.RbsFindParams()
+            for f in fields(self):
+                setattr(p, f.name, getattr(self, f.name))
+            return p
+
+    def __init__(self, sensor, object_model, params=None):
+        self._lib = _capi.load()
+        self.sensor = sensor
+        self.params = params or ObjectFinder.Parameters()
+        self.centers = np.array(object_model.centers)
+        self._f = C.c_void_p()
+        cp = self.params.c_params()
+        rc = self._lib.rbs_find_create(sensor._h, C.byref(cp), C.byref(self._f))
+        if rc != 0:
+            self._f = C.c_void_p()
+            sensor._check(rc)
+        sensor._register_dependent(self)   # the finder borrows the sensor handle
+
+    def close(self):
+        if getattr(self, "_f", None) is not None and self._f.value:
+            self._lib.rbs_find_destroy(self._f)
+            self._f = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def _check(self, rc):
+        if rc != 0:
+            raise RbSensorError(rc, self._lib.rbs_find_last_error(self._f).decode())
+
+    def find(self, frame=None, k=None):
+        """frame: rows*cols depth (metres, NaN = no reading) at the sensor's resolution, or None for
+        the sensor's current observation.  Returns up to k (default n_survivors) poses, best first."""
+        k = int(self.params.n_survivors if k is None else k)
+        poses = np.zeros((max(k, 1), 12))
+        scores = np.zeros(max(k, 1))
+        n, found = C.c_int32(), C.c_int32()
+        dp = C.POINTER(C.c_double)
+        img = None
+        if frame is not None:
+            img = np.ascontiguousarray(frame, dtype=np.float32).ravel()
+            if img.size != self.sensor.rows * self.sensor.cols:
+                raise ValueError(f"frame has {img.size} pixels, the sensor {self.sensor.rows * self.sensor.cols}")
+        self._check(self._lib.rbs_find_run(self._f, img.ctypes.data_as(C.POINTER(C.c_float)) if img is not None else None, k,
+                                           poses.ctypes.data_as(dp), scores.ctypes.data_as(dp), C.byref(n), C.byref(found)))
+        K = int(n.value)
+        poses, scores = poses[:K].copy(), scores[:K].copy()
+        states = np.zeros((K, 12))
+        c = self.centers[0]
+        for i in range(K):
+            R = poses[i, :9].reshape(3, 3)
+            states[i, 0:3] = poses[i, 9:12] - R @ c
+            states[i, 3:6] = matrix_to_rotvec(R)
+        return FindResult(bool(found.value), states, poses, scores)
+
+    def stage(self, stage, round=0):
+        """One stage's exact outputs of the last find: (poses, scores, indices, info); see rbs_find_get_stage."""
+        if isinstance(stage, str):
+            stage = {"seeds": 0, "coarse": 1, "candidates": 2, "survivors": 3, "children": 4, "result": 5}[stage]
+        n = C.c_int64()
+        info = np.zeros(6)
+        dp, lp = C.POINTER(C.c_double), C.POINTER(C.c_int64)
+        self._check(self._lib.rbs_find_get_stage(self._f, stage, round, None, None, None, C.byref(n), info.ctypes.data_as(dp)))
+        m = int(n.value)
+        width = 4 if stage == _capi.RBS_FIND_SEEDS else 12
+        poses = np.zeros((m, width))
+        scores = np.zeros(m)
+        idx = np.zeros(m, dtype=np.int64)
+        self._check(self._lib.rbs_find_get_stage(self._f, stage, round, poses.ctypes.data_as(dp), scores.ctypes.data_as(dp),
+                                                 idx.ctypes.data_as(lp), C.byref(n), None))
+        return poses, scores, idx, info
+
+    def stage_ms(self):
+        """Device ms of the last find: frame + seeds, coarse scoring, selection, refinement, whole find."""
+        out = (C.c_float * 5)()
+        self._check(self._lib.rbs_find_stage_ms(self._f, out))
+        return list(out)

@@ -81,6 +81,27 @@ def build_gaussian_tracker(params, native_camera_matrix, mesh_package_path, devi
     return tracker, object_model, camera_data, ori
 
 
+def build_object_finder(params, native_camera_matrix, mesh_package_path, device_id=0, sensor=None):
+    """The object finder that stands in for the controller's FindObject service
+    (R:source/dbot_ros/tracker/object_tracker_controller_service_node.cpp:143-167): the object model and camera data
+    assembled as build_particle_tracker does, its parameters from the optional `object_finder:` mapping.  sensor: a
+    sensor to search with (a tracker's own); None builds one from the tree.  Returns (finder, object_model,
+    camera_data); close the finder, then a sensor built here (finder.sensor)."""
+    from .finder import ObjectFinder
+    pre = params["particle_filter"]
+    obj = params["object"]
+    ori = ObjectResourceIdentifier(mesh_package_path, obj["directory"], obj["meshes"])
+    vs, ts = SimpleWavefrontObjectModelLoader(ori).load()
+    object_model = ObjectModel(vs, ts, center=bool(pre["center_object_frame"]))
+    camera_data = CameraData.from_native(native_camera_matrix, int(params["resolution"]["width"]),
+                                         int(params["resolution"]["height"]), int(params["downsampling_factor"]))
+    if sensor is None:
+        params_obsrv = RbSensorBuilder.Parameters.from_rosparam(params)
+        params_obsrv.sample_count = 1
+        sensor = RbSensorBuilder(object_model, camera_data, params_obsrv, device_id=device_id).build()
+    return ObjectFinder(sensor, object_model, ObjectFinder.Parameters.from_rosparam(params)), object_model, camera_data
+
+
 def to_eigen_vector(native_image, downsampling_factor):
     """ri::to_eigen_vector (R:source/dbot_ros/util/ros_interface.h:152-168) on the host."""
     img = np.asarray(native_image)
@@ -89,7 +110,7 @@ def to_eigen_vector(native_image, downsampling_factor):
     return np.ascontiguousarray(img[: rows * f: f, : cols * f: f]).ravel()
 
 
-def replay_dataset(params, dataset, mesh_package_path, initial_states, device_id=0, seed=0, max_frames=None,
+def replay_dataset(params, dataset, mesh_package_path, initial_states=None, device_id=0, seed=0, max_frames=None,
                    look_ahead=False):
     """Run the tracker over a recorded TrackingDataset (dbot_ros_amd.dataset) the way
     the node runs over live topics: K from the bag's camera_info (frame 0, as GetCameraMatrix does,
@@ -99,15 +120,28 @@ def replay_dataset(params, dataset, mesh_package_path, initial_states, device_id
     look_ahead: a recorded sequence has the next frame at hand, so frame k+1 is submitted before
     frame k's estimate is collected (tracker.submit / tracker.result: two frames in flight, the
     same numbers); False drives tracker.track frame by frame as a live camera would.
+    initial_states=None: the controller's auto_detect + auto_confirm path
+    (R:source/dbot_ros/tracker/object_tracker_controller_service_node.cpp:143-167) -- the object is found on frame 0
+    by an object finder over the tracker's own sensor, and the tracker starts from its best state.
     Returns (estimates [frames, parts*12], wall seconds of the tracking loop)."""
     import time
     tracker, object_model, camera_data, _ = build_particle_tracker(params, dataset.get_camera_matrix(0),
                                                                    mesh_package_path, device_id=device_id, seed=seed)
     f = int(params["downsampling_factor"])
     try:
-        tracker.initialize(initial_states)
         n = dataset.size() if max_frames is None else min(max_frames, dataset.size())
         frames = [dataset.frame_vector(i, f) for i in range(n)]      # host decode outside the timed loop
+        if initial_states is None:
+            finder, _, _ = build_object_finder(params, dataset.get_camera_matrix(0), mesh_package_path, device_id=device_id,
+                                               sensor=tracker.sensor)
+            try:
+                found = finder.find(frames[0])
+            finally:
+                finder.close()
+            if not found.found:
+                raise RuntimeError("replay_dataset: the object finder found no object on frame 0")
+            initial_states = [found.states[0]]
+        tracker.initialize(initial_states)
         ests = []
         t0 = time.perf_counter()
         if look_ahead and hasattr(tracker, "submit") and frames:

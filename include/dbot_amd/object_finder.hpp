@@ -1,0 +1,108 @@
+// object_finder.hpp -- C++ host-side mirror of the object finder (rbs_find_*, include/rbsensor_mi355x.h), in the style
+// of rb_sensor_builder.hpp.
+//
+// It stands in for the FindObject service the reference's controller calls when a request has auto_detect set, and
+// whose pose starts the tracker (R:source/dbot_ros/tracker/object_tracker_controller_service_node.cpp:143-167):
+//     ObjectFinder finder(sensor, object_model, params);
+//     ObjectFinder::Result r = finder.find(image);        // r.states[0] -> tracker->initialize({r.states[0]})
+// States are in the caller's mesh frame (center_object_frame undone) with zero velocities; poses are R|t of the
+// sensor's (centred) mesh frame, as the C-ABI returns them.
+//
+// Header-only; link with -lrbsensor_mi355x.  No CPU fallback: without a device the sensor cannot be built.
+#pragma once
+
+#include <cmath>
+#include <memory>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "rb_sensor_builder.hpp"
+
+namespace dbot_amd
+{
+class ObjectFinder
+{
+public:
+    typedef FreeFloatingRigidBodiesState State;
+    typedef std::vector<float> Obsrv;  // rows*cols depth image, metres, NaN = no reading
+
+    /// rbs_find_params with the library's defaults (the optional object_finder: rosparam mapping overrides fields).
+    struct Parameters : rbs_find_params {
+        Parameters() { rbs_find_default_params(this); }
+    };
+
+    struct Result {
+        bool found = false;
+        std::vector<State> states;       // best first
+        std::vector<Real> poses;         // [K][12]
+        std::vector<Real> scores;        // [K]
+    };
+
+    ObjectFinder(const std::shared_ptr<RbSensor<State>>& sensor, const std::shared_ptr<ObjectModel>& om, const Parameters& p = Parameters())
+        : sensor_(sensor), om_(om), k_(p.n_survivors)
+    {
+        if (rbs_find_create(sensor_->handle(), &p, &f_) != RBS_OK)
+            throw std::runtime_error(std::string("ObjectFinder: ") + rbs_last_error(sensor_->handle()));
+    }
+    ~ObjectFinder() { rbs_find_destroy(f_); }
+    ObjectFinder(const ObjectFinder&) = delete;
+    ObjectFinder& operator=(const ObjectFinder&) = delete;
+
+    /// One find on `image` (the sensor's resolution); an empty image: the sensor's current observation.
+    Result find(const Obsrv& image = Obsrv())
+    {
+        Result r;
+        r.poses.assign(12 * static_cast<size_t>(k_), 0.0);
+        r.scores.assign(static_cast<size_t>(k_), 0.0);
+        int32_t n = 0, found = 0;
+        if (rbs_find_run(f_, image.empty() ? nullptr : image.data(), k_, r.poses.data(), r.scores.data(), &n, &found) != RBS_OK)
+            throw std::runtime_error(std::string("ObjectFinder::find: ") + rbs_find_last_error(f_));
+        r.found = found != 0;
+        r.poses.resize(12 * static_cast<size_t>(n));
+        r.scores.resize(static_cast<size_t>(n));
+        const Real* c = om_->centers().data();
+        for (int i = 0; i < n; ++i) {
+            const Real* P = r.poses.data() + 12 * static_cast<size_t>(i);
+            State s(1);
+            for (int k = 0; k < 3; ++k) s.position(0)[k] = P[9 + k] - (P[3 * k] * c[0] + P[3 * k + 1] * c[1] + P[3 * k + 2] * c[2]);
+            rotation_vector(P, s.euler_vector(0));
+            r.states.push_back(s);
+        }
+        return r;
+    }
+
+    rbs_find* handle() { return f_; }
+
+private:
+    /// row-major rotation matrix -> rotation vector (atan2 form, as dbot_ros_amd.pose.matrix_to_rotvec)
+    static void rotation_vector(const Real* R, Real* rv)
+    {
+        const Real s[3] = {0.5 * (R[7] - R[5]), 0.5 * (R[2] - R[6]), 0.5 * (R[3] - R[1])};
+        const Real sn = std::sqrt(s[0] * s[0] + s[1] * s[1] + s[2] * s[2]);
+        const Real cs = 0.5 * (R[0] + R[4] + R[8] - 1.0);
+        const Real angle = std::atan2(sn, cs);
+        if (sn > 1e-8) {
+            for (int k = 0; k < 3; ++k) rv[k] = s[k] * (angle / sn);
+            return;
+        }
+        if (cs > 0.0) {
+            for (int k = 0; k < 3; ++k) rv[k] = s[k];
+            return;
+        }
+        Real d[3];
+        for (int k = 0; k < 3; ++k) d[k] = std::sqrt(std::fmax((R[4 * k] + 1.0) * 0.5, 0.0));
+        const int i = d[0] >= d[1] ? (d[0] >= d[2] ? 0 : 2) : (d[1] >= d[2] ? 1 : 2);
+        Real a[3];
+        for (int k = 0; k < 3; ++k) a[k] = (R[3 * k + i] + (k == i ? 1.0 : 0.0)) / (2.0 * d[i]);
+        const Real an = std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
+        for (int k = 0; k < 3; ++k) rv[k] = a[k] / an * angle;
+    }
+
+    std::shared_ptr<RbSensor<State>> sensor_;
+    std::shared_ptr<ObjectModel> om_;
+    int k_;
+    rbs_find* f_ = nullptr;
+};
+
+}  // namespace dbot_amd

@@ -632,6 +632,113 @@ int32_t rbs_gauss_submit(rbs_gauss* g, const float* frame);   /* NULL: a frame s
 int32_t rbs_gauss_submit_f64(rbs_gauss* g, const double* frame);
 int32_t rbs_gauss_result(rbs_gauss* g, double* out_state, double* out_cov);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Object finder: the object's initial pose from one depth frame, without a prior.  The reference answers a
+ * request with auto_detect set by calling an external FindObject service and starting the tracker at the pose
+ * it returns (R:source/dbot_ros/tracker/object_tracker_controller_service_node.cpp:143-167, "controller" below);
+ * rbs_find_run is that service's search, on the device.
+ *
+ * The score of a pose is the log-likelihood rbs_loglikes(update = 0) gives it on a freshly reset handle of the
+ * sensor's configuration: the first frame after rbs_reset, every index 0 -- what a tracker started at that pose
+ * sees on its first frame -- in a call of at least 2 x (compute units) poses (512 on an MI355X): the finder scores
+ * through the sensor's own raster kernels (same precision, occlusion mode, layout) on handles of its own, whose tile
+ * split is fixed to that of such calls.  A smaller rbs_loglikes call splits a rectangle into more pieces and sums in
+ * another order, so re-scoring one returned pose in a call of one pose agrees to rounding, not bit for bit; pad such
+ * a call (repeat the pose) for the same bits.  Every stage is deterministic and none depends on `batch`.
+ *
+ *   1 coarse frame  the frame sub-sampled by f = coarse_downsampling (every f-th pixel of every f-th row, as
+ *                   ri::to_eigen_vector; K's top two rows divided by f); 0: the largest of {1, 2, 4} that leaves
+ *                   >= 160 columns.
+ *   2 seeds         coarse pixels (u, v) = (j s, i s), s = seed_stride, whose depth d is finite and inside
+ *                   [min_depth, max_depth], in row-major order; n of them are thinned to every step-th,
+ *                   step = ceil(n / max_seeds).  Seed -> t = d K^-1 (u, v, 1) + depth_offset r, r the unit
+ *                   vector along K^-1 (u, v, 1) (coarse K); depth_offset < 0: the mean distance of the mesh's
+ *                   vertices from their mean.
+ *   3 rotations     a Super-Fibonacci spiral of n_rotations unit quaternions (Alexa, CVPR 2022): for
+ *                   i < N, s = i + 1/2, r = sqrt(s / N), R = sqrt(1 - s / N), a = 2 pi s / sqrt(2),
+ *                   b = 2 pi s / 1.533751168755204288118041, q = (x, y, z, w) = (r sin a, r cos a, R sin b,
+ *                   R cos b).  Hypothesis h = seed * n_rotations + rotation, generated on the device in binary64.
+ *   4 coarse scores every hypothesis at the coarse resolution, `batch` at a time.
+ *   5 selection     the n_candidates best in the order (score descending, hypothesis ascending), NaN never;
+ *                   then a greedy non-maximum suppression in that order: a candidate is dropped when a kept one
+ *                   has |t - t'|^2 <= nms_translation^2 AND trace(R^T R') >= 1 + 2 cos(nms_angle); at most
+ *                   n_survivors are kept.
+ *   6 refinement    `rounds` rounds at the sensor's resolution; survivor k has `children` children per round r:
+ *                   child 0 is the survivor, child j > 0 is R = R(sa_r n) R_k, t = t_k + st_r n' with
+ *                   st_r = sigma_translation decay^r, sa_r = sigma_angle decay^r, R(v) the rotation by the
+ *                   vector v, and (n, n') six standard normals: Box-Muller pairs p = 0, 1, 2 of Philox4x32-10
+ *                   (key = seed, counter = (j << 2 | p, round << 32 | k)), u1 = 1 - u01(x, y), u2 = u01(z, w),
+ *                   n_2p = sqrt(-2 log u1) cos(2 pi u2), n_2p+1 = ... sin(...).  A survivor keeps its best child,
+ *                   ties to the lowest j, NaN never beats a number, so its score never goes down.  The survivors
+ *                   are then sorted as in step 5 (by survivor index on ties).
+ *   7 output        the k <= n_survivors best poses [k][12] (R row-major | t, the sensor's mesh frame) and their
+ *                   scores; found = (best score >= min_score).  A frame without a valid seed: RBS_OK, found = 0,
+ *                   *n_out = 0.
+ *
+ * Memory: per finder about the frame at two resolutions with their per-pixel terms, the mesh, and `batch` poses
+ * and scores (two scoring handles whose occlusion state is ONE plane each); the sensor's max_particles does not
+ * limit it.  Limits: one object and a single-device handle (RBS_ERR_UNSUPPORTED otherwise); bad parameters:
+ * RBS_ERR_INVALID_ARGUMENT.
+ *
+ * A find does not touch the sensor's state: observation, clock, occlusion planes, windows and any tracker over it
+ * are left as they were, so a tracker can re-detect mid-sequence.  With frame == NULL the find reads the sensor's
+ * current observation as rbs_get_observation does: it WAITS for the work queued on the sensor, a frame a tracker
+ * has in flight (rbs_tracker_submit / rbs_gauss_submit) included, and leaves that frame's result unchanged.  With
+ * a frame given it reads nothing of the sensor.  A finder is driven by one thread at a time and must be destroyed
+ * before its sensor. */
+typedef struct rbs_find rbs_find;
+
+typedef struct rbs_find_params {
+    int32_t coarse_downsampling;   /* f: 0 = the library's choice (above); else 1, 2 or 4                          */
+    int32_t seed_stride;           /* 4                                                                             */
+    double min_depth, max_depth;   /* 0.2, 3.0 (metres)                                                             */
+    double depth_offset;           /* -1: mean vertex distance from the mesh's centre                               */
+    int32_t max_seeds;             /* 1 024                                                                         */
+    int32_t n_rotations;           /* 1 024                                                                         */
+    int32_t n_candidates;          /* 512 (<= 1 024)                                                                */
+    double nms_translation;        /* 0.02 (metres)                                                                 */
+    double nms_angle;              /* 30 degrees, in radians                                                        */
+    int32_t n_survivors;           /* 32 (<= 64, <= n_candidates)                                                   */
+    int32_t rounds;                /* 8 (0 .. 64)                                                                   */
+    int32_t children;              /* 64 (>= 1)                                                                     */
+    double sigma_translation;      /* 0.01 (metres)                                                                 */
+    double sigma_angle;            /* 10 degrees, in radians                                                        */
+    double decay;                  /* 0.6, in (0, 1]                                                                */
+    int32_t batch;                 /* 65 536 hypotheses scored per launch                                           */
+    uint64_t seed;                 /* Philox key of the refinement                                                  */
+    double min_score;              /* -inf: a find reports the best pose whatever its score                         */
+} rbs_find_params;
+
+/* The defaults above, stated once. */
+void rbs_find_default_params(rbs_find_params* p);
+/* controller:143-167 -- the finder over the sensor's mesh, camera, parameters and device. */
+int32_t rbs_find_create(rbs_handle* sensor, const rbs_find_params* p, rbs_find** out);
+void rbs_find_destroy(rbs_find* f);
+/* controller:143-167 -- one find.  frame: rows*cols floats at the sensor's resolution (NULL: the sensor's current
+ * observation); k: room for k poses; poses [k][12] and scores [k] (either may be NULL); *n_out := min(k, survivors);
+ * *found := best score >= min_score (0 when there is no pose). */
+int32_t rbs_find_run(rbs_find* f, const float* frame, int32_t k, double* poses, double* scores, int32_t* n_out,
+                     int32_t* found);
+/* controller:143-167 -- inspection of the last find, for the tests: one stage's exact outputs.  Stage
+ *   RBS_FIND_SEEDS       poses [n][4] = (u, v, depth, coarse pixel index); scores unused; indices = seed number
+ *   RBS_FIND_COARSE      every hypothesis: poses [n][12], coarse scores, indices = h
+ *   RBS_FIND_CANDIDATES  the selection's order: poses, coarse scores, hypothesis indices
+ *   RBS_FIND_SURVIVORS   after the suppression, in that order: poses, coarse scores, hypothesis indices
+ *   RBS_FIND_CHILDREN    round `round`: poses [n_survivors][children][12], full-resolution scores, k * children + j
+ *   RBS_FIND_RESULT      the sorted survivors: poses, full-resolution scores, survivor index k
+ * Any pointer may be NULL; *n := the stage's count (call with NULL buffers to size them).  Before the first find
+ * or for a bad stage / round: RBS_ERR_INVALID_ARGUMENT.  Also *info (may be NULL) [6] := coarse rows, cols,
+ * f, hypotheses, valid seed pixels before thinning, depth_offset. */
+enum { RBS_FIND_SEEDS = 0, RBS_FIND_COARSE = 1, RBS_FIND_CANDIDATES = 2, RBS_FIND_SURVIVORS = 3, RBS_FIND_CHILDREN = 4,
+       RBS_FIND_RESULT = 5 };
+int32_t rbs_find_get_stage(rbs_find* f, int32_t stage, int32_t round, double* poses, double* scores, int64_t* indices,
+                           int64_t* n, double* info);
+/* Device time of the last find's stages in ms (HIP events): [0] frame + seeds, [1] coarse scoring, [2] selection
+ * (top-k + suppression), [3] refinement, [4] the whole find. */
+int32_t rbs_find_stage_ms(rbs_find* f, float* out5);
+/* Message of the last error on this finder. Never NULL. */
+const char* rbs_find_last_error(const rbs_find* f);
+
 #ifdef __cplusplus
 }
 #endif

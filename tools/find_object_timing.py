@@ -1,0 +1,131 @@
+"""Time per find of the object finder (rbs_find_*) on one device, per stage, beside the CPU oracle's cost of the same
+scoring.  Prints ONE JSON line:
+
+    {"tool": "find_object_timing", "cases": [{"case", "size", "coarse", "hypotheses", "children", "ms_per_find",
+      "stage_ms": {"frame_seeds", "coarse", "selection", "refinement"}, "hypotheses_per_s", "oracle_s",
+      "found": {"dt_mm", "iou", "score", "truth_score"}, "nearest_candidate": {"dt_mm", "deg"},
+      "nearest_survivor": {"dt_mm", "deg"}}, ...]}
+
+Cases: M1, M2, M3 at 640x480 and M4 at 1280x960, the header's default parameters; one synth.make_frame frame per case
+(background plane, occluder, noise, 5 % NaN) with the object at a seeded random rotation, z in 0.55-0.9 m.
+ms_per_find: host clock around rbs_find_run, averaged over the timed finds (after a warm-up find); stage_ms: the
+library's HIP events of the last find.  oracle_s: the CPU oracle's (EAGER, one core) time per pose at the coarse
+resolution, measured on --oracle-poses poses, times the hypothesis count, plus the same at full resolution times the
+refinement's children.  nearest_candidate / nearest_survivor: the coarse stage's closest pose to the truth (translation,
+then rotation angle of that pose) -- whether the search had the object in hand before the refinement.
+Usage: python tools/find_object_timing.py [--finds N] [--oracle-poses P] [--cases m1,m2,m3,m4]
+"""
+import os
+
+for _v in ("OMP_NUM_THREADS", "OPENBLAS_NUM_THREADS", "MKL_NUM_THREADS"):   # the oracle: one core
+    os.environ[_v] = "1"
+
+import argparse  # noqa: E402
+import json  # noqa: E402
+import math  # noqa: E402
+import sys  # noqa: E402
+import time  # noqa: E402
+
+import numpy as np  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+
+import oracle_binding as ob  # noqa: E402
+import scenarios as sc  # noqa: E402
+from dbot_ros_amd import CameraData, RbSensor, synth  # noqa: E402
+from dbot_ros_amd.finder import ObjectFinder  # noqa: E402
+from dbot_ros_amd.pose import quat_to_matrix  # noqa: E402
+
+CASES = {"m1": ("m1", 640, 480), "m2": ("m2", 640, 480), "m3": ("m3", 640, 480), "m4": ("m4", 1280, 960)}
+
+
+def scene(sensor, cam, seed):
+    rng = np.random.default_rng(seed)
+    q = rng.normal(size=4)
+    R = quat_to_matrix(q / np.linalg.norm(q))
+    z = rng.uniform(0.55, 0.9)
+    K = cam.camera_matrix
+    u, v = rng.uniform(0.3, 0.7) * cam.cols, rng.uniform(0.3, 0.7) * cam.rows
+    truth = np.concatenate([R.ravel(), [(u - K[0, 2]) / K[0, 0] * z, (v - K[1, 2]) / K[1, 1] * z, z]])
+    d = sensor.render_depth(truth)
+    return truth, synth.make_frame(np.where(np.isfinite(d), d, np.inf), cam.rows, cam.cols, rng)
+
+
+def nearest(poses, truth):
+    if len(poses) == 0:
+        return None
+    dt = np.linalg.norm(poses[:, 9:] - truth[9:], axis=1)
+    i = int(np.argmin(dt))
+    c = (np.trace(poses[i, :9].reshape(3, 3).T @ truth[:9].reshape(3, 3)) - 1.0) / 2.0
+    return {"dt_mm": round(float(dt[i]) * 1e3, 2), "deg": round(math.degrees(math.acos(max(-1.0, min(1.0, c)))), 1)}
+
+
+def oracle_s_per_pose(om, K, rows, cols, P, frame, poses):
+    o = ob.Oracle(om, CameraData(K, rows, cols), P, max_particles=len(poses), mode=ob.EAGER)
+    o.reset()
+    o.set_observation(np.asarray(frame, dtype=np.float64))
+    t0 = time.perf_counter()
+    o.loglikes_poses(poses.reshape(len(poses), 1, 12), np.zeros(len(poses), dtype=np.int32), update=False)
+    s = (time.perf_counter() - t0) / len(poses)
+    o.close()
+    return s
+
+
+def run_case(name, finds, oracle_poses, seed=101):
+    mesh, cols, rows = CASES[name]
+    om, cam, P = sc.make_scene((mesh,), cols, rows, max_particles=1)
+    with RbSensor(om, cam, P, max_particles=1) as sensor:
+        truth, frame = scene(sensor, cam, seed)
+        p = ObjectFinder.Parameters()
+        with ObjectFinder(sensor, om, p) as fnd:
+            fnd.find(frame)                                       # warm-up
+            t0 = time.perf_counter()
+            for _ in range(finds):
+                r = fnd.find(frame)
+            ms = (time.perf_counter() - t0) / finds * 1e3
+            st = fnd.stage_ms()
+            _, _, _, info = fnd.stage("seeds")
+            cp, _, _, _ = fnd.stage("candidates")
+            sp, _, _, _ = fnd.stage("survivors")
+            kp, _, _, _ = fnd.stage("children", p.rounds - 1) if p.rounds else (np.zeros((0, 12)),) * 4
+        crows, ccols, f, hyp = int(info[0]), int(info[1]), int(info[2]), int(info[3])
+        best = r.poses[0] if len(r.poses) else None
+        d_best, d_truth = sensor.render_depth(best) if best is not None else None, sensor.render_depth(truth)
+    with RbSensor(om, cam, P, max_particles=1024) as ref:
+        ref.reset()
+        ref.set_observation(frame)
+        truth_score = float(ref.loglikes_poses(np.repeat(truth[None], 1024, 0), np.zeros(1024, dtype=np.int32))[0])
+    Kc = cam.camera_matrix.copy()
+    Kc[:2] /= f
+    coarse = frame.reshape(rows, cols)[: crows * f: f, : ccols * f: f].ravel()
+    sample = cp[:oracle_poses] if len(cp) else np.repeat(truth[None], oracle_poses, 0)
+    per_coarse = oracle_s_per_pose(om, Kc, crows, ccols, P, coarse, sample)
+    per_full = oracle_s_per_pose(om, cam.camera_matrix, rows, cols, P, frame, kp[: max(1, oracle_poses // 4)]) if len(kp) else 0.0
+    children = p.n_survivors * p.children * p.rounds
+    found = None
+    if best is not None:
+        a, b = np.isfinite(d_best), np.isfinite(d_truth)
+        found = {"dt_mm": round(float(np.linalg.norm(best[9:] - truth[9:])) * 1e3, 2),
+                 "iou": round(float((a & b).sum() / max((a | b).sum(), 1)), 3),
+                 "score": round(float(r.scores[0]), 1), "truth_score": round(truth_score, 1)}
+    return {"case": name, "size": [cols, rows], "coarse": [ccols, crows], "hypotheses": hyp, "children": children,
+            "ms_per_find": round(ms, 2),
+            "stage_ms": dict(zip(("frame_seeds", "coarse", "selection", "refinement"), (round(x, 3) for x in st[:4]))),
+            "hypotheses_per_s": round(hyp / (st[1] * 1e-3)) if st[1] > 0 else None,
+            "oracle_s": round(per_coarse * hyp + per_full * children, 1),
+            "found": found, "nearest_candidate": nearest(cp, truth), "nearest_survivor": nearest(sp, truth)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--finds", type=int, default=5)
+    ap.add_argument("--oracle-poses", type=int, default=16)
+    ap.add_argument("--cases", default="m1,m2,m3,m4")
+    a = ap.parse_args()
+    cases = [run_case(c, a.finds, a.oracle_poses) for c in a.cases.split(",")]
+    print(json.dumps({"tool": "find_object_timing", "cases": cases}))
+
+
+if __name__ == "__main__":
+    main()
