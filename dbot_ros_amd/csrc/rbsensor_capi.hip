@@ -55,16 +55,12 @@ struct rbs_handle {
     float* d_frame = nullptr;
     double* d_aux = nullptr;    // per-frame-pixel model terms, [npx][4] (precision F64), of a frame ingested from device memory
     double* d_aux_slot[2] = {nullptr, nullptr};   // ... of the host frame uploaded into d_fin[k] (computed on the upload stream)
-    const double* cur_aux = nullptr;              // what the kernels read: d_aux, or d_aux_slot[cur_slot]
     float* d_pbg = nullptr;
     float* d_occ[2] = {nullptr, nullptr};
     int cur = 0;
     int pending_frames = 0;     // set_observation calls since the last updating loglikes
-    const float* lazy_frame = nullptr;   // frame handed over by rbs_set_observation_device whose ingest
-    hipStream_t lazy_stream = nullptr;   //   kernel has not been launched yet (it rides on the next loglikes)
     double* d_poses = nullptr;
     int* d_indices = nullptr;
-    double* d_out = nullptr;
     int* d_rects[2] = {nullptr, nullptr};  // [max_particles][4], alternating per call: the previous
                                 // call's copy kernel may still be reading its rectangles
     rbs::Groups* d_groups[2] = {nullptr, nullptr};   // [max_particles] per-group rectangles (several bodies), alternating like d_rects
@@ -194,26 +190,32 @@ struct rbs_handle {
     float* h_frames_dev[2] = {nullptr, nullptr};   // ... as the device addresses them
     size_t frame_pull_bytes = 128 * 1024;      // frames up to this size are read from the staging buffer by a kernel (RBS_FRAME_PULL_BYTES)
     hipEvent_t ev_frame[2] = {nullptr, nullptr};   // the upload out of h_frames[k] into d_fin[k] has finished
-    int frame_slot = 0;
     // Host frames travel on their own stream into one of two device staging buffers, and the launch
     // stream only waits for the upload where it ingests the frame: a frame handed over while the
     // previous frame's kernels are still running (rbs_tracker_submit) is uploaded beside them.
     hipStream_t up_stream = nullptr;
     float* d_fin[2] = {nullptr, nullptr};
-    hipEvent_t ev_used[2] = {nullptr, nullptr};    // the ingest kernel that read d_fin[k] has run
-    int lazy_slot = -1;                            // d_fin slot the pending (lazy) frame sits in
-    // A host frame needs no ingest on the launch stream (precision F64: its per-pixel terms are
-    // computed behind the copy on the upload stream, into d_aux_slot[k]): the staging
-    // image d_fin[k] IS the observation until the next frame replaces it, and only the raster
-    // kernel (not the rectangles kernel before it) waits for the upload.
-    const float* cur_frame = nullptr;              // what the kernels read: d_frame, or d_fin[cur_slot]
-    int cur_slot = -1;
-    int frame_wait = -1;                           // ev_frame[] the raster launches wait for
+    hipEvent_t ev_used[2] = {nullptr, nullptr};    // the readers of d_fin[k] have been enqueued up to here
     hipEvent_t ev_reader = nullptr;                // orders the handle's stream after a reader on a caller's stream
-    // the older routes, kept behind environment switches read at rbs_create (A/B runs, differential tests):
-    bool frame_ingest = false;                     // RBS_FRAME_INGEST=1: host frames are copied into d_frame by the ingest kernel
-    bool host_copies = false;                      // RBS_HOST_STAGED_COPIES=1: poses / results travel as H2D / D2H copies
-    float* h_frame = nullptr;   // = h_frames[frame_slot]
+    // The observation and the frame on its way to becoming it (only the frame section of this file touches them).  A host
+    // frame needs no ingest on the launch stream (F64: its per-pixel terms are computed behind the copy, into d_aux_slot[k]):
+    // the staging image d_fin[cur] IS the observation, and only the raster kernel waits for its upload.  cur = -1: d_frame,
+    // where a device frame is ingested.  `next` holds at most ONE frame -- every hand-over stages, ingests or abandons the one
+    // before it: a borrowed host frame or a device frame whose ingest rides on the next loglikes on `stream` (both counted by
+    // the model clock), or a frame uploaded AHEAD into staging image `slot`, waiting beside the observation.
+    struct NextFrame {
+        enum Kind { NONE, BORROWED_F64, BORROWED_F32, DEVICE, AHEAD } kind = NONE;
+        const void* src = nullptr;      // BORROWED_*, DEVICE
+        hipStream_t stream = nullptr;   // DEVICE
+        int slot = -1;                  // AHEAD
+        bool borrowed() const { return kind == BORROWED_F64 || kind == BORROWED_F32; }
+    };
+    struct FrameState {
+        int cur = -1;             // staging image that is the observation, -1: d_frame
+        int stage = 0;            // pinned image (h_frames) the next host frame is staged in
+        bool acquired = false;    // rbs_acquire_frame_buffer without its rbs_commit_frame_buffer yet
+        NextFrame next;
+    } fr;
     hipStream_t stream = nullptr;
     hipStream_t copy_stream = nullptr;   // the copy kernel runs here, beside the raster kernel
     hipEvent_t ev_fork = nullptr;
@@ -236,11 +238,6 @@ struct rbs_handle {
     long calls = 0;
     int join_pending = -1;      // ring slot whose copy kernel later work on the planes must wait for
     std::string err;
-    bool frame_acquired = false;       // rbs_acquire_frame_buffer without its rbs_commit_frame_buffer yet
-    int prefetched_slot = -1;          // staging slot holding a frame uploaded ahead of its turn (rbs_loglikes_prefetch), -1: none
-    const float* borrowed_f32 = nullptr;   // ... the same for a float frame (the device tracker's frames at small particle counts)
-    const double* borrowed = nullptr;  // rbs_set_observation_borrowed: the caller's frame, staged by the next host-pointer likelihood call
-                                       // while that call's geometry kernel runs (or by whatever else needs the observation first)
     // A call that failed half-way through a fan-out (some shards enqueued, others not) or between a
     // tracker's buffer swaps leaves the handle's double buffers out of step: every later call is
     // refused with this message until rbs_reset (rbs_tracker_initialize) re-establishes a known state.
@@ -324,6 +321,12 @@ int32_t fail(rbs_handle* h, int32_t code, const std::string& msg)
     h->err = msg;
     return code;
 }
+#define RBS_REFUSE_POISONED(h)                                                                \
+    do {                                                                                      \
+        if ((h)->poisoned)                                                                    \
+            return fail(h, RBS_ERR_HIP, "the handle is in an undefined state after a failed call (" + (h)->poison_msg + \
+                                            "): call rbs_reset / rbs_tracker_initialize");    \
+    } while (0)
 
 // alpha/beta of the occlusion process over n frames (affine form of SURVEY A.5), rounded
 // once to float -- the same rule as oracle orc_eager_coeffs().
@@ -376,25 +379,361 @@ size_t tiles_upper_bound(int cols, int rows, int max_w, int cap_px)
     return worst;
 }
 
-// Launch the ingest of a frame rbs_set_observation_device left pending, on the stream it was
-// given for; `then` (if not that stream) is ordered after it.
-int32_t flush_lazy_frame(rbs_handle* h, hipStream_t then)
+// ----------------------------------------------------------------------------- the frame section (rbs_handle::fr)
+// A hand-over: frame_begin, the entry point's own checks, frame_ready, one hand_over_*.  A reader: make_current (or, in
+// enqueue_loglikes, its pieces), then obs_frame / obs_aux.
+using NextFrame = rbs_handle::NextFrame;
+
+// What the kernels read: the staging image of slot fr.cur (F64: with its model terms), or d_frame / d_aux.
+const float* obs_frame(const rbs_handle* h) { return h->fr.cur >= 0 ? h->d_fin[h->fr.cur] : h->d_frame; }
+const double* obs_aux(const rbs_handle* h) { return h->fr.cur >= 0 ? h->d_aux_slot[h->fr.cur] : h->d_aux; }
+float* staging(const rbs_handle* h) { return h->h_frames[h->fr.stage]; }
+
+// Can borrow: only a handle that stages a frame between the two kernels of the split launch takes one without copying it at
+// once (one device, binary64 likelihood, windowed planes).
+bool can_borrow(const rbs_handle* h)
 {
-    if (!h->lazy_frame) return RBS_OK;
+    return h->shards.empty() && !h->group && h->precision == RBS_PRECISION_F64 && h->windowed;
+}
+
+// The pending device frame if its ingest is to run on stream s, taken: the caller launches that ingest (enqueue_loglikes: on
+// the rectangles kernel's launch).  nullptr otherwise.
+const float* take_device_frame(rbs_handle* h, hipStream_t s)
+{
+    if (h->fr.next.kind != NextFrame::DEVICE || h->fr.next.stream != s) return nullptr;
+    const float* f = static_cast<const float*>(h->fr.next.src);
+    h->fr.next = {};
+    return f;
+}
+
+// Launch the ingest of a device frame left pending, on the stream it was given for; `then` (if not that stream) is ordered
+// after it.
+int32_t flush_device_frame(rbs_handle* h, hipStream_t then)
+{
+    if (h->fr.next.kind != NextFrame::DEVICE) return RBS_OK;
+    const hipStream_t fs = h->fr.next.stream;
+    const float* f = take_device_frame(h, fs);
     const size_t n = (size_t)h->npx;
     // (precision F32 keeps no per-pixel terms: a frame already in the handle's buffer needs nothing)
-    if (h->d_aux || h->lazy_frame != h->d_frame)
-    hipLaunchKernelGGL(rbs::frame_aux_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->lazy_stream,
-                       h->lazy_frame, h->d_aux, h->d_pbg, h->npx, h->base.tw, h->base.ms, h->base.sf,
-                       h->base.lambda, h->lazy_frame == h->d_frame ? (float*)nullptr : h->d_frame);
+    if (h->d_aux || f != h->d_frame)
+    hipLaunchKernelGGL(rbs::frame_aux_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, fs,
+                       f, h->d_aux, h->d_pbg, h->npx, h->base.tw, h->base.ms, h->base.sf,
+                       h->base.lambda, f == h->d_frame ? (float*)nullptr : h->d_frame);
     RBS_HIP(h, hipGetLastError());
-    h->lazy_frame = nullptr;
-    if (h->lazy_slot >= 0) { RBS_HIP(h, hipEventRecord(h->ev_used[h->lazy_slot], h->lazy_stream)); h->lazy_slot = -1; }
-    if (then != h->lazy_stream) {
-        RBS_HIP(h, hipEventRecord(h->ev_fork, h->lazy_stream));
+    if (then != fs) {
+        RBS_HIP(h, hipEventRecord(h->ev_fork, fs));
         RBS_HIP(h, hipStreamWaitEvent(then, h->ev_fork, 0));
     }
     return RBS_OK;
+}
+
+// A device frame pending on a caller's stream is ingested there, into d_frame: that stream first waits for the readers
+// enqueued on the handle's stream so far.
+int32_t device_frame_after_readers(rbs_handle* h)
+{
+    if (h->fr.next.kind != NextFrame::DEVICE || h->fr.next.stream == h->stream) return RBS_OK;
+    RBS_HIP(h, hipEventRecord(h->ev_reader, h->stream));
+    RBS_HIP(h, hipStreamWaitEvent(h->fr.next.stream, h->ev_reader, 0));
+    return RBS_OK;
+}
+
+// Read done: frame N + 2's upload into the observation's staging image waits for the readers enqueued on s so far.
+int32_t frame_read_done(rbs_handle* h, hipStream_t s)
+{
+    if (h->fr.cur >= 0) RBS_HIP(h, hipEventRecord(h->ev_used[h->fr.cur], s));
+    return RBS_OK;
+}
+
+// Stream s waits for the upload of the observation's staging image (nothing to wait for on d_frame).
+int32_t wait_for_upload(rbs_handle* h, hipStream_t s)
+{
+    if (h->fr.cur >= 0) RBS_HIP(h, hipStreamWaitEvent(s, h->ev_frame[h->fr.cur], 0));
+    return RBS_OK;
+}
+
+// The staging image that served as the observation stops doing so (a new frame is coming): it may
+// be overwritten once everything launched so far has run.
+int32_t release_frame_slot(rbs_handle* h)
+{
+    if (int32_t rc = frame_read_done(h, h->stream)) return rc;
+    h->fr.cur = -1;
+    return RBS_OK;
+}
+
+// H2D of a frame staged in pinned host memory (`src`, normally staging(h)) on the upload stream into
+// the device staging buffer of the current slot, which then IS the observation; the raster kernel
+// waits for the upload (wait_for_upload).
+// `pageable`: the caller's own frame, still to be staged into `src` (= staging(h)) -- staged and sent
+// in h->upload_chunks pieces, so that the copy engine carries one piece while the host copies the next
+// (a 640x480 frame: 41 us of memcpy + 29 us of transfer one after the other, ~20 us less interleaved).
+// dbot hands the image over as a vector of DOUBLES (R:source/dbot_ros/util/ros_interface.h:152-168): double -> float while
+// staging.  The scalar loop converts 2 values per instruction on a baseline x86-64 build; AVX2 (every host this library
+// meets; checked at run time) does 4 per instruction and halves the time of a 640x480 frame.
+#if defined(__x86_64__)
+__attribute__((target("avx2"))) static void convert_f64_f32_avx2(float* __restrict__ dst, const double* __restrict__ src, size_t n)
+{
+    size_t p = 0;
+    for (; p + 8 <= n; p += 8) {
+        const __m128 a = _mm256_cvtpd_ps(_mm256_loadu_pd(src + p)), b = _mm256_cvtpd_ps(_mm256_loadu_pd(src + p + 4));
+        _mm256_storeu_ps(dst + p, _mm256_set_m128(b, a));
+    }
+    for (; p < n; ++p) dst[p] = (float)src[p];
+}
+// AVX-512 hosts: 8 values per instruction and streaming stores (the staging image is read next by the copy engine, not by
+// this core: no line of it needs to be fetched to be overwritten) -- 42 us against 50 per 640x480 frame out of L3 (EPYC 9575F,
+// tools/dbg/convert_bench.cpp); the plugin path gains ~1 %
+__attribute__((target("avx512f"))) static void convert_f64_f32_avx512(float* __restrict__ dst, const double* __restrict__ src, size_t n)
+{
+    size_t p = 0;
+    for (; p + 16 <= n; p += 16) {
+        const __m256 a = _mm512_cvtpd_ps(_mm512_loadu_pd(src + p)), b = _mm512_cvtpd_ps(_mm512_loadu_pd(src + p + 8));
+        _mm512_stream_ps(dst + p, _mm512_castpd_ps(_mm512_insertf64x4(_mm512_castpd256_pd512(_mm256_castps_pd(a)), _mm256_castps_pd(b), 1)));
+    }
+    _mm_sfence();
+    for (; p < n; ++p) dst[p] = (float)src[p];
+}
+#endif
+static void convert_f64_f32(float* __restrict__ dst, const double* __restrict__ src, size_t n)
+{
+#if defined(__x86_64__)
+    static const bool avx512 = __builtin_cpu_supports("avx512f") && !std::getenv("RBS_NO_AVX512");
+    if (avx512 && (reinterpret_cast<uintptr_t>(dst) & 63) == 0) return convert_f64_f32_avx512(dst, src, n);
+    static const bool avx2 = __builtin_cpu_supports("avx2");
+    if (avx2) return convert_f64_f32_avx2(dst, src, n);
+#endif
+    for (size_t p = 0; p < n; ++p) dst[p] = (float)src[p];
+}
+
+// Precision F64: the per-pixel model terms of the frame in d_fin[k], computed right behind its copy, on the upload stream,
+// into the slot's own table -- the launch stream does not wait for the frame until the raster kernel needs it, so a caller's
+// transition and the rectangles kernel run while the frame is still travelling (a tracker frame: 35 us of 400).
+int32_t slot_aux(rbs_handle* h, int k)
+{
+    if (!h->d_aux) return RBS_OK;
+    hipLaunchKernelGGL(rbs::frame_aux_kernel, dim3((unsigned)((h->npx + 255) / 256)), dim3(256), 0, h->up_stream,
+                       h->d_fin[k], h->d_aux_slot[k], h->d_pbg, h->npx, h->base.tw, h->base.ms, h->base.sf, h->base.lambda, (float*)nullptr);
+    RBS_HIP(h, hipGetLastError());
+    return RBS_OK;
+}
+
+int32_t upload_frame(rbs_handle* h, const float* src, const float* pageable = nullptr, const double* pageable_f64 = nullptr)
+{
+    const int k = h->fr.stage;
+    const size_t n = (size_t)h->npx;
+    h->fr.next = {};   // (a frame uploaded ahead, or borrowed and never evaluated, is abandoned; a device frame: flushed first)
+    // (the two staging images alternate, so k is never the image that serves as the observation --
+    // should it be, its readers are recorded first: the wait below must not be on a stale event)
+    if (k == h->fr.cur)
+        if (int32_t rc = release_frame_slot(h)) return rc;
+    RBS_HIP(h, hipStreamWaitEvent(h->up_stream, h->ev_used[k], 0));   // d_fin[k]: its readers were enqueued two frames ago
+    // A SMALL frame (the reference's default operating point is 80x60: 19 KB) is not worth a transfer: a copy-engine
+    // job costs ~11 us before it moves a byte and ~9 more until a kernel behind it starts.  The kernel that computes
+    // the frame's model terms reads it where the host staged it (this handle's pinned buffer, over PCIe) and leaves
+    // the observation in d_fin[k] as it goes (precision F32: that copy is all it does).
+    const bool pull = h->frame_pull_bytes > 0 && n * sizeof(float) <= h->frame_pull_bytes && h->h_frames_dev[k] &&
+                      (pageable || pageable_f64 || src == h->h_frames[k]);
+    if (pageable || pageable_f64) {
+        float* stage = h->h_frames[k];
+        // (a frame of doubles takes the host ~4x as long to stage as a frame of floats: twice the pieces)
+        const size_t want = (size_t)h->upload_chunks * (pageable_f64 && h->upload_chunks > 1 ? 2 : 1);
+        const int pieces = h->quiet ? (int)std::max<size_t>(1, std::min<size_t>(want, n / 16384)) : 1;
+        const size_t per = ((n + pieces - 1) / pieces + 1023) / 1024 * 1024;
+        for (size_t off = 0; off < n; off += per) {
+            const size_t len = std::min(per, n - off);
+            if (pageable) std::memcpy(stage + off, pageable + off, len * sizeof(float));
+            else convert_f64_f32(stage + off, pageable_f64 + off, len);   // dbot hands a vector of doubles
+            if (!pull) RBS_HIP(h, hipMemcpyAsync(h->d_fin[k] + off, stage + off, len * sizeof(float), hipMemcpyHostToDevice, h->up_stream));
+        }
+    } else if (!pull) {
+        RBS_HIP(h, hipMemcpyAsync(h->d_fin[k], src, n * sizeof(float), hipMemcpyHostToDevice, h->up_stream));
+    }
+    if (pull) {
+        hipLaunchKernelGGL(rbs::frame_aux_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->up_stream,
+                           h->h_frames_dev[k], h->d_aux ? h->d_aux_slot[k] : (double*)nullptr, h->d_pbg, h->npx, h->base.tw,
+                           h->base.ms, h->base.sf, h->base.lambda, h->d_fin[k]);
+        RBS_HIP(h, hipGetLastError());
+    } else if (int32_t rc = slot_aux(h, k)) {
+        return rc;
+    }
+    RBS_HIP(h, hipEventRecord(h->ev_frame[k], h->up_stream));
+    if (int32_t rc = release_frame_slot(h)) return rc;
+    h->fr.cur = k;   // (and, F64, its slot's table the model terms) until the next frame replaces it
+    return RBS_OK;
+}
+
+// The pinned frame buffer the next host frame is staged in: the other one of the two, once the
+// upload that last used it has finished (two frames ago: in practice never a wait).
+int32_t next_frame_staging(rbs_handle* h)
+{
+    h->fr.stage ^= 1;
+    RBS_HIP(h, hipEventSynchronize(h->ev_frame[h->fr.stage]));
+    return RBS_OK;
+}
+
+// rbs_set_observation_borrowed's frame becomes the observation now: staged (double -> float) into pinned memory and sent.
+int32_t stage_borrowed(rbs_handle* h)
+{
+    const NextFrame b = h->fr.next;
+    if (!b.borrowed()) return RBS_OK;
+    h->fr.next = {};
+    if (int32_t rc = next_frame_staging(h)) return rc;
+    if (b.kind == NextFrame::BORROWED_F64) return upload_frame(h, staging(h), nullptr, static_cast<const double*>(b.src));
+    return upload_frame(h, staging(h), static_cast<const float*>(b.src));
+}
+
+// A borrowed frame is the caller's memory until the likelihood call behind it RETURNS -- however it returns.  A call that is
+// refused or fails before its kernels staged the frame must not leave the pointer behind for a later call to read: on the way
+// out the frame is copied after all (it becomes the observation, as rbs_set_observation would have made it), or dropped where
+// the handle takes no more work.
+struct BorrowedFrameGuard {
+    rbs_handle* h;
+    ~BorrowedFrameGuard()
+    {
+        if (!h->fr.next.borrowed()) return;
+        if (h->poisoned || hipSetDevice(h->device) != hipSuccess) { h->fr.next = {}; return; }
+        const std::string keep = h->err;      // (the message of the failure that brought us here stays rbs_last_error's)
+        const int32_t rc = stage_borrowed(h);   // (whatever it returns, the frame is no longer the handle's)
+        if (rc == RBS_OK) h->err = keep;
+    }
+};
+
+// The NEXT frame, uploaded while the current one is still the observation (rbs_loglikes_prefetch: called between
+// the launch of a call's kernels and the wait for its results, so the host's staging copy and the transfer pass
+// behind the raster kernel): staged into the other pinned image, sent on the upload stream, its model terms
+// (precision F64) computed behind it -- everything upload_frame does except making it the observation.
+// What rbs_loglikes_prefetch needs, checked BEFORE the call's kernels are enqueued (ADVICE r4: a prefetch that failed
+// behind an updating call left the caller with a failed call whose planes had already flipped).
+int32_t prefetch_check(rbs_handle* h)
+{
+    if (h->fr.next.kind == NextFrame::AHEAD)
+        return fail(h, RBS_ERR_INVALID_ARGUMENT, "loglikes_prefetch: the frame uploaded ahead by the previous rbs_loglikes_prefetch has not been "
+                                                 "installed yet (rbs_set_observation_prefetched)");
+    if ((h->fr.stage ^ 1) == h->fr.cur)
+        return fail(h, RBS_ERR_INVALID_ARGUMENT, "loglikes_prefetch: the staging image the next frame would use is the current observation "
+                                                 "(the staging images did not alternate)");
+    return RBS_OK;
+}
+
+int32_t prefetch_frame(rbs_handle* h, const float* depth)
+{
+    if (int32_t rc = prefetch_check(h)) return rc;   // (before the staging image is switched: a refused call changes nothing)
+    if (int32_t rc = next_frame_staging(h)) return rc;
+    const int k = h->fr.stage;
+    const size_t n = (size_t)h->npx;
+    RBS_HIP(h, hipStreamWaitEvent(h->up_stream, h->ev_used[k], 0));   // d_fin[k]: its readers were enqueued two frames ago
+    std::memcpy(h->h_frames[k], depth, n * sizeof(float));
+    RBS_HIP(h, hipMemcpyAsync(h->d_fin[k], h->h_frames[k], n * sizeof(float), hipMemcpyHostToDevice, h->up_stream));
+    if (int32_t rc = slot_aux(h, k)) return rc;
+    RBS_HIP(h, hipEventRecord(h->ev_frame[k], h->up_stream));
+    h->fr.next = {NextFrame::AHEAD, nullptr, nullptr, k};
+    return RBS_OK;
+}
+
+
+// Make current: the observation complete in stream s's order -- a borrowed frame staged, a device frame ingested, the upload
+// of a host frame waited for.
+int32_t make_current(rbs_handle* h, hipStream_t s)
+{
+    if (int32_t rc = stage_borrowed(h)) return rc;
+    if (int32_t rc = flush_device_frame(h, s)) return rc;
+    return wait_for_upload(h, s);
+}
+
+// Begin, the prologue of every hand-over: a handle left undefined by a failed call is refused, and a buffer acquired but never
+// committed is abandoned.  Then, once the entry point has checked its frame, frame_ready: on the handle's device, a device
+// frame handed over before and never evaluated is ingested (its clock tick stays counted), ordered before stream s.
+int32_t frame_begin(rbs_handle* h)
+{
+    RBS_REFUSE_POISONED(h);
+    h->fr.acquired = false;
+    return RBS_OK;
+}
+int32_t frame_ready(rbs_handle* h, hipStream_t s)
+{
+    RBS_HIP(h, hipSetDevice(h->device));
+    return flush_device_frame(h, s);
+}
+
+// Hand over: the frame becomes the observation -- a borrowed or device frame at the next call that needs it -- whatever waited
+// in fr.next is abandoned, and the model clock advances one frame.
+// ... the caller's host frame (floats or doubles), copied now
+int32_t hand_over_host(rbs_handle* h, const float* f32, const double* f64)
+{
+    if (int32_t rc = next_frame_staging(h)) return rc;
+    if (int32_t rc = upload_frame(h, staging(h), f32, f64)) return rc;   // (staged and sent piece by piece)
+    h->pending_frames += 1;
+    return RBS_OK;
+}
+// ... a frame in pinned memory: the committed buffer (a group's: shard 0's, sent to every shard)
+int32_t hand_over_pinned(rbs_handle* h, const float* src)
+{
+    if (int32_t rc = upload_frame(h, src)) return rc;
+    h->pending_frames += 1;
+    return RBS_OK;
+}
+// ... the driver's full-resolution frame, sub-sampled by f.
+// The reference's rule (R:source/dbot_ros/util/ros_interface.h:152-168): evaluated(r, c) =
+// native(r f, c f) -- applied while the frame is staged, so that only the rows*cols values the
+// sensor evaluates are copied and sent (1/f^2 of the driver's frame: 19 KB of 1.2 MB at the
+// reference's default factor 8) and the frame then travels like any other host frame.
+int32_t hand_over_native(rbs_handle* h, const float* native, int width, int f)
+{
+    if (int32_t rc = next_frame_staging(h)) return rc;
+    for (int r = 0; r < h->rows; ++r) {
+        const float* src = native + (size_t)r * f * width;
+        float* dst = staging(h) + (size_t)r * h->cols;
+        for (int c = 0; c < h->cols; ++c) dst[c] = src[(size_t)c * f];
+    }
+    return hand_over_pinned(h, staging(h));
+}
+// ... the caller's host frame, borrowed (can_borrow): a borrowed frame nobody evaluated is simply replaced
+void hand_over_borrowed(rbs_handle* h, const float* f32, const double* f64)
+{
+    h->fr.next = f64 ? NextFrame{NextFrame::BORROWED_F64, f64} : NextFrame{NextFrame::BORROWED_F32, f32};
+    h->pending_frames += 1;
+}
+// ... a frame in device memory, ingested on stream s by whatever needs it first
+int32_t hand_over_device(rbs_handle* h, const float* d_depth, hipStream_t s)
+{
+    if (int32_t rc = release_frame_slot(h)) return rc;
+    h->fr.next = {NextFrame::DEVICE, d_depth, s};
+    h->pending_frames += 1;
+    return RBS_OK;
+}
+// ... the frame uploaded ahead (fr.next is AHEAD)
+int32_t hand_over_ahead(rbs_handle* h)
+{
+    const int k = h->fr.next.slot;
+    h->fr.next = {};
+    if (int32_t rc = release_frame_slot(h)) return rc;   // the readers of the frame it replaces are on the launch stream by now
+    h->fr.cur = k;
+    h->pending_frames += 1;
+    return RBS_OK;
+}
+
+// The pinned image the caller writes the next frame into (rbs_acquire_frame_buffer).  One image (shard 0's) feeds every device
+// of a group: it is free once every shard's upload of the frame before last has finished.
+int32_t acquire_staging(rbs_handle* h, float** buf)
+{
+    rbs_handle* const s0 = h->shards.empty() ? h : h->shards[0];
+    const int k = s0->fr.stage ^ 1;
+    for (size_t i = 0; i < std::max<size_t>(1, h->shards.size()); ++i) {
+        rbs_handle* sh = h->shards.empty() ? h : h->shards[i];
+        RBS_HIP(h, hipSetDevice(sh->device));
+        sh->fr.stage = k;
+        RBS_HIP(h, hipEventSynchronize(sh->ev_frame[k]));
+    }
+    *buf = staging(s0);
+    h->fr.acquired = true;
+    return RBS_OK;
+}
+
+// rbs_reset: an acquired buffer, a borrowed frame and a frame uploaded ahead belong to the session that ended (a device frame
+// has been ingested by the drain before).
+void frame_abandon(rbs_handle* h)
+{
+    h->fr.acquired = false;
+    h->fr.next = {};
 }
 
 // The instantiations of the raster kernel: updating or read-only call, likelihood precision,
@@ -481,8 +820,6 @@ void launch_raster(const rbs_handle* h, bool update, dim3 grid, dim3 block, size
     }
 }
 
-int32_t stage_borrowed(rbs_handle* h);
-
 // The shared plane's own step on stream s: bgp[1 - cur] = step(bgp[cur]), re-based first on local slot `rebase` of the planes
 // (occ, win, reg) -- its owner's, wherever they live -- or (-2) reset to the scalar level.
 int32_t launch_bgp_step(rbs_handle* h, const DevParams& P, const float* occ, const int4* win, const int4* reg, int rebase, hipStream_t s)
@@ -527,7 +864,7 @@ int32_t enqueue_loglikes(rbs_handle* h, const double* d_poses, const int* d_indi
     h->quiet = false;
     // a borrowed frame (rbs_set_observation_borrowed) is staged BETWEEN the two kernels of the split launch, while the
     // geometry kernel -- which needs no frame -- runs; a handle that cannot launch that way stages it here and now
-    if ((h->borrowed || h->borrowed_f32) && !(h->precision == RBS_PRECISION_F64 && h->windowed && s == h->stream))
+    if (!(can_borrow(h) && s == h->stream))
         if (int32_t rc = stage_borrowed(h)) return rc;
     DevParams P = h->base;
     occlusion_coeffs(h, h->pending_frames, &P.alpha, &P.beta);
@@ -548,8 +885,8 @@ int32_t enqueue_loglikes(rbs_handle* h, const double* d_poses, const int* d_indi
     P.win_src = h->d_win[h->cur];
     P.win_dst = h->d_win[1 - h->cur];
     P.win_used = h->d_win_used;
-    P.frame = h->cur_frame;
-    P.aux = h->cur_aux;
+    P.frame = obs_frame(h);
+    P.aux = obs_aux(h);
     P.pbg = h->d_pbg;
     P.occ_src = h->d_occ[h->cur];
     P.occ_dst = h->d_occ[1 - h->cur];
@@ -670,7 +1007,7 @@ int32_t enqueue_loglikes(rbs_handle* h, const double* d_poses, const int* d_indi
                                                                      : (h->exact ? rbs::kTilePxExact : f64 ? rbs::kTilePxF64 : rbs::kTilePx);
     // split launch: binary64 likelihood on windowed planes (the tile size is the handle's for its whole life, like the
     // monolith's: the split of a rectangle into items decides the order in which a particle's partial sums are added)
-    const bool have_borrowed = h->borrowed != nullptr || h->borrowed_f32 != nullptr;
+    const bool have_borrowed = h->fr.next.borrowed();
     bool split = (h->split || have_borrowed) && f64 && h->windowed;   // (the same tile, the same items, the same bits either way)
     if (split && !h->exact && !(!h->windowed && h->raster_blocks <= 2 * h->cu_count)) P.tile_px = rbs::kDepthTilePx;   // (= kTilePxF64 already; stamped planes: their own, smaller)
     P.tile_w = 256;
@@ -730,8 +1067,8 @@ int32_t enqueue_loglikes(rbs_handle* h, const double* d_poses, const int* d_indi
             split = false;
             if (have_borrowed) {
                 if (int32_t rc = stage_borrowed(h)) return rc;
-                P.frame = h->cur_frame;
-                P.aux = h->cur_aux;
+                P.frame = obs_frame(h);
+                P.aux = obs_aux(h);
             }
         }
     }
@@ -792,16 +1129,13 @@ int32_t enqueue_loglikes(rbs_handle* h, const double* d_poses, const int* d_indi
                        !P.groups && h->n_bodies == 1 && !h->many_clusters && !h->group && h->peer_world <= 1 && !h->ipc_exported &&
                        (h->precision == RBS_PRECISION_F32 || h->one_body_kernel);
     if (timed && fused) h->ring_update[tslot] = false;   // (no copy kernel to time: timing_summary's copy_kernel_ms is 0)
-    if (h->lazy_frame && h->lazy_stream == s) {
+    if (const float* df = take_device_frame(h, s)) {   // a device frame pending on this stream rides on the rectangles kernel
         constexpr int ptb = 64 * rbs::kPrepPerBlock;
-        const int aux_blocks = (h->d_aux || h->lazy_frame != h->d_frame) ? (h->npx + ptb - 1) / ptb : 0;
+        const int aux_blocks = (h->d_aux || df != h->d_frame) ? (h->npx + ptb - 1) / ptb : 0;
         hipLaunchKernelGGL(rbs::rbs_frame_prep_kernel, dim3((unsigned)(aux_blocks + (n + rbs::kPrepPerBlock - 1) / rbs::kPrepPerBlock)), dim3(ptb), 0, s, P,
-                           d_rects, update ? 1 : 0, h->lazy_frame, h->d_aux, h->d_pbg,
-                           h->lazy_frame == h->d_frame ? (float*)nullptr : h->d_frame, aux_blocks);
-        h->lazy_frame = nullptr;
-        if (h->lazy_slot >= 0) { RBS_HIP(h, hipEventRecord(h->ev_used[h->lazy_slot], s)); h->lazy_slot = -1; }
+                           d_rects, update ? 1 : 0, df, h->d_aux, h->d_pbg, df == h->d_frame ? (float*)nullptr : h->d_frame, aux_blocks);
     } else {
-        if (int32_t rc = flush_lazy_frame(h, s)) return rc;
+        if (int32_t rc = flush_device_frame(h, s)) return rc;
         if (host_deltas) hipLaunchKernelGGL(rbs::rbs_prep_deltas_kernel, pgrid, dim3(64 * rbs::kPrepPerBlock), 0, s, P, d_rects, update ? 1 : 0);
         else hipLaunchKernelGGL(rbs::rbs_prep_kernel, pgrid, dim3(64 * rbs::kPrepPerBlock), 0, s, P, d_rects, update ? 1 : 0);
     }
@@ -850,7 +1184,7 @@ int32_t enqueue_loglikes(rbs_handle* h, const double* d_poses, const int* d_indi
     // a host frame that is read where it was uploaded: only now does the stream wait for the upload
     // (split launch: the geometry kernel needs no frame -- the wait sits between the two kernels, and a host frame
     // travels while the depth tiles are rasterized)
-    if (!split && h->frame_wait >= 0) RBS_HIP(h, hipStreamWaitEvent(s, h->ev_frame[h->frame_wait], 0));
+    if (!split) if (int32_t rc = wait_for_upload(h, s)) return rc;
     // the windowed copy kernel (one-wave blocks beside the persistent kernels, on the handle's second stream).  A call that stages a
     // borrowed frame between its two kernels launches it BEFORE the staging: it then runs beside the geometry kernel instead of
     // beside the likelihood kernel the caller is waiting for (plugin step +0.7 %, tests/cpp/host_bench --plugin)
@@ -902,10 +1236,10 @@ int32_t enqueue_loglikes(rbs_handle* h, const double* d_poses, const int* d_indi
                 h->poison_msg = h->err;
                 return rc;
             }
-            P.frame = h->cur_frame;
-            P.aux = h->cur_aux;
+            P.frame = obs_frame(h);
+            P.aux = obs_aux(h);
         }
-        if (h->frame_wait >= 0) RBS_HIP(h, hipStreamWaitEvent(s, h->ev_frame[h->frame_wait], 0));
+        if (int32_t rc = wait_for_upload(h, s)) return rc;
         if (h->exact) {
 #define RBS_X(U, S, T) hipLaunchKernelGGL((rbs::rbs_eval_kernel<U, S, T, true>), egrid, block, esm, s, P); break
             switch ((update ? 4 : 0) | (h->slab_px ? 2 : 0) | (P.bgp_src ? 1 : 0)) {
@@ -985,7 +1319,7 @@ int32_t enqueue_loglikes(rbs_handle* h, const double* d_poses, const int* d_indi
         if (timed) RBS_HIP(h, hipEventRecord(h->ev_raster_stop[tslot], s));
     }
     if (timed) { RBS_HIP(h, hipEventRecord(h->ev_stop[tslot], s)); h->timed_calls += 1; }
-    if (h->cur_slot >= 0 && s != h->stream) {
+    if (h->fr.cur >= 0 && s != h->stream) {
         // the staging image is released on the handle's stream: keep that stream behind its readers
         RBS_HIP(h, hipEventRecord(h->ev_reader, s));
         RBS_HIP(h, hipStreamWaitEvent(h->stream, h->ev_reader, 0));
@@ -1246,7 +1580,7 @@ int32_t slab_housekeeping(rbs_handle* h)
 // Make stream `s` (and the host, if sync) see the planes of the last updating call complete.
 int32_t drain(rbs_handle* h, bool host_sync)
 {
-    if (int32_t rc = flush_lazy_frame(h, h->stream)) return rc;
+    if (int32_t rc = flush_device_frame(h, h->stream)) return rc;
     if (h->join_pending >= 0) {
         RBS_HIP(h, hipStreamWaitEvent(h->stream, h->ev_join[h->join_pending], 0));
         if (host_sync) RBS_HIP(h, hipEventSynchronize(h->ev_join[h->join_pending]));
@@ -1278,7 +1612,6 @@ void release(rbs_handle* h)
     (void)hipFree(h->d_occ[1]);
     (void)hipFree(h->d_poses);
     (void)hipFree(h->d_indices);
-    (void)hipFree(h->d_out);
     (void)hipFree(h->d_rects[0]);
     (void)hipFree(h->d_rects[1]);
     (void)hipFree(h->d_groups[0]);
@@ -1345,210 +1678,6 @@ void release(rbs_handle* h)
     if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
-}
-
-// The staging image that served as the observation stops doing so (a new frame is coming): it may
-// be overwritten once everything launched so far has run.
-int32_t release_frame_slot(rbs_handle* h)
-{
-    if (h->cur_slot >= 0) {
-        RBS_HIP(h, hipEventRecord(h->ev_used[h->cur_slot], h->stream));
-        h->cur_slot = -1;
-    }
-    h->cur_frame = h->d_frame;
-    h->cur_aux = h->d_aux;
-    h->frame_wait = -1;
-    return RBS_OK;
-}
-
-// H2D of a frame staged in pinned host memory (`src`, normally h->h_frame) on the upload stream into
-// the device staging buffer of the current slot; the launch stream waits for it, and the ingest
-// kernel (copy into d_frame + per-frame model terms) rides on the next loglikes launch
-// (flush_lazy_frame otherwise).
-// `pageable`: the caller's own frame, still to be staged into `src` (= h->h_frame) -- staged and sent
-// in h->upload_chunks pieces, so that the copy engine carries one piece while the host copies the next
-// (a 640x480 frame: 41 us of memcpy + 29 us of transfer one after the other, ~20 us less interleaved).
-// dbot hands the image over as a vector of DOUBLES (R:source/dbot_ros/util/ros_interface.h:152-168): double -> float while
-// staging.  The scalar loop converts 2 values per instruction on a baseline x86-64 build; AVX2 (every host this library
-// meets; checked at run time) does 4 per instruction and halves the time of a 640x480 frame.
-#if defined(__x86_64__)
-__attribute__((target("avx2"))) static void convert_f64_f32_avx2(float* __restrict__ dst, const double* __restrict__ src, size_t n)
-{
-    size_t p = 0;
-    for (; p + 8 <= n; p += 8) {
-        const __m128 a = _mm256_cvtpd_ps(_mm256_loadu_pd(src + p)), b = _mm256_cvtpd_ps(_mm256_loadu_pd(src + p + 4));
-        _mm256_storeu_ps(dst + p, _mm256_set_m128(b, a));
-    }
-    for (; p < n; ++p) dst[p] = (float)src[p];
-}
-// AVX-512 hosts: 8 values per instruction and streaming stores (the staging image is read next by the copy engine, not by
-// this core: no line of it needs to be fetched to be overwritten) -- 42 us against 50 per 640x480 frame out of L3 (EPYC 9575F,
-// tools/dbg/convert_bench.cpp); the plugin path gains ~1 %
-__attribute__((target("avx512f"))) static void convert_f64_f32_avx512(float* __restrict__ dst, const double* __restrict__ src, size_t n)
-{
-    size_t p = 0;
-    for (; p + 16 <= n; p += 16) {
-        const __m256 a = _mm512_cvtpd_ps(_mm512_loadu_pd(src + p)), b = _mm512_cvtpd_ps(_mm512_loadu_pd(src + p + 8));
-        _mm512_stream_ps(dst + p, _mm512_castpd_ps(_mm512_insertf64x4(_mm512_castpd256_pd512(_mm256_castps_pd(a)), _mm256_castps_pd(b), 1)));
-    }
-    _mm_sfence();
-    for (; p < n; ++p) dst[p] = (float)src[p];
-}
-#endif
-static void convert_f64_f32(float* __restrict__ dst, const double* __restrict__ src, size_t n)
-{
-#if defined(__x86_64__)
-    static const bool avx512 = __builtin_cpu_supports("avx512f") && !std::getenv("RBS_NO_AVX512");
-    if (avx512 && (reinterpret_cast<uintptr_t>(dst) & 63) == 0) return convert_f64_f32_avx512(dst, src, n);
-    static const bool avx2 = __builtin_cpu_supports("avx2");
-    if (avx2) return convert_f64_f32_avx2(dst, src, n);
-#endif
-    for (size_t p = 0; p < n; ++p) dst[p] = (float)src[p];
-}
-
-int32_t upload_frame(rbs_handle* h, const float* src, const float* pageable = nullptr, const double* pageable_f64 = nullptr)
-{
-    const int k = h->frame_slot;
-    const size_t n = (size_t)h->npx;
-    h->prefetched_slot = -1;   // (a frame uploaded ahead of its turn that another frame overtakes is abandoned)
-    h->borrowed = nullptr;     // (... and so is a borrowed frame nobody evaluated)
-    h->borrowed_f32 = nullptr;
-    // (the two staging images alternate, so k is never the image that serves as the observation --
-    // should it be, its readers are recorded first: the wait below must not be on a stale event)
-    if (k == h->cur_slot)
-        if (int32_t rc = release_frame_slot(h)) return rc;
-    RBS_HIP(h, hipStreamWaitEvent(h->up_stream, h->ev_used[k], 0));   // d_fin[k]: read by the ingest kernel two frames ago
-    // A SMALL frame (the reference's default operating point is 80x60: 19 KB) is not worth a transfer: a copy-engine
-    // job costs ~11 us before it moves a byte and ~9 more until a kernel behind it starts.  The kernel that computes
-    // the frame's model terms reads it where the host staged it (this handle's pinned buffer, over PCIe) and leaves
-    // the observation in d_fin[k] as it goes (precision F32: that copy is all it does).
-    const bool pull = h->frame_pull_bytes > 0 && n * sizeof(float) <= h->frame_pull_bytes && h->h_frames_dev[k] && !h->frame_ingest &&
-                      (pageable || pageable_f64 || src == h->h_frames[k]);
-    if (pageable || pageable_f64) {
-        float* stage = h->h_frames[k];
-        // (a frame of doubles takes the host ~4x as long to stage as a frame of floats: twice the pieces)
-        const size_t want = (size_t)h->upload_chunks * (pageable_f64 && h->upload_chunks > 1 ? 2 : 1);
-        const int pieces = h->quiet ? (int)std::max<size_t>(1, std::min<size_t>(want, n / 16384)) : 1;
-        const size_t per = ((n + pieces - 1) / pieces + 1023) / 1024 * 1024;
-        for (size_t off = 0; off < n; off += per) {
-            const size_t len = std::min(per, n - off);
-            if (pageable) std::memcpy(stage + off, pageable + off, len * sizeof(float));
-            else convert_f64_f32(stage + off, pageable_f64 + off, len);   // dbot hands a vector of doubles
-            if (!pull) RBS_HIP(h, hipMemcpyAsync(h->d_fin[k] + off, stage + off, len * sizeof(float), hipMemcpyHostToDevice, h->up_stream));
-        }
-    } else if (!pull) {
-        RBS_HIP(h, hipMemcpyAsync(h->d_fin[k], src, n * sizeof(float), hipMemcpyHostToDevice, h->up_stream));
-    }
-    if (pull) {
-        hipLaunchKernelGGL(rbs::frame_aux_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->up_stream,
-                           h->h_frames_dev[k], h->d_aux ? h->d_aux_slot[k] : (double*)nullptr, h->d_pbg, h->npx, h->base.tw,
-                           h->base.ms, h->base.sf, h->base.lambda, h->d_fin[k]);
-        RBS_HIP(h, hipGetLastError());
-    } else if (h->d_aux && !h->frame_ingest) {
-        // precision F64: the frame's per-pixel model terms are computed right behind the copy, on the
-        // upload stream, into the slot's own table -- the launch stream does not wait for the frame
-        // until the raster kernel needs it, so a caller's transition and the rectangles kernel run
-        // while the frame is still travelling (a tracker frame: 35 us of 400)
-        hipLaunchKernelGGL(rbs::frame_aux_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->up_stream,
-                           h->d_fin[k], h->d_aux_slot[k], h->d_pbg, h->npx, h->base.tw, h->base.ms, h->base.sf,
-                           h->base.lambda, (float*)nullptr);
-        RBS_HIP(h, hipGetLastError());
-    }
-    RBS_HIP(h, hipEventRecord(h->ev_frame[k], h->up_stream));
-    if (int32_t rc = release_frame_slot(h)) return rc;
-    if (!h->frame_ingest) {   // (callers have flushed any pending frame)
-        // the staging image IS the observation (and, F64, its slot's table the model terms) until the
-        // next frame replaces it
-        h->cur_frame = h->d_fin[k];
-        h->cur_aux = h->d_aux ? h->d_aux_slot[k] : nullptr;
-        h->cur_slot = k;
-        h->frame_wait = k;
-        return RBS_OK;
-    }
-    RBS_HIP(h, hipStreamWaitEvent(h->stream, h->ev_frame[k], 0));
-    h->lazy_frame = h->d_fin[k];
-    h->lazy_stream = h->stream;
-    h->lazy_slot = k;
-    return RBS_OK;
-}
-
-// The pinned frame buffer the next host frame is staged in: the other one of the two, once the
-// upload that last used it has finished (two frames ago: in practice never a wait).
-int32_t next_frame_staging(rbs_handle* h)
-{
-    h->frame_slot ^= 1;
-    h->h_frame = h->h_frames[h->frame_slot];
-    RBS_HIP(h, hipEventSynchronize(h->ev_frame[h->frame_slot]));
-    return RBS_OK;
-}
-
-// rbs_set_observation_borrowed's frame becomes the observation now: staged (double -> float) into pinned memory and sent.
-int32_t stage_borrowed(rbs_handle* h)
-{
-    if (!h->borrowed && !h->borrowed_f32) return RBS_OK;
-    const double* d = h->borrowed;
-    const float* f = h->borrowed_f32;
-    h->borrowed = nullptr;
-    h->borrowed_f32 = nullptr;
-    if (int32_t rc = next_frame_staging(h)) return rc;
-    return d ? upload_frame(h, h->h_frame, nullptr, d) : upload_frame(h, h->h_frame, f);
-}
-
-// A borrowed frame is the caller's memory until the likelihood call behind it RETURNS -- however it returns.  A call that is
-// refused or fails before its kernels staged the frame must not leave the pointer behind for a later call to read: on the way
-// out the frame is copied after all (it becomes the observation, as rbs_set_observation would have made it), or dropped where
-// the handle takes no more work.
-struct BorrowedFrameGuard {
-    rbs_handle* h;
-    ~BorrowedFrameGuard()
-    {
-        if (!h->borrowed && !h->borrowed_f32) return;
-        if (h->poisoned || hipSetDevice(h->device) != hipSuccess) { h->borrowed = nullptr; h->borrowed_f32 = nullptr; return; }
-        const std::string keep = h->err;      // (the message of the failure that brought us here stays rbs_last_error's)
-        const int32_t rc = stage_borrowed(h);
-        h->borrowed = nullptr;
-        h->borrowed_f32 = nullptr;
-        if (rc == RBS_OK) h->err = keep;
-    }
-};
-
-// The NEXT frame, uploaded while the current one is still the observation (rbs_loglikes_prefetch: called between
-// the launch of a call's kernels and the wait for its results, so the host's staging copy and the transfer pass
-// behind the raster kernel): staged into the other pinned image, sent on the upload stream, its model terms
-// (precision F64) computed behind it -- everything upload_frame does except making it the observation.
-// What rbs_loglikes_prefetch needs, checked BEFORE the call's kernels are enqueued (ADVICE r4: a prefetch that failed
-// behind an updating call left the caller with a failed call whose planes had already flipped).
-int32_t prefetch_check(rbs_handle* h)
-{
-    if (h->frame_ingest)   // (frames ingested on the launch stream: RBS_FRAME_INGEST tooling mode)
-        return fail(h, RBS_ERR_UNSUPPORTED, "loglikes_prefetch: not with RBS_FRAME_INGEST");
-    if (h->prefetched_slot >= 0)
-        return fail(h, RBS_ERR_INVALID_ARGUMENT, "loglikes_prefetch: the frame uploaded ahead by the previous rbs_loglikes_prefetch has not been "
-                                                 "installed yet (rbs_set_observation_prefetched)");
-    if ((h->frame_slot ^ 1) == h->cur_slot)
-        return fail(h, RBS_ERR_INVALID_ARGUMENT, "loglikes_prefetch: the staging image the next frame would use is the current observation "
-                                                 "(the staging images did not alternate)");
-    return RBS_OK;
-}
-
-int32_t prefetch_frame(rbs_handle* h, const float* depth)
-{
-    if (int32_t rc = prefetch_check(h)) return rc;   // (before the staging image is switched: a refused call changes nothing)
-    if (int32_t rc = next_frame_staging(h)) return rc;
-    const int k = h->frame_slot;
-    const size_t n = (size_t)h->npx;
-    RBS_HIP(h, hipStreamWaitEvent(h->up_stream, h->ev_used[k], 0));   // d_fin[k]: its readers were enqueued two frames ago
-    std::memcpy(h->h_frames[k], depth, n * sizeof(float));
-    RBS_HIP(h, hipMemcpyAsync(h->d_fin[k], h->h_frames[k], n * sizeof(float), hipMemcpyHostToDevice, h->up_stream));
-    if (h->d_aux) {
-        hipLaunchKernelGGL(rbs::frame_aux_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->up_stream,
-                           h->d_fin[k], h->d_aux_slot[k], h->d_pbg, h->npx, h->base.tw, h->base.ms, h->base.sf,
-                           h->base.lambda, (float*)nullptr);
-        RBS_HIP(h, hipGetLastError());
-    }
-    RBS_HIP(h, hipEventRecord(h->ev_frame[k], h->up_stream));
-    h->prefetched_slot = k;
-    return RBS_OK;
 }
 
 int32_t create_impl(const rbs_config* cfg, rbs_handle* h)
@@ -1967,12 +2096,10 @@ int32_t create_impl(const rbs_config* cfg, rbs_handle* h)
     RBS_HIP(h, hipMemcpy(h->d_soup, soup.data(), soup.size() * sizeof(double), hipMemcpyHostToDevice));
     B.soup = h->d_soup;
     RBS_HIP(h, hipMalloc(&h->d_frame, plane));
-    h->cur_frame = h->d_frame;
     if (h->precision == RBS_PRECISION_F64) {   // F32 derives the per-pixel terms from the observation on the fly
         RBS_HIP(h, hipMalloc(&h->d_aux, sizeof(double) * rbs::AUX_PLANES * (size_t)h->npx));
         RBS_HIP(h, hipMalloc(&h->d_aux_slot[0], sizeof(double) * rbs::AUX_PLANES * (size_t)h->npx));
         RBS_HIP(h, hipMalloc(&h->d_aux_slot[1], sizeof(double) * rbs::AUX_PLANES * (size_t)h->npx));
-        h->cur_aux = h->d_aux;
         RBS_HIP(h, hipMalloc(&h->d_pbg, plane));
     }
     RBS_HIP(h, hipMalloc(&h->d_render, plane));
@@ -2041,7 +2168,6 @@ int32_t create_impl(const rbs_config* cfg, rbs_handle* h)
     }
     RBS_HIP(h, hipMalloc(&h->d_poses, sizeof(double) * 12 * h->n_bodies * (size_t)h->max_particles));
     RBS_HIP(h, hipMalloc(&h->d_indices, sizeof(int) * (size_t)h->max_particles));
-    RBS_HIP(h, hipMalloc(&h->d_out, sizeof(double) * (size_t)h->max_particles));
     RBS_HIP(h, hipMalloc(&h->d_rects[0], sizeof(int) * 4 * (size_t)h->max_particles));
     RBS_HIP(h, hipMalloc(&h->d_rects[1], sizeof(int) * 4 * (size_t)h->max_particles));
     if (h->n_bodies > 1 && !(std::getenv("RBS_NO_GROUPS") && std::atoi(std::getenv("RBS_NO_GROUPS")))) {
@@ -2100,9 +2226,7 @@ int32_t create_impl(const rbs_config* cfg, rbs_handle* h)
         RBS_HIP(h, hipMemcpy(h->d_vtx, vtx.data(), sizeof(float) * vtx.size(), hipMemcpyHostToDevice));
         B.vtx = reinterpret_cast<const rbs::floatx4*>(h->d_vtx);
     }
-    if (const char* e = std::getenv("RBS_FRAME_INGEST")) h->frame_ingest = std::atoi(e) != 0;
     if (const char* e = std::getenv("RBS_FRAME_PULL_BYTES")) h->frame_pull_bytes = (size_t)std::max(0L, std::atol(e));
-    if (const char* e = std::getenv("RBS_HOST_STAGED_COPIES")) h->host_copies = std::atoi(e) != 0;
     RBS_HIP(h, hipStreamCreateWithFlags(&h->up_stream, hipStreamNonBlocking));
     for (int k = 0; k < 2; ++k) {
         RBS_HIP(h, hipHostMalloc(&h->h_frames[k], plane, hipHostMallocPortable));   // (every device of a group uploads from shard 0's)
@@ -2112,7 +2236,6 @@ int32_t create_impl(const rbs_config* cfg, rbs_handle* h)
         if (k == 0) RBS_HIP(h, hipEventCreateWithFlags(&h->ev_reader, hipEventDisableTiming));
         RBS_HIP(h, hipMalloc(&h->d_fin[k], plane));
     }
-    h->h_frame = h->h_frames[0];
     {
         const size_t pose_bytes = sizeof(double) * 12 * h->n_bodies * (size_t)h->max_particles;
         h->in_idx_off = pose_bytes;
@@ -2171,8 +2294,8 @@ int32_t create_impl(const rbs_config* cfg, rbs_handle* h)
     RBS_HIP(h, hipEventRecord(h->ev_fork, h->copy_stream));
     RBS_HIP(h, hipStreamSynchronize(h->copy_stream));
     // no observation yet: every pixel "no reading"
-    for (int p = 0; p < h->npx; ++p) h->h_frame[p] = NAN;
-    if (int32_t rc = upload_frame(h, h->h_frame)) return rc;
+    for (int p = 0; p < h->npx; ++p) staging(h)[p] = NAN;
+    if (int32_t rc = upload_frame(h, staging(h))) return rc;
     return rbs_reset(h);
 }
 
@@ -2204,12 +2327,6 @@ int32_t poison(rbs_handle* h, int32_t rc)
     h->err = why;
     return rc;
 }
-#define RBS_REFUSE_POISONED(h)                                                                \
-    do {                                                                                      \
-        if ((h)->poisoned)                                                                    \
-            return fail(h, RBS_ERR_HIP, "the handle is in an undefined state after a failed call (" + (h)->poison_msg + \
-                                            "): call rbs_reset / rbs_tracker_initialize");    \
-    } while (0)
 
 // Every shard orders its next call after EVERY shard's previous one: a call reads parents from
 // the other shards' current planes (complete only when their previous updating call is) and
@@ -2467,7 +2584,7 @@ void release_group(rbs_handle* g)
 // device copy of the poses the raster kernel reads) and the raster kernel stores the
 // log-likelihoods straight into the pinned result buffer.  A separate H2D copy of 200 KB queued
 // behind the frame's upload on the same engine, and each copy <-> kernel hand-over costs ~10 us:
-// together 30 us of a 300 us step.  RBS_HOST_STAGED_COPIES=1 restores the copies.
+// together 30 us of a 300 us step.
 // rbs_loglikes_deltas: state deltas + default poses instead of absolute poses (packed on the way into pinned memory,
 // composed on the device by the rectangles kernel, rbs_prep_deltas_kernel).
 struct DeltaArgs { const double* deltas; const double* deflt; int stride; };
@@ -2477,7 +2594,6 @@ struct DeltaArgs { const double* deltas; const double* deflt; int stride; };
 
 int32_t host_call(rbs_handle* h, const double* poses, const int32_t* indices, int n, bool update, const DeltaArgs* da = nullptr)
 {
-    const bool copies = h->host_copies && !da;
     const size_t pose_bytes = sizeof(double) * 12 * h->n_bodies * (size_t)n;
     // slabs: the overflow flag as it stands BEFORE this call -- set, it belongs to an asynchronous call
     // that has not been reported yet
@@ -2494,7 +2610,7 @@ int32_t host_call(rbs_handle* h, const double* poses, const int32_t* indices, in
         for (int b = 0; b < B; ++b) std::memcpy(st + 6 * nb + 6 * b, da->deflt + (size_t)da->stride * b, sizeof(double) * 6);
         std::memcpy(h->h_in + h->in_idx_off, indices, sizeof(int) * (size_t)n);
         // (the rectangles kernel composes: the wave that owns a particle reads its 48 bytes per body from here)
-        if (h->lazy_frame) if (int32_t rc = flush_lazy_frame(h, h->stream)) return rc;   // (a pending device frame: its ingest has no deltas variant)
+        if (int32_t rc = flush_device_frame(h, h->stream)) return rc;   // (a pending device frame: its ingest has no deltas variant)
         if (int32_t rc = enqueue_loglikes(h, reinterpret_cast<const double*>(h->d_in),
                                           reinterpret_cast<const int*>(h->h_in_dev + h->in_idx_off), n, update,
                                           reinterpret_cast<double*>(h->h_out_dev), h->stream, nullptr,
@@ -2506,25 +2622,11 @@ int32_t host_call(rbs_handle* h, const double* poses, const int32_t* indices, in
     }
     std::memcpy(h->h_in, poses, pose_bytes);
     std::memcpy(h->h_in + h->in_idx_off, indices, sizeof(int) * (size_t)n);
-    if (copies) {
-        if (pose_bytes == h->in_idx_off) {
-            RBS_HIP(h, hipMemcpyAsync(h->d_in, h->h_in, pose_bytes + sizeof(int) * (size_t)n, hipMemcpyHostToDevice, h->stream));
-        } else {
-            RBS_HIP(h, hipMemcpyAsync(h->d_in, h->h_in, pose_bytes, hipMemcpyHostToDevice, h->stream));
-            RBS_HIP(h, hipMemcpyAsync(h->d_in + h->in_idx_off, h->h_in + h->in_idx_off, sizeof(int) * (size_t)n,
-                                      hipMemcpyHostToDevice, h->stream));
-        }
-        if (int32_t rc = enqueue_loglikes(h, reinterpret_cast<const double*>(h->d_in),
-                                          reinterpret_cast<const int*>(h->d_in + h->in_idx_off), n, update, h->d_out, h->stream))
-            return rc;
-        RBS_HIP(h, hipMemcpyAsync(h->h_out, h->d_out, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
-    } else {
-        if (int32_t rc = enqueue_loglikes(h, reinterpret_cast<const double*>(h->d_in),
-                                          reinterpret_cast<const int*>(h->h_in_dev + h->in_idx_off), n, update,
-                                          reinterpret_cast<double*>(h->h_out_dev), h->stream,
-                                          reinterpret_cast<const double*>(h->h_in_dev)))
-            return rc;
-    }
+    if (int32_t rc = enqueue_loglikes(h, reinterpret_cast<const double*>(h->d_in),
+                                      reinterpret_cast<const int*>(h->h_in_dev + h->in_idx_off), n, update,
+                                      reinterpret_cast<double*>(h->h_out_dev), h->stream,
+                                      reinterpret_cast<const double*>(h->h_in_dev)))
+        return rc;
     if (h->slab_px) RBS_HIP(h, hipMemcpyAsync(h->h_err, h->d_err, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     RBS_HIP(h, hipEventRecord(h->ev_out, h->stream));
     return RBS_OK;
@@ -2651,12 +2753,9 @@ int32_t group_set_observation_device(rbs_handle* g, const float* d_depth, hipStr
     for (size_t k = 0; k < g->shards.size(); ++k) {
         rbs_handle* h = g->shards[k];
         if (hipSetDevice(h->device) != hipSuccess) return poison(g, fail(g, RBS_ERR_HIP, fmt("hipSetDevice(%d) failed", h->device)));
-        if (int32_t rc = flush_lazy_frame(h, h->stream)) return k == 0 ? gfail(g, h, rc) : poison(g, gfail(g, h, rc));
-        if (int32_t rc = release_frame_slot(h)) return k == 0 ? gfail(g, h, rc) : poison(g, gfail(g, h, rc));
+        if (int32_t rc = flush_device_frame(h, h->stream)) return k == 0 ? gfail(g, h, rc) : poison(g, gfail(g, h, rc));
+        if (int32_t rc = hand_over_device(h, d_depth, h->stream)) return k == 0 ? gfail(g, h, rc) : poison(g, gfail(g, h, rc));
         if (hipStreamWaitEvent(h->stream, s0->ev_reader, 0) != hipSuccess) return poison(g, fail(g, RBS_ERR_HIP, "hipStreamWaitEvent failed"));
-        h->lazy_frame = d_depth;
-        h->lazy_stream = h->stream;
-        h->pending_frames += 1;
     }
     return RBS_OK;
 }
@@ -2814,7 +2913,7 @@ int32_t rbs_reset(rbs_handle* h)
             RBS_HIP(h, hipEventRecord(sh_->ev_done, sh_->stream));
         }
         h->poisoned = false;
-        h->frame_acquired = false;
+        frame_abandon(h);
         h->stp = false;
         h->stp_leave_pending = false;
         h->stp_now = rbs_handle::StpNow();
@@ -2829,10 +2928,7 @@ int32_t rbs_reset(rbs_handle* h)
     // in use: both pairs start from zero again)
     RBS_HIP(h, hipMemsetAsync(h->d_ctr, 0, 8 * sizeof(int), h->stream));
     h->poisoned = false;
-    h->frame_acquired = false;
-    h->prefetched_slot = -1;   // (a frame uploaded ahead belongs to the session that ended)
-    h->borrowed = nullptr;
-    h->borrowed_f32 = nullptr;
+    frame_abandon(h);
     h->stp = false;            // (every plane is all background again: the scalar says it all)
     h->stp_request = -1;
     h->stp_last_rebase = -1000000;
@@ -2868,75 +2964,47 @@ int32_t rbs_reset(rbs_handle* h)
     return RBS_OK;
 }
 
+// rbs_set_observation / _f32 (`what`: the entry point's name in its messages): the caller's host frame, copied now.
+static int32_t set_host_frame(rbs_handle* h, const float* f32, const double* f64, size_t n, const char* what)
+{
+    if (!h) return RBS_ERR_INVALID_ARGUMENT;
+    if (int32_t rc = frame_begin(h)) return rc;
+    RBS_GROUP_ALL_MUT(h, set_host_frame(sh_, f32, f64, n, what));
+    if ((!f32 && !f64) || n != (size_t)h->npx)
+        return fail(h, RBS_ERR_INVALID_ARGUMENT, fmt("%s: expected %d pixels, got %zu", what, h->npx, n));
+    if (int32_t rc = frame_ready(h, h->stream)) return rc;
+    return hand_over_host(h, f32, f64);
+}
+
+// rbs_set_observation_borrowed / _f32: handles that cannot stage between two kernels (several devices; float32 likelihood;
+// whole planes) copy at once.
+static int32_t set_borrowed_frame(rbs_handle* h, const float* f32, const double* f64, size_t n, const char* what)
+{
+    if (!h) return RBS_ERR_INVALID_ARGUMENT;
+    if (!can_borrow(h)) return set_host_frame(h, f32, f64, n, f64 ? "set_observation" : "set_observation_f32");
+    if (int32_t rc = frame_begin(h)) return rc;
+    if ((!f32 && !f64) || n != (size_t)h->npx)
+        return fail(h, RBS_ERR_INVALID_ARGUMENT, fmt("%s: expected %d pixels, got %zu", what, h->npx, n));
+    if (int32_t rc = frame_ready(h, h->stream)) return rc;
+    hand_over_borrowed(h, f32, f64);
+    return RBS_OK;
+}
+
 int32_t rbs_set_observation(rbs_handle* h, const double* depth, size_t n)
 {
-    if (!h) return RBS_ERR_INVALID_ARGUMENT;
-    RBS_REFUSE_POISONED(h);
-    h->frame_acquired = false;   // (an acquired buffer that was never committed is abandoned)
-    RBS_GROUP_ALL_MUT(h, rbs_set_observation(sh_, depth, n));
-    if (!depth || n != (size_t)h->npx)
-        return fail(h, RBS_ERR_INVALID_ARGUMENT,
-                    fmt("set_observation: expected %d pixels, got %zu", h->npx, n));
-    RBS_HIP(h, hipSetDevice(h->device));
-    if (int32_t rc = flush_lazy_frame(h, h->stream)) return rc;
-    if (int32_t rc = next_frame_staging(h)) return rc;
-    if (int32_t rc = upload_frame(h, h->h_frame, nullptr, depth)) return rc;   // (converted and sent piece by piece)
-    h->pending_frames += 1;
-    return RBS_OK;
+    return set_host_frame(h, nullptr, depth, n, "set_observation");   // (converted and sent piece by piece)
 }
-
-int32_t rbs_set_observation_borrowed(rbs_handle* h, const double* depth, size_t n)
-{
-    if (!h) return RBS_ERR_INVALID_ARGUMENT;
-    // handles that cannot stage between two kernels (several devices; float32 likelihood; whole planes) copy at once
-    if (!h->shards.empty() || h->group || h->precision != RBS_PRECISION_F64 || !h->windowed || h->frame_ingest)
-        return rbs_set_observation(h, depth, n);
-    RBS_REFUSE_POISONED(h);
-    h->frame_acquired = false;
-    if (!depth || n != (size_t)h->npx)
-        return fail(h, RBS_ERR_INVALID_ARGUMENT, fmt("set_observation_borrowed: expected %d pixels, got %zu", h->npx, n));
-    RBS_HIP(h, hipSetDevice(h->device));
-    if (int32_t rc = flush_lazy_frame(h, h->stream)) return rc;
-    h->prefetched_slot = -1;
-    h->borrowed_f32 = nullptr;
-    h->borrowed = depth;          // (a borrowed frame nobody evaluated is simply replaced)
-    h->pending_frames += 1;
-    return RBS_OK;
-}
-
-int32_t rbs_set_observation_borrowed_f32(rbs_handle* h, const float* depth, size_t n)
-{
-    if (!h) return RBS_ERR_INVALID_ARGUMENT;
-    if (!h->shards.empty() || h->group || h->precision != RBS_PRECISION_F64 || !h->windowed || h->frame_ingest)
-        return rbs_set_observation_f32(h, depth, n);
-    RBS_REFUSE_POISONED(h);
-    h->frame_acquired = false;
-    if (!depth || n != (size_t)h->npx)
-        return fail(h, RBS_ERR_INVALID_ARGUMENT, fmt("set_observation_borrowed_f32: expected %d pixels, got %zu", h->npx, n));
-    RBS_HIP(h, hipSetDevice(h->device));
-    if (int32_t rc = flush_lazy_frame(h, h->stream)) return rc;
-    h->prefetched_slot = -1;
-    h->borrowed = nullptr;
-    h->borrowed_f32 = depth;
-    h->pending_frames += 1;
-    return RBS_OK;
-}
-
 int32_t rbs_set_observation_f32(rbs_handle* h, const float* depth, size_t n)
 {
-    if (!h) return RBS_ERR_INVALID_ARGUMENT;
-    RBS_REFUSE_POISONED(h);
-    h->frame_acquired = false;   // (an acquired buffer that was never committed is abandoned)
-    RBS_GROUP_ALL_MUT(h, rbs_set_observation_f32(sh_, depth, n));
-    if (!depth || n != (size_t)h->npx)
-        return fail(h, RBS_ERR_INVALID_ARGUMENT,
-                    fmt("set_observation_f32: expected %d pixels, got %zu", h->npx, n));
-    RBS_HIP(h, hipSetDevice(h->device));
-    if (int32_t rc = flush_lazy_frame(h, h->stream)) return rc;
-    if (int32_t rc = next_frame_staging(h)) return rc;
-    if (int32_t rc = upload_frame(h, h->h_frame, depth)) return rc;   // (staged and sent piece by piece)
-    h->pending_frames += 1;
-    return RBS_OK;
+    return set_host_frame(h, depth, nullptr, n, "set_observation_f32");
+}
+int32_t rbs_set_observation_borrowed(rbs_handle* h, const double* depth, size_t n)
+{
+    return set_borrowed_frame(h, nullptr, depth, n, "set_observation_borrowed");
+}
+int32_t rbs_set_observation_borrowed_f32(rbs_handle* h, const float* depth, size_t n)
+{
+    return set_borrowed_frame(h, depth, nullptr, n, "set_observation_borrowed_f32");
 }
 
 int32_t rbs_acquire_frame_buffer(rbs_handle* h, float** buf)
@@ -2944,28 +3012,9 @@ int32_t rbs_acquire_frame_buffer(rbs_handle* h, float** buf)
     if (!h) return RBS_ERR_INVALID_ARGUMENT;
     if (!buf) return fail(h, RBS_ERR_INVALID_ARGUMENT, "acquire_frame_buffer: null pointer");
     RBS_REFUSE_POISONED(h);
-    if (h->frame_acquired)
+    if (h->fr.acquired)
         return fail(h, RBS_ERR_INVALID_ARGUMENT, "acquire_frame_buffer: the buffer handed out last has not been committed (rbs_commit_frame_buffer)");
-    if (!h->shards.empty()) {
-        // one staging buffer (shard 0's) feeds every device: it is free once every shard's upload
-        // of the frame before last has finished
-        rbs_handle* s0 = h->shards[0];
-        s0->frame_slot ^= 1;
-        s0->h_frame = s0->h_frames[s0->frame_slot];
-        for (rbs_handle* sh : h->shards) {
-            RBS_HIP(h, hipSetDevice(sh->device));
-            sh->frame_slot = s0->frame_slot;
-            RBS_HIP(h, hipEventSynchronize(sh->ev_frame[sh->frame_slot]));
-        }
-        *buf = s0->h_frame;
-        h->frame_acquired = true;
-        return RBS_OK;
-    }
-    RBS_HIP(h, hipSetDevice(h->device));
-    if (int32_t rc = next_frame_staging(h)) return rc;
-    *buf = h->h_frame;
-    h->frame_acquired = true;
-    return RBS_OK;
+    return acquire_staging(h, buf);
 }
 
 int32_t rbs_commit_frame_buffer(rbs_handle* h)
@@ -2975,76 +3024,48 @@ int32_t rbs_commit_frame_buffer(rbs_handle* h)
     // a commit uploads the buffer the matching acquire handed out: without one (or after another
     // rbs_set_observation* call took the acquire's place) there is nothing defined to upload, and the
     // upload would land in the image the kernels in flight are reading
-    if (!h->frame_acquired)
+    if (!h->fr.acquired)
         return fail(h, RBS_ERR_INVALID_ARGUMENT, "commit_frame_buffer: no buffer acquired (rbs_acquire_frame_buffer comes first, once per frame)");
-    h->frame_acquired = false;
+    if (int32_t rc = frame_begin(h)) return rc;
     if (!h->shards.empty()) {
-        const float* src = h->shards[0]->h_frame;
+        const float* src = staging(h->shards[0]);
         for (rbs_handle* sh : h->shards) {
-            if (hipSetDevice(sh->device) != hipSuccess) return poison(h, fail(h, RBS_ERR_HIP, fmt("hipSetDevice(%d) failed", sh->device)));
-            if (int32_t rc = flush_lazy_frame(sh, sh->stream)) return poison(h, gfail(h, sh, rc));
-            if (int32_t rc = upload_frame(sh, src)) return poison(h, gfail(h, sh, rc));
-            sh->pending_frames += 1;
+            if (int32_t rc = frame_ready(sh, sh->stream)) return poison(h, gfail(h, sh, rc));
+            if (int32_t rc = hand_over_pinned(sh, src)) return poison(h, gfail(h, sh, rc));
         }
         return RBS_OK;
     }
-    RBS_HIP(h, hipSetDevice(h->device));
-    if (int32_t rc = flush_lazy_frame(h, h->stream)) return rc;
-    if (int32_t rc = upload_frame(h, h->h_frame)) return rc;
-    h->pending_frames += 1;
-    return RBS_OK;
+    if (int32_t rc = frame_ready(h, h->stream)) return rc;
+    return hand_over_pinned(h, staging(h));
 }
 
 int32_t rbs_set_observation_native_f32(rbs_handle* h, const float* native, int32_t width,
                                        int32_t height, int32_t f)
 {
     if (!h) return RBS_ERR_INVALID_ARGUMENT;
-    RBS_REFUSE_POISONED(h);
-    h->frame_acquired = false;
+    if (int32_t rc = frame_begin(h)) return rc;
     RBS_GROUP_ALL_MUT(h, rbs_set_observation_native_f32(sh_, native, width, height, f));
     if (!native || f <= 0 || width <= 0 || height <= 0 || height / f != h->rows || width / f != h->cols)
         return fail(h, RBS_ERR_INVALID_ARGUMENT,
                     fmt("set_observation_native: %dx%d / %d does not give the evaluated %dx%d", width,
                         height, f, h->cols, h->rows));
     if (f == 1) return rbs_set_observation_f32(h, native, (size_t)h->npx);
-    RBS_HIP(h, hipSetDevice(h->device));
-    if (int32_t rc = flush_lazy_frame(h, h->stream)) return rc;
-    if (int32_t rc = next_frame_staging(h)) return rc;
-    // The reference's rule (R:source/dbot_ros/util/ros_interface.h:152-168): evaluated(r, c) =
-    // native(r f, c f) -- applied while the frame is staged, so that only the rows*cols values the
-    // sensor evaluates are copied and sent (1/f^2 of the driver's frame: 19 KB of 1.2 MB at the
-    // reference's default factor 8) and the frame then travels like any other host frame.
-    for (int r = 0; r < h->rows; ++r) {
-        const float* src = native + (size_t)r * f * width;
-        float* dst = h->h_frame + (size_t)r * h->cols;
-        for (int c = 0; c < h->cols; ++c) dst[c] = src[(size_t)c * f];
-    }
-    if (int32_t rc = upload_frame(h, h->h_frame)) return rc;
-    h->pending_frames += 1;
-    return RBS_OK;
+    if (int32_t rc = frame_ready(h, h->stream)) return rc;
+    return hand_over_native(h, native, width, f);
 }
 
 int32_t rbs_set_observation_device(rbs_handle* h, const float* d_depth, void* stream)
 {
     if (!h) return RBS_ERR_INVALID_ARGUMENT;
-    RBS_REFUSE_POISONED(h);
-    h->frame_acquired = false;
+    if (int32_t rc = frame_begin(h)) return rc;
     if (!d_depth) return fail(h, RBS_ERR_INVALID_ARGUMENT, "set_observation_device: null pointer");
     if (!h->shards.empty()) return group_set_observation_device(h, d_depth, static_cast<hipStream_t>(stream));
-    RBS_HIP(h, hipSetDevice(h->device));
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
     // the ingest kernel (copy into the handle's buffer + per-pixel model terms) is not launched
     // here: it shares a launch with the next rbs_loglikes* call's rectangles kernel when that
     // call comes on the same stream, and is launched on `s` by whatever needs the frame otherwise
-    if (int32_t rc = flush_lazy_frame(h, s)) return rc;   // an earlier frame nobody evaluated
-    if (int32_t rc = release_frame_slot(h)) return rc;
-    h->prefetched_slot = -1;   // (a frame uploaded ahead of its turn that another frame overtakes is abandoned: ADVICE r4)
-    h->borrowed = nullptr;
-    h->borrowed_f32 = nullptr;
-    h->lazy_frame = d_depth;
-    h->lazy_stream = s;
-    h->pending_frames += 1;
-    return RBS_OK;
+    if (int32_t rc = frame_ready(h, s)) return rc;   // (an earlier frame nobody evaluated)
+    return hand_over_device(h, d_depth, s);
 }
 
 int32_t rbs_get_observation(rbs_handle* h, float* out)
@@ -3053,11 +3074,9 @@ int32_t rbs_get_observation(rbs_handle* h, float* out)
     RBS_GROUP_FIRST(h, rbs_get_observation(sh_, out));
     if (!out) return fail(h, RBS_ERR_INVALID_ARGUMENT, "get_observation: null pointer");
     RBS_HIP(h, hipSetDevice(h->device));
-    if (int32_t rc = stage_borrowed(h)) return rc;
-    if (int32_t rc = flush_lazy_frame(h, h->stream)) return rc;
+    if (int32_t rc = make_current(h, h->stream)) return rc;
     RBS_HIP(h, hipStreamSynchronize(h->stream));
-    if (h->frame_wait >= 0) RBS_HIP(h, hipEventSynchronize(h->ev_frame[h->frame_wait]));
-    RBS_HIP(h, hipMemcpy(out, h->cur_frame, sizeof(float) * h->npx, hipMemcpyDeviceToHost));
+    RBS_HIP(h, hipMemcpy(out, obs_frame(h), sizeof(float) * h->npx, hipMemcpyDeviceToHost));
     return RBS_OK;
 }
 
@@ -3114,20 +3133,11 @@ int32_t rbs_set_observation_prefetched(rbs_handle* h)
 {
     if (!h) return RBS_ERR_INVALID_ARGUMENT;
     RBS_REFUSE_POISONED(h);
-    if (h->prefetched_slot < 0)
+    if (h->fr.next.kind != NextFrame::AHEAD)
         return fail(h, RBS_ERR_INVALID_ARGUMENT, "set_observation_prefetched: no frame was uploaded ahead (rbs_loglikes_prefetch), or another frame has been set since");
-    RBS_HIP(h, hipSetDevice(h->device));
-    h->frame_acquired = false;
-    if (int32_t rc = flush_lazy_frame(h, h->stream)) return rc;
-    const int k = h->prefetched_slot;
-    h->prefetched_slot = -1;
-    if (int32_t rc = release_frame_slot(h)) return rc;   // the readers of the frame it replaces are on the launch stream by now
-    h->cur_frame = h->d_fin[k];
-    h->cur_aux = h->d_aux ? h->d_aux_slot[k] : nullptr;
-    h->cur_slot = k;
-    h->frame_wait = k;
-    h->pending_frames += 1;
-    return RBS_OK;
+    if (int32_t rc = frame_begin(h)) return rc;
+    if (int32_t rc = frame_ready(h, h->stream)) return rc;
+    return hand_over_ahead(h);
 }
 
 static int32_t loglikes_impl(rbs_handle* h, const double* poses, int32_t* indices, int32_t n, int32_t update, double* out_loglik,
@@ -4102,7 +4112,7 @@ int32_t rbs_tracker_initialize(rbs_tracker* t, const double* default_state)
             RBT_HIP(t, hipEventRecord(sh->ev_done, sh->stream));
         }
         t->s->poisoned = false;
-        t->s->frame_acquired = false;
+        frame_abandon(t->s);
         return RBS_OK;
     }
     rbt::TrackerDev& T = t->T;
@@ -4340,14 +4350,10 @@ static int32_t tracker_submit_impl(rbs_tracker* t, const float* frame, const dou
             // kTrackerSplitMax evaluations the one-kernel launch's shorter kernel time wins (RBS_TRACKER_SPLIT_MAX, 0: never).
             const int split_max = h->tracker_split_max;
             const bool idle = t->submitted == t->collected;   // (a frame already in flight -- look-ahead -- hides the journey by itself, and the one-kernel launch is the shorter)
-            if (idle && T.n * T.parts <= split_max && h->precision == RBS_PRECISION_F64 && h->windowed && !h->frame_ingest && !h->group) {
-                RBS_REFUSE_POISONED(h);
-                h->frame_acquired = false;
-                if (int32_t rc = flush_lazy_frame(h, h->stream)) return rc;
-                h->prefetched_slot = -1;
-                h->borrowed = frame64;          // (doubles, as dbot hands images over: converted while they are staged)
-                h->borrowed_f32 = frame64 ? nullptr : frame;
-                h->pending_frames += 1;
+            if (idle && T.n * T.parts <= split_max && can_borrow(h)) {
+                if (int32_t rc = frame_begin(h)) return rc;
+                if (int32_t rc = frame_ready(h, h->stream)) return rc;
+                hand_over_borrowed(h, frame, frame64);   // (doubles, as dbot hands images over: converted while they are staged)
             } else if (int32_t rc = frame64 ? rbs_set_observation(h, frame64, (size_t)h->npx) : rbs_set_observation_f32(h, frame, (size_t)h->npx)) return rc;
         }
         if (int32_t rc = enqueue_loglikes(h, T.poses, T.idx, T.n, last, T.ll_new, s)) return rc;

@@ -615,14 +615,14 @@ const char* check_params(const rbs_gauss_params* p)
     return nullptr;
 }
 
-// The moments kernel's arguments (the frame: h->cur_frame).
+// The moments kernel's arguments (the frame: the sensor's observation, made current).
 rbs::GaussArgs moments_args(rbs_gauss* g)
 {
     rbs_handle* h = g->s;
     rbs::GaussArgs G{};
     G.planes = g->d_planes;
     G.rects = g->d_rects;
-    G.frame = h->cur_frame;
+    G.frame = obs_frame(h);
     G.cols = h->cols;
     G.npx = h->npx;
     G.wm0 = g->wm0; G.wc0 = g->wc0; G.w = g->w;
@@ -651,9 +651,7 @@ int32_t track_impl(rbs_gauss* g, const float* f32, const double* f64, double* ou
     const size_t npx = (size_t)h->npx;
     if (f32) { if (int32_t rc = rbs_set_observation_f32(h, f32, npx)) return rc; }
     else if (f64) { if (int32_t rc = rbs_set_observation(h, f64, npx)) return rc; }
-    if (int32_t rc = stage_borrowed(h)) return rc;
-    if (int32_t rc = flush_lazy_frame(h, h->stream)) return rc;
-    if (h->frame_wait >= 0) RBS_HIP(h, hipStreamWaitEvent(h->stream, h->ev_frame[h->frame_wait], 0));
+    if (int32_t rc = make_current(h, h->stream)) return rc;
     h->quiet = false;
 
     const int B = g->B, D = g->D, NP = g->NP, nd = g->nd;
@@ -834,15 +832,10 @@ int32_t submit_impl(rbs_gauss* g, const float* f32, const double* f64, bool* enq
     const bool behind = g->submitted > g->collected;
     // a frame staged on a caller's stream (rbs_set_observation_device) is copied into the handle's buffer there: after the
     // frame in flight has read that buffer
-    if (behind && h->lazy_frame && h->lazy_stream != h->stream) {
-        RBS_HIP(h, hipEventRecord(h->ev_reader, h->stream));
-        RBS_HIP(h, hipStreamWaitEvent(h->lazy_stream, h->ev_reader, 0));
-    }
+    if (behind) if (int32_t rc = device_frame_after_readers(h)) return rc;
     if (f32) { if (int32_t rc = rbs_set_observation_f32(h, f32, npx)) return rc; }
     else if (f64) { if (int32_t rc = rbs_set_observation(h, f64, npx)) return rc; }
-    if (int32_t rc = stage_borrowed(h)) return rc;
-    if (int32_t rc = flush_lazy_frame(h, h->stream)) return rc;
-    if (h->frame_wait >= 0) RBS_HIP(h, hipStreamWaitEvent(h->stream, h->ev_frame[h->frame_wait], 0));
+    if (int32_t rc = make_current(h, h->stream)) return rc;
     h->quiet = false;
     *enqueued = true;
     hipStream_t s = h->stream;
@@ -878,9 +871,8 @@ int32_t submit_impl(rbs_gauss* g, const float* f32, const double* f64, bool* enq
     default: hipLaunchKernelGGL(rbs::rbs_gauss_moments_kernel<3>, dim3(rbs::kGaussBlocks), dim3(256), 0, s, A); break;
     }
     RBS_HIP(h, hipGetLastError());
-    // the frame's staging image (h->cur_frame, on a windowed F64 handle d_fin[cur_slot] itself) has been read: frame N + 2's
-    // upload into it waits for this, not for the frame's result
-    if (h->cur_slot >= 0) RBS_HIP(h, hipEventRecord(h->ev_used[h->cur_slot], s));
+    // the frame's staging image has been read: frame N + 2's upload into it waits for this, not for the frame's result
+    if (int32_t rc = frame_read_done(h, s)) return rc;
     RBS_HIP(h, hipEventRecord(g->ev[2], s));
     hipLaunchKernelGGL(rbs::rbs_gauss_reduce_update_kernel, dim3(1), dim3(256), 0, s, G);
     RBS_HIP(h, hipGetLastError());

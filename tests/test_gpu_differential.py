@@ -166,51 +166,59 @@ def test_device_tracker_across_configurations(gpu_lib, meshes, n):
 
 @pytest.mark.parametrize("precision,layout,ids", [("f32", "window", None), ("f32", "dense", None), ("f64", "window", None),
                                                   ("f32", "window", [0, 0])])
-def test_host_call_routes_agree_bit_for_bit(gpu_lib, monkeypatch, precision, layout, ids):
-    """The host-pointer call's fast route -- frame read where it was uploaded (F32), poses and
-    parent slots pulled from pinned memory by the rectangles kernel, log-likelihoods stored into
-    pinned memory by the raster kernel -- against the older route (ingest copy, H2D / D2H copies;
-    RBS_FRAME_INGEST=1, RBS_HOST_STAGED_COPIES=1, read at rbs_create): the same numbers and planes
-    bit for bit over a resampled sequence with repeated, skipped and frame-buffer frames."""
+def test_host_call_routes_agree_bit_for_bit(gpu_lib, precision, layout, ids):
+    """The host-pointer call's route -- frame read where it was uploaded, poses and parent slots
+    pulled from pinned memory by the rectangles kernel, log-likelihoods stored into pinned memory
+    by the raster kernel -- against the device-pointer route (rbs_set_observation_device +
+    rbs_loglikes_device from device tensors: frame ingested into the handle's buffer, poses,
+    parents and results in device memory): the same numbers and planes bit for bit over a
+    resampled sequence with repeated, skipped and frame-buffer frames."""
+    import torch
     n, cols, rows = 64, 160, 120
     om, cam, P = sc.make_scene(("m1_l2", "box12"), cols, rows, max_particles=n)
-
-    def make(old):
-        monkeypatch.setenv("RBS_FRAME_INGEST", "1" if old else "0")
-        monkeypatch.setenv("RBS_HOST_STAGED_COPIES", "1" if old else "0")
-        return RbSensor(om, cam, P, max_particles=n, precision=precision, state_layout=layout, device_ids=ids)
-
-    new, old = make(False), make(True)
+    dev = torch.device("cuda", 0)
+    stream = torch.cuda.Stream(device=dev)
+    host = RbSensor(om, cam, P, max_particles=n, precision=precision, state_layout=layout, device_ids=ids)
+    devp = RbSensor(om, cam, P, max_particles=n, precision=precision, state_layout=layout, device_ids=ids)
     try:
         rng = np.random.default_rng(21)
         with RbSensor(om, cam, P, max_particles=1) as r:
             frames = [synth.make_frame(r.render_depth(synth.truth_pose(2, frame=k)), rows, cols, rng).astype(np.float32) for k in range(12)]
-        idx = {id(new): np.arange(n, dtype=np.int32), id(old): np.arange(n, dtype=np.int32)}
+        d_frames = [torch.from_numpy(f).to(dev) for f in frames]
+        torch.cuda.synchronize()
         for k in range(40):
-            f = frames[k % len(frames)]
+            f = k % len(frames)
             m = n if k % 5 else n // 2
-            poses = synth.particle_poses(synth.truth_pose(2, frame=k % len(frames)), m, rng)
+            poses = synth.particle_poses(synth.truth_pose(2, frame=f), m, rng)
             parents = rng.integers(0, n, m).astype(np.int32)
             upd = k % 4 != 3
-            outs = []
-            for s in (new, old):
-                if k % 6 == 2:                      # two frames, the first never evaluated
-                    s.set_observation(frames[(k + 1) % len(frames)])
-                if k % 3 == 1:                      # through the handle's pinned buffer
-                    np.copyto(s.frame_buffer(), f)
-                    s.commit_frame()
-                elif k % 7 != 6:                    # (k % 7 == 6: the previous frame again, no new observation)
-                    s.set_observation(f)
-                outs.append(s.loglikes_poses(poses, parents.copy(), update=upd))
-            assert np.array_equal(outs[0], outs[1], equal_nan=True), k
+            if k % 6 == 2:                          # two frames, the first never evaluated
+                host.set_observation(frames[(k + 1) % len(frames)])
+                devp.set_observation_device(d_frames[(k + 1) % len(frames)].data_ptr(), stream.cuda_stream)
+            if k % 3 == 1:                          # through the handle's pinned buffer
+                np.copyto(host.frame_buffer(), frames[f])
+                host.commit_frame()
+            elif k % 7 != 6:                        # (k % 7 == 6: the previous frame again, no new observation)
+                host.set_observation(frames[f])
+            if k % 3 == 1 or k % 7 != 6:
+                devp.set_observation_device(d_frames[f].data_ptr(), stream.cuda_stream)
+            got_host = host.loglikes_poses(poses, parents.copy(), update=upd)
+            dp = torch.from_numpy(np.ascontiguousarray(poses.reshape(m, -1))).to(dev)
+            di = torch.from_numpy(parents.copy()).to(dev)
+            do = torch.empty(m, dtype=torch.float64, device=dev)
+            torch.cuda.synchronize()
+            devp.loglikes_device(dp.data_ptr(), di.data_ptr(), m, upd, do.data_ptr(), stream.cuda_stream)
+            devp.synchronize()
+            torch.cuda.synchronize()
+            assert np.array_equal(got_host, do.cpu().numpy(), equal_nan=True), k
             if k % 10 == 9:
-                assert np.array_equal(new.get_observation(), old.get_observation(), equal_nan=True), k
+                assert np.array_equal(host.get_observation(), devp.get_observation(), equal_nan=True), k
         for slot in range(0, n, 7):
-            assert np.array_equal(new.get_window(slot), old.get_window(slot)), slot
-            assert np.array_equal(new.get_occlusion(slot), old.get_occlusion(slot)), slot
+            assert np.array_equal(host.get_window(slot), devp.get_window(slot)), slot
+            assert np.array_equal(host.get_occlusion(slot), devp.get_occlusion(slot)), slot
     finally:
-        new.close()
-        old.close()
+        host.close()
+        devp.close()
 
 
 @pytest.mark.parametrize("precision", ["f32", "f64"])
