@@ -4511,3 +4511,7 @@ int32_t rbs_tracker_get(rbs_tracker* t, double* particles, double* log_weights, 
 // The robust Gaussian tracker (rbs_gauss_*): its kernels and host side.
 #include "rbsensor_gauss.hip"
 #include "rbsensor_find.hip"
+
+#ifdef RBS_TEST_HOOKS   // (librbsensor_mi355x_hooks.so only) rbs_test_*: the per-pixel likelihood's inline functions, value by value (tests/test_gpu_pixel_math.py)
+#include "rbsensor_probes.hip"
+#endif

@@ -1179,10 +1179,10 @@ __device__ RBS_EVAL_INLINE double pixel_loglik(const DevParams& P, const MathTab
 // (Numerical Recipes' erfcc, fractional error 1.2e-7 everywhere); E1/(E1-1) as
 // 1/(1 - exp(-lam r)); log(sum / p_bg) as log(sum) - log(p_bg), log(p_bg) recomputed per evaluated
 // pixel in float32 like every other term that depends on the observation only.  About 50 VALU instructions per 64 pixels instead of 125 (ocml's
-// expf / erfcf / logf and correctly rounded divisions) or 250 (binary64).  Per-pixel error of
-// the log term: 1.3e-7 mean, 1.7e-6 max, bias -3e-8 (numpy float32 emulation over 4e5 random
-// pixels); the particle's sum is accumulated in binary64.  tests/: <= 1e-5 relative against the
-// reference-semantics (LAZY) oracle, the north_star tolerance.
+// expf / erfcf / logf and correctly rounded divisions) or 250 (binary64).  Per-pixel error of the log term against the oracle: 1.8e-7 mean,
+// 3.0e-6 max, bias +3e-8, posterior 6.6e-7 max (tests/pixel_f32_twin.py, the numpy float32 twin of these functions, over 4e5 pixels; the device
+// is held to twice the twin's worst and mean pixel by pixel: tests/test_gpu_pixel_math.py); the particle's sum is accumulated
+// in binary64.  tests/: <= 1e-5 relative against the reference-semantics (LAZY) oracle, the north_star tolerance.
 #ifndef RBS_F32_EXP
 #define RBS_F32_EXP 0
 #endif

@@ -16,6 +16,11 @@ void rbsm_log_f32(const float* x, double* out, long n)
 {
     for (long i = 0; i < n; ++i) out[i] = rbsm::log_f32(x[i], rbsm::kLogTab);
 }
+// the per-frame terms of n observed depths, [n][4] (what the device stores per frame pixel)
+void rbsm_frame_terms(const float* obs, long n, double tw, double ms, double sf, double lam, double* out4)
+{
+    for (long i = 0; i < n; ++i) rbsm::frame_terms((double)obs[i], tw, ms, sf, lam, out4 + 4 * i);
+}
 }
 
 // The whole pixel likelihood as the F64 raster kernel evaluates it (rbsm::frame_terms +

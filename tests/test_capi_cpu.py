@@ -220,8 +220,19 @@ def test_create_survives_arbitrary_configs():
 
 
 def test_release_library_carries_no_fault_injection_hook():
-    """RBS_TEST_FAULT is read by the test build (librbsensor_mi355x_hooks.so, -DRBS_TEST_HOOKS) only."""
+    """RBS_TEST_FAULT is read by the test build (librbsensor_mi355x_hooks.so, -DRBS_TEST_HOOKS) only.  So are the per-pixel
+    likelihood's probes (rbsensor_probes.hip, tests/test_gpu_pixel_math.py): the hooks build exports every one, the release build none."""
+    from pixel_probes import PROBE_SYMBOLS
     lib = os.path.join(ROOT, "dbot_ros_amd", "lib")
-    assert b"RBS_TEST_FAULT" not in open(os.path.join(lib, "librbsensor_mi355x.so"), "rb").read()
+    release = open(os.path.join(lib, "librbsensor_mi355x.so"), "rb").read()
+    assert b"RBS_TEST_FAULT" not in release
     hooks = os.path.join(lib, "librbsensor_mi355x_hooks.so")
-    assert os.path.exists(hooks) and b"RBS_TEST_FAULT" in open(hooks, "rb").read()
+    assert os.path.exists(hooks)
+    test_build = open(hooks, "rb").read()
+    assert b"RBS_TEST_FAULT" in test_build
+    assert len(PROBE_SYMBOLS) == 8
+    assert b"rbs_test_" not in release and b"rbs5probe" not in release        # no entry point, no probe kernel (rbs::probe::*)
+    for s in PROBE_SYMBOLS:
+        assert s.encode() + b"\0" in test_build, s                            # (a name in the dynamic symbol table)
+    exported = C.CDLL(hooks) if os.path.abspath(_capi.LIB_PATH) == os.path.abspath(hooks) else None
+    assert exported is None or all(hasattr(exported, s) for s in PROBE_SYMBOLS)

@@ -18,7 +18,9 @@ import numpy as np
 import pytest
 
 import oracle_binding as ob
+import pixel_math_cases as cases
 import scenarios as sc
+from pixel_math_cases import pixels as _pixels   # (the generators are shared with tests/test_gpu_pixel_math.py)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB = os.path.join(HERE, "cpp", "librbs_math_host.so")
@@ -38,13 +40,11 @@ def _call(lib, fn, x, dtype=np.float64):
 
 
 def test_exp_nonpos(mlib):
-    rng = np.random.default_rng(0)
-    x = -np.concatenate([rng.uniform(0, 40, 300000), rng.uniform(0, 1, 200000), rng.uniform(0, 700, 100000),
-                         [0.0, 1e-300, 0.5 * np.log(2), 708.0]])
+    x = cases.exp_args()
     got, ref = _call(mlib, "rbsm_exp_nonpos", x), np.exp(x)
     assert (np.abs(got - ref) / ref).max() <= 1e-15
     # the far tail: gradual underflow and the clamp, never NaN / negative
-    tail = _call(mlib, "rbsm_exp_nonpos", [-745.0, -800.0, -1e6, -np.inf])
+    tail = _call(mlib, "rbsm_exp_nonpos", cases.EXP_TAIL)
     assert np.all(tail >= 0) and np.all(tail <= 1e-320)
     assert _call(mlib, "rbsm_exp_nonpos", [0.0])[0] == 1.0
 
@@ -61,9 +61,7 @@ def test_exp_against_mpmath(mlib):
 
 def test_erfc_pos(mlib):
     from scipy.special import erfc
-    rng = np.random.default_rng(2)
-    z = np.concatenate([rng.uniform(0, 6, 400000), rng.uniform(0, 0.5, 100000), rng.uniform(6, 1e3, 1000),
-                        np.arange(0, 49) / 8.0, np.arange(1, 49) / 8.0 - 1e-12, [np.inf, 1e300]])
+    z = cases.erfc_args()
     got = _call(mlib, "rbsm_erfc_pos", z)
     assert np.abs(got - erfc(z)).max() <= 4e-16
     assert np.all(got >= 0) and np.all(got <= 1.0)
@@ -80,33 +78,17 @@ def test_erfc_against_mpmath(mlib):
 
 
 def test_log_f32(mlib):
-    rng = np.random.default_rng(4)
-    x = np.concatenate([rng.uniform(1e-3, 1e4, 400000), np.exp(rng.uniform(-87, 88, 300000)), rng.uniform(0.9, 1.1, 100000),
-                        [1.0, 2.0, 0.5, np.float32(1.0) + np.finfo(np.float32).eps, 1.1754944e-38, 3.4028235e38]]).astype(np.float32)
+    x = cases.log_args()
     got, ref = _call(mlib, "rbsm_log_f32", x, np.float32), np.log(x.astype(np.float64))
     assert np.all(np.abs(got - ref) <= 2.5e-16 + np.spacing(np.abs(ref)))
     assert abs(_call(mlib, "rbsm_log_f32", [1.0], np.float32)[0]) <= 1e-17
     # not a positive normal float: what log gives (never a finite number read off the exponent field)
-    odd = _call(mlib, "rbsm_log_f32", [0.0, np.inf, np.nan, -1.0, 1e-40], np.float32)
+    odd = _call(mlib, "rbsm_log_f32", cases.LOG_ODD, np.float32)
     assert odd[0] == -np.inf and odd[1] == np.inf and np.isnan(odd[2]) and np.isnan(odd[3])
     assert abs(odd[4] - np.log(np.float64(np.float32(1e-40)))) <= 1e-13
 
 
-def _pixels(n, seed):
-    """(observation, rendered depth, prior) triples as the raster kernel meets them: the object seen
-    (|r - o| of a few sigma), occluders in front (o << r), the background behind (o >> r), priors
-    over the whole unit interval."""
-    rng = np.random.default_rng(seed)
-    r = rng.uniform(0.3, 3.0, n)
-    sigma = 0.003 + 0.0014247 * r * r
-    kind = rng.integers(0, 4, n)
-    o = np.where(kind <= 1, r + sigma * rng.normal(0, 1.5, n),
-                 np.where(kind == 2, r - rng.uniform(0.01, 0.29, n), r + rng.uniform(0.01, 3.0, n)))
-    prior = np.where(rng.random(n) < 0.5, rng.uniform(0.0, 1.0, n), np.float32(0.1))
-    return o.astype(np.float32), r.astype(np.float32), prior.astype(np.float32)
-
-
-@pytest.mark.parametrize("params", [{}, {"tail_weight": 0.05, "model_sigma": 0.001, "sigma_factor": 0.003}])
+@pytest.mark.parametrize("params", cases.PARAM_SETS)
 def test_pixel_likelihood_matches_the_oracle_pixel_by_pixel(mlib, params):
     om, cam, P = sc.make_scene(("m1_l2",), 80, 60, max_particles=1)
     for k, v in params.items():
@@ -120,16 +102,4 @@ def test_pixel_likelihood_matches_the_oracle_pixel_by_pixel(mlib, params):
     mlib.rbsm_pixel_loglik(o.ctypes.data_as(fp), r.ctypes.data_as(fp), prior.ctypes.data_as(fp), C.c_long(n),
                            C.c_double(P.kinect.tail_weight), C.c_double(P.kinect.model_sigma), C.c_double(P.kinect.sigma_factor),
                            C.c_double(np.log(2.0)), C.c_double(6.0), ll.ctypes.data_as(C.POINTER(C.c_double)), post.ctypes.data_as(fp))
-    assert np.all(np.isfinite(ll)) and np.all(np.isfinite(ref_ll))
-    same = ll == ref_ll
-    d = np.abs(ll - ref_ll)
-    # where the argument of the log (a float) is the same, the logs agree to their rounding; a flipped
-    # float rounding moves the term by a float ulp or two of the ratio
-    assert d[same].size and np.all(d <= 2.6e-7)
-    close = d <= 2.5e-16 + 2 * np.spacing(np.abs(ref_ll))
-    assert (~close).mean() <= 2e-5, (~close).mean()
-    pd = np.abs(post.view(np.int32).astype(np.int64) - ref_post.view(np.int32).astype(np.int64))
-    assert pd.max() <= 1 and (pd != 0).mean() <= 2e-5, (pd.max(), (pd != 0).mean())
-    # a particle's sum over 5 000 such pixels: the north-star tolerance with six orders to spare
-    s, sr = ll.reshape(-1, 5000).sum(1), ref_ll.reshape(-1, 5000).sum(1)
-    assert (np.abs(s - sr) / np.maximum(1.0, np.abs(sr))).max() <= 1e-11
+    cases.check_pixel_terms(ll, post, ref_ll, ref_post)
