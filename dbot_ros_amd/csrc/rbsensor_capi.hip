@@ -3979,6 +3979,43 @@ void launch_mean(const rbt::TrackerDev& T, hipStream_t s)
     hipLaunchKernelGGL(rbt::mean_m2_kernel, dim3((unsigned)blocks), dim3(1024), 0, s, T);
     hipLaunchKernelGGL(rbt::mean_m3_kernel, dim3(1), dim3(64), 0, s, T, blocks);
 }
+// The other steps of a frame, each with its launch geometry in one place: rbs_tracker_submit, the
+// tracker over several devices and the test build's filter probe (rbsensor_probes.hip) launch them
+// through these.
+inline dim3 per_particle_grid(const rbt::TrackerDev& T) { return dim3((unsigned)((T.n + 255) / 256)); }
+void launch_propagate(const rbt::TrackerDev& T, int b, int recentre, hipStream_t s)
+{
+    hipLaunchKernelGGL(rbt::propagate_kernel, per_particle_grid(T), dim3(256), 0, s, T, b, recentre);
+}
+void launch_resample_gather(const rbt::TrackerDev& T, int b, hipStream_t s)
+{
+    hipLaunchKernelGGL(rbt::resample_gather_kernel, dim3((unsigned)T.n), dim3(64), 0, s, T, b);
+}
+void launch_gather(const rbt::TrackerDev& T, hipStream_t s)
+{
+    hipLaunchKernelGGL(rbt::gather_kernel, dim3((unsigned)T.n), dim3(64), 0, s, T);
+}
+void launch_filter_tail(const rbt::TrackerDev& T, int b, int updated, hipStream_t s)
+{
+    hipLaunchKernelGGL(rbt::filter_tail_kernel, dim3(1), dim3(1024), 0, s, T, b, updated);
+}
+void launch_filter_step(const rbt::TrackerDev& T, int b, int updated, int last, hipStream_t s)
+{
+    hipLaunchKernelGGL(rbt::filter_step_kernel, dim3(1), dim3(1024), 0, s, T, b, updated, last);
+}
+void launch_recentre(const rbt::TrackerDev& T, double* particles, hipStream_t s)
+{
+    hipLaunchKernelGGL(rbt::recentre_kernel, per_particle_grid(T), dim3(256), 0, s, T, particles);
+}
+// after a sampling block's gather: the gathered arrays are the block's result
+void swap_gathered(rbt::TrackerDev& T)
+{
+    std::swap(T.part_old, T.part_old2);
+    std::swap(T.part_new, T.part_new2);
+    std::swap(T.noise, T.noise2);
+    std::swap(T.ll, T.ll2);
+    std::swap(T.idx, T.idx2);
+}
 
 // One device's tracker state.  cap > 0: the sensor is a shard of a group with `cap` slots per device.
 int32_t tracker_create_one(rbs_handle* sensor, const rbs_tracker_params* p, int n_dev, int cap, rbs_tracker** out)
@@ -4186,7 +4223,7 @@ int32_t group_tracker_track(rbs_tracker* t, const float* frame, const double* no
         for (int k = 0; k < nd; ++k) {
             rbs_tracker* r = t->reps[k];
             RBT_HIP(t, hipSetDevice(r->s->device));
-            hipLaunchKernelGGL(rbt::propagate_kernel, g256, b256, 0, streams[k], r->T, b, 0);
+            launch_propagate(r->T, b, 0, streams[k]);
             hipLaunchKernelGGL(rbt::layout_kernel, dim3(1), dim3(1024), 0, streams[k], r->T, nd, cap);
             const int lo = std::min(n, k * cap), cnt = std::min(n, (k + 1) * cap) - lo;
             if (cnt > 0)
@@ -4216,13 +4253,9 @@ int32_t group_tracker_track(rbs_tracker* t, const float* frame, const double* no
             hipLaunchKernelGGL(rbt::shard_scatter_kernel, g256, b256, 0, s, T, last ? 1 : 0);
             launch_weights(T, 0, s);
             hipLaunchKernelGGL(rbt::resample_kernel, g256, b256, 0, s, T, b);
-            hipLaunchKernelGGL(rbt::gather_kernel, dim3((unsigned)T.n), dim3(64), 0, s, T);
+            launch_gather(T, s);
             RBT_HIP(t, hipGetLastError());
-            std::swap(T.part_old, T.part_old2);
-            std::swap(T.part_new, T.part_new2);
-            std::swap(T.noise, T.noise2);
-            std::swap(T.ll, T.ll2);
-            std::swap(T.idx, T.idx2);
+            swap_gathered(T);
         }
     }
     int flags[2] = {0, 0};
@@ -4231,7 +4264,7 @@ int32_t group_tracker_track(rbs_tracker* t, const float* frame, const double* no
         rbt::TrackerDev& T = r->T;
         RBT_HIP(t, hipSetDevice(r->s->device));
         launch_mean(T, streams[k]);
-        hipLaunchKernelGGL(rbt::recentre_kernel, g256, b256, 0, streams[k], T, T.part_new);
+        launch_recentre(T, T.part_new, streams[k]);
         RBT_HIP(t, hipGetLastError());
         std::swap(T.part_old, T.part_new);   // this frame's particles are the next frame's old ones
         if (k == 0) {
@@ -4328,7 +4361,6 @@ static int32_t tracker_submit_impl(rbs_tracker* t, const float* frame, const dou
     T.seed = seed;
     T.host_state = t->h_state_dev[slot];
     T.host_flags = t->h_flags_dev[slot];
-    const dim3 g256((unsigned)((T.n + 255) / 256)), b256(256);
     const char* nf = std::getenv("RBS_TRACKER_FUSED");
     const bool fused = T.n <= rbt::kFusedFilterMax && !(nf && std::atoi(nf) == 0);
     static const bool tail_on = [] { const char* e = std::getenv("RBS_TRACKER_TAIL"); return !(e && std::atoi(e) == 0); }();
@@ -4337,7 +4369,7 @@ static int32_t tracker_submit_impl(rbs_tracker* t, const float* frame, const dou
         const bool last = b == T.parts - 1;
         // (the transition fused into the sensor's rectangles kernel -- one launch less -- measured no
         // gain: 3 987 against 3 976 frames/s at 2 000 particles)
-        hipLaunchKernelGGL(rbt::propagate_kernel, g256, b256, 0, s, T, b, b == 0 && t->recentre_pending ? 1 : 0);
+        launch_propagate(T, b, b == 0 && t->recentre_pending ? 1 : 0, s);
         if (b == 0) t->recentre_pending = false;
         RBT_HIP(t, hipGetLastError());
         // the frame is handed over AFTER the first transition launch: the transition (and the
@@ -4358,24 +4390,20 @@ static int32_t tracker_submit_impl(rbs_tracker* t, const float* frame, const dou
         }
         if (int32_t rc = enqueue_loglikes(h, T.poses, T.idx, T.n, last, T.ll_new, s)) return rc;
         if (fused) {
-            hipLaunchKernelGGL(rbt::filter_step_kernel, dim3(1), dim3(1024), 0, s, T, b, last ? 1 : 0, last ? 1 : 0);
+            launch_filter_step(T, b, last ? 1 : 0, last ? 1 : 0, s);
         } else if (tail && last) {
             // the estimate first (one launch, the result event right behind it), the gather after
-            hipLaunchKernelGGL(rbt::filter_tail_kernel, dim3(1), dim3(1024), 0, s, T, b, 1);
+            launch_filter_tail(T, b, 1, s);
             RBT_HIP(t, hipGetLastError());
             if (h->slab_px) RBT_HIP(t, hipMemcpyAsync(t->h_serr[slot], h->d_err, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
             RBT_HIP(t, hipEventRecord(t->ev_res[slot], s));
-            hipLaunchKernelGGL(rbt::gather_kernel, dim3((unsigned)T.n), dim3(64), 0, s, T);
+            launch_gather(T, s);
         } else {
             launch_weights(T, last ? 1 : 0, s);
-            hipLaunchKernelGGL(rbt::resample_gather_kernel, dim3((unsigned)T.n), dim3(64), 0, s, T, b);
+            launch_resample_gather(T, b, s);
         }
         RBT_HIP(t, hipGetLastError());
-        std::swap(T.part_old, T.part_old2);
-        std::swap(T.part_new, T.part_new2);
-        std::swap(T.noise, T.noise2);
-        std::swap(T.ll, T.ll2);
-        std::swap(T.idx, T.idx2);
+        swap_gathered(T);
     }
     if (!fused) {
         // (re-centring inside the single mean block was tried: its two rounds of rotations per thread
@@ -4384,7 +4412,7 @@ static int32_t tracker_submit_impl(rbs_tracker* t, const float* frame, const dou
         // the re-centring itself rides in the next frame's first transition launch (the thread that
         // moves particle i re-centres it first); rbs_tracker_get applies it on demand
         static const bool now = [] { const char* e = std::getenv("RBS_TRACKER_RECENTRE_NOW"); return e && std::atoi(e) != 0; }();
-        if (now) hipLaunchKernelGGL(rbt::recentre_kernel, g256, b256, 0, s, T, T.part_new);
+        if (now) launch_recentre(T, T.part_new, s);
         else t->recentre_pending = true;
     }
     RBT_HIP(t, hipGetLastError());
@@ -4495,7 +4523,7 @@ int32_t rbs_tracker_get(rbs_tracker* t, double* particles, double* log_weights, 
     rbt::TrackerDev& T = t->T;
     RBT_HIP(t, hipSetDevice(t->s->device));
     if (t->recentre_pending) {   // (deferred into the next frame's transition launch: apply it now)
-        hipLaunchKernelGGL(rbt::recentre_kernel, dim3((unsigned)((T.n + 255) / 256)), dim3(256), 0, t->s->stream, T, T.part_old);
+        launch_recentre(T, T.part_old, t->s->stream);
         RBT_HIP(t, hipGetLastError());
         t->recentre_pending = false;
     }

@@ -7,6 +7,11 @@
 // inline functions -- the function the raster kernels call, nothing copied -- over a host array, one thread per element, and
 // hands every value back: tests/test_gpu_pixel_math.py compares them one by one.
 //
+// rbs_test_filter does the same for the particle filter's kernels (rbsensor_tracker.hip): it builds an rbt::TrackerDev from host
+// arrays, launches a caller-chosen order of the frame's steps through the launch_* helpers rbs_tracker_submit itself uses
+// (rbsensor_capi.hip: no kernel body and no launch geometry is restated here), and hands every array back:
+// tests/test_gpu_filter_kernels.py.
+//
 // Entry points (rbs_test_*): host arrays in, host arrays out, synchronous on the current device.  Null pointers and n < 0 (or
 // n > kProbeMax) are RBS_ERR_INVALID_ARGUMENT, n == 0 is RBS_OK and touches nothing, a HIP failure is RBS_ERR_HIP.
 namespace rbs {
@@ -96,12 +101,14 @@ __global__ void __launch_bounds__(kBlock) pixel_f32_kernel(const DevParams P, co
 
 // Device buffers of one call: freed on every way out.
 struct Buffers {
-    void* p[8] = {};
+    static constexpr int kMax = 32;
+    void* p[kMax] = {};
     int k = 0;
     hipError_t err = hipSuccess;
     template <class T> T* make(size_t count, const T* from = nullptr)
     {
         void* d = nullptr;
+        if (err == hipSuccess && k >= kMax) err = hipErrorOutOfMemory;
         if (err == hipSuccess) err = hipMalloc(&d, sizeof(T) * count);
         if (err != hipSuccess) return nullptr;
         p[k++] = d;
@@ -136,6 +143,42 @@ inline DevParams probe_params(double tw, double ms, double sf, double lam)
 
 }  // namespace probe
 }  // namespace rbs
+
+// ---------------------------------------------------------------------------- the particle filter's kernels
+// One call's arrays.  Every array is copied to the device before the first step and back after the last one, under the name
+// it has THEN (RBS_TEST_STEP_SWAP exchanges an array with its gather target, as rbs_tracker_submit does after a sampling
+// block), so the caller sees everything the kernels wrote and, by the values it put there, everything they left alone.
+// normals [parts][n][6] and uniforms [parts][n] may be null: the device generator then draws them from (seed, frame).
+struct rbs_test_filter_io {
+    int32_t n, parts;
+    double sigma[6];
+    double vf, max_kl;
+    uint64_t seed, frame;
+    double* part_old; double* part_new; double* part_old2; double* part_new2;   // [n][parts * 12]
+    double* noise; double* noise2;                                                // [n][parts][6]
+    double* logw; double* ll; double* ll2; double* ll_new; double* cdf;          // [n]
+    int32_t* idx; int32_t* idx2; int32_t* parents;                               // [n]
+    double* deflt;                                                                // [parts * 12]
+    double* mean;                                                                 // [parts * 12 + parts * 9]
+    double* poses;                                                                // [n][parts][12]
+    int32_t* flag;                                                                // [2]
+    const double* normals; const double* uniforms;
+    double* host_state;                                                           // [parts * 12]: publish_result's pinned target, in and out
+    int32_t* host_flags;                                                          // [3]
+};
+enum {
+    RBS_TEST_STEP_PROPAGATE = 0,        // b, recentre
+    RBS_TEST_STEP_WEIGHTS = 1,          // updated
+    RBS_TEST_STEP_RESAMPLE_GATHER = 2,  // b
+    RBS_TEST_STEP_GATHER = 3,
+    RBS_TEST_STEP_FILTER_TAIL = 4,      // b, updated
+    RBS_TEST_STEP_FILTER_STEP = 5,      // b, updated, last
+    RBS_TEST_STEP_MEAN = 6,
+    RBS_TEST_STEP_RECENTRE = 7,         // part_new, in place
+    RBS_TEST_STEP_SWAP = 8,             // no launch: swap_gathered
+    RBS_TEST_STEP_COUNT = 9
+};
+struct rbs_test_filter_step { int32_t code, b, updated, last, recentre; };
 
 extern "C" {
 
@@ -284,3 +327,82 @@ int32_t rbs_test_pixel_f32(const float* obs, const float* depth, const float* pr
 }
 
 }  // extern "C"
+
+extern "C" int32_t rbs_test_filter(const rbs_test_filter_io* io, const rbs_test_filter_step* steps, int32_t n_steps)
+{
+    namespace pr = rbs::probe;
+    constexpr int kMaxSteps = 16;
+    if (!io || !steps || n_steps < 0 || n_steps > kMaxSteps) return RBS_ERR_INVALID_ARGUMENT;
+    if (io->n < 1 || io->n > rbt::kRedBlocks * rbt::kChunk || io->parts < 1 || io->parts > rbs::kMaxBodies) return RBS_ERR_INVALID_ARGUMENT;
+    if (!io->part_old || !io->part_new || !io->part_old2 || !io->part_new2 || !io->noise || !io->noise2 || !io->logw || !io->ll || !io->ll2 ||
+        !io->ll_new || !io->cdf || !io->idx || !io->idx2 || !io->parents || !io->deflt || !io->mean || !io->poses || !io->flag ||
+        !io->host_state || !io->host_flags)
+        return RBS_ERR_INVALID_ARGUMENT;
+    for (int k = 0; k < n_steps; ++k)
+        if (steps[k].code < 0 || steps[k].code >= RBS_TEST_STEP_COUNT || steps[k].b < 0 || steps[k].b >= io->parts) return RBS_ERR_INVALID_ARGUMENT;
+    const size_t n = (size_t)io->n, parts = (size_t)io->parts, D = parts * rbt::kBody, P6 = parts * 6;
+    pr::Buffers B;
+    rbt::TrackerDev T{};
+    T.n = io->n; T.parts = io->parts; T.D = (int)D;
+    for (int k = 0; k < 6; ++k) T.sigma[k] = io->sigma[k];
+    T.vf = io->vf; T.max_kl = io->max_kl; T.seed = io->seed; T.frame = io->frame;
+    T.part_old = B.make<double>(n * D, io->part_old);    T.part_new = B.make<double>(n * D, io->part_new);
+    T.part_old2 = B.make<double>(n * D, io->part_old2);  T.part_new2 = B.make<double>(n * D, io->part_new2);
+    T.noise = B.make<double>(n * P6, io->noise);         T.noise2 = B.make<double>(n * P6, io->noise2);
+    T.logw = B.make<double>(n, io->logw);                T.ll = B.make<double>(n, io->ll);
+    T.ll2 = B.make<double>(n, io->ll2);                  T.ll_new = B.make<double>(n, io->ll_new);
+    T.cdf = B.make<double>(n, io->cdf);
+    T.idx = B.make<int>(n, io->idx);                     T.idx2 = B.make<int>(n, io->idx2);
+    T.parents = B.make<int>(n, io->parents);
+    T.deflt = B.make<double>(D, io->deflt);              T.mean = B.make<double>(D + parts * 9, io->mean);
+    T.poses = B.make<double>(n * parts * 12, io->poses); T.flag = B.make<int>(2, io->flag);
+    T.red = B.make<double>((size_t)rbt::kRedBlocks * (3 + D));
+    if (io->normals) T.normals = B.make<double>(n * P6, io->normals);
+    if (io->uniforms) T.uniforms = B.make<double>(n * parts, io->uniforms);
+    // publish_result's target: pinned host memory of this call's own, as rbs_tracker_create maps the tracker's
+    double* h_state = nullptr;
+    int* h_flags = nullptr;
+    if (B.err == hipSuccess) B.err = hipHostMalloc(&h_state, sizeof(double) * D, hipHostMallocDefault);
+    if (B.err == hipSuccess) B.err = hipHostMalloc(&h_flags, sizeof(int) * 4, hipHostMallocDefault);
+    if (B.err == hipSuccess) {
+        std::memcpy(h_state, io->host_state, sizeof(double) * D);
+        for (int k = 0; k < 3; ++k) h_flags[k] = io->host_flags[k];
+        B.err = hipHostGetDevicePointer(reinterpret_cast<void**>(&T.host_state), h_state, 0);
+    }
+    if (B.err == hipSuccess) B.err = hipHostGetDevicePointer(reinterpret_cast<void**>(&T.host_flags), h_flags, 0);
+    if (B.err == hipSuccess) B.err = hipMemset(T.red, 0, sizeof(double) * (size_t)rbt::kRedBlocks * (3 + D));
+    if (B.err == hipSuccess) {
+        hipStream_t s = nullptr;
+        for (int k = 0; k < n_steps; ++k) {
+            const rbs_test_filter_step& q = steps[k];
+            switch (q.code) {
+            case RBS_TEST_STEP_PROPAGATE: launch_propagate(T, q.b, q.recentre ? 1 : 0, s); break;
+            case RBS_TEST_STEP_WEIGHTS: launch_weights(T, q.updated ? 1 : 0, s); break;
+            case RBS_TEST_STEP_RESAMPLE_GATHER: launch_resample_gather(T, q.b, s); break;
+            case RBS_TEST_STEP_GATHER: launch_gather(T, s); break;
+            case RBS_TEST_STEP_FILTER_TAIL: launch_filter_tail(T, q.b, q.updated ? 1 : 0, s); break;
+            case RBS_TEST_STEP_FILTER_STEP: launch_filter_step(T, q.b, q.updated ? 1 : 0, q.last ? 1 : 0, s); break;
+            case RBS_TEST_STEP_MEAN: launch_mean(T, s); break;
+            case RBS_TEST_STEP_RECENTRE: launch_recentre(T, T.part_new, s); break;
+            default: swap_gathered(T); break;
+            }
+        }
+        B.ran();
+    }
+    B.fetch(io->part_old, T.part_old, n * D);    B.fetch(io->part_new, T.part_new, n * D);
+    B.fetch(io->part_old2, T.part_old2, n * D);  B.fetch(io->part_new2, T.part_new2, n * D);
+    B.fetch(io->noise, T.noise, n * P6);         B.fetch(io->noise2, T.noise2, n * P6);
+    B.fetch(io->logw, T.logw, n);                B.fetch(io->ll, T.ll, n);
+    B.fetch(io->ll2, T.ll2, n);                  B.fetch(io->cdf, T.cdf, n);
+    B.fetch(io->idx, T.idx, n);                  B.fetch(io->idx2, T.idx2, n);
+    B.fetch(io->parents, T.parents, n);
+    B.fetch(io->deflt, T.deflt, D);              B.fetch(io->mean, T.mean, D + parts * 9);
+    B.fetch(io->poses, T.poses, n * parts * 12); B.fetch(io->flag, T.flag, 2);
+    if (B.err == hipSuccess) {
+        std::memcpy(io->host_state, h_state, sizeof(double) * D);
+        for (int k = 0; k < 3; ++k) io->host_flags[k] = h_flags[k];
+    }
+    if (h_state) (void)hipHostFree(h_state);
+    if (h_flags) (void)hipHostFree(h_flags);
+    return B.status();
+}

@@ -247,6 +247,15 @@ __device__ inline void weights_body(const TrackerDev& T, int updated, double* sh
         const double t = __shfl_up(v, off, 64);
         if (lane >= off) v += t;
     }
+    // The scan's sums and a thread's own running sum below are rounded in different orders and may differ by an ulp
+    // either way: where a particle's weight is zero the cdf then stepped DOWN by that ulp, and a uniform inside the gap
+    // chose the weightless particle behind it.  So the thread ends become a running maximum (exact, no rounding), each
+    // thread's values stop at its end, and the next thread -- and through sh[] the next wave -- starts from it.
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const double t = __shfl_up(v, off, 64);
+        if (lane >= off) v = fmax(v, t);
+    }
     const double below = __shfl_up(v, 1, 64);   // the wave's sum up to the previous lane
     __syncthreads();
     if (lane == 63) sh[wv] = v;
@@ -257,9 +266,10 @@ __device__ inline void weights_body(const TrackerDev& T, int updated, double* sh
         total += sh[k];
     }
     double run = prefix + (lane ? below : 0.0);
+    const double top = prefix + v;
     for (int i = lo; i < hi; ++i) {
         run += exp(T.logw[i] - m);
-        T.cdf[i] = run / total;
+        T.cdf[i] = fmin(run, top) / total;
     }
 }
 
@@ -360,11 +370,22 @@ __global__ __launch_bounds__(1024) void weights_w4_kernel(const TrackerDev T)
         sh[threadIdx.x] += v;
         __syncthreads();
     }
-    double acc = T.red[kRedBlocks + blockIdx.x] + (threadIdx.x ? sh[threadIdx.x - 1] : 0.0);
+    // non-decreasing across threads and blocks, as in weights_body: the thread ends as a running maximum, a thread's
+    // values stop at its end and at the next block's offset (w3's sums of w2's block sums: yet another order)
+    for (int off = 1; off < 1024; off <<= 1) {
+        const double v = (int)threadIdx.x >= off ? sh[threadIdx.x - off] : 0.0;
+        __syncthreads();
+        sh[threadIdx.x] = fmax(sh[threadIdx.x], v);
+        __syncthreads();
+    }
     const double S = T.red[0];
+    const double offset = T.red[kRedBlocks + blockIdx.x];
+    const double next = blockIdx.x + 1 < gridDim.x ? T.red[kRedBlocks + blockIdx.x + 1] : S;
+    double acc = offset + (threadIdx.x ? sh[threadIdx.x - 1] : 0.0);
+    const double top = fmin(offset + sh[threadIdx.x], next);
     for (int k = 0; k < 4; ++k) {
         acc += e[k];
-        if (base + k < T.n) T.cdf[base + k] = acc / S;
+        if (base + k < T.n) T.cdf[base + k] = fmin(acc, top) / S;
     }
 }
 
