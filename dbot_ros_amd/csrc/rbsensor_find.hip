@@ -265,7 +265,8 @@ __global__ __launch_bounds__(256) void rbs_find_children_kernel(const double* __
     o[11] = P[11] + st * nz[5];
 }
 
-// One thread per survivor: its best child (ties: lowest j; NaN never beats a number) becomes the survivor.
+// One thread per survivor: its best child (ties: lowest j; NaN never beats a number) becomes the survivor.  All children NaN:
+// child 0 -- the survivor itself -- with a NaN score; the final sort then puts it last (include/rbsensor_mi355x.h, step 6).
 __global__ __launch_bounds__(64) void rbs_find_select_kernel(const double* __restrict__ child, const double* __restrict__ child_score,
                                                              int S, int children, double* __restrict__ surv, double* __restrict__ surv_score)
 {
@@ -311,6 +312,98 @@ __global__ __launch_bounds__(64) void rbs_find_keep_kernel(const double* __restr
     surv_idx[i] = cand_idx[c];
 }
 
+// ---------------------------------------------------------------------------- launches
+// One helper per launch of a find: a stream and raw device pointers, nothing of an rbs_find.  rbs_find_run and
+// rbs_find_get_stage launch through these, and so do the probes of the test build (rbsensor_probes.hip).
+
+// the suppression's two thresholds from the parameters: |t - t'|^2 <= t2 and trace(R^T R') >= trace_min
+inline void nms_thresholds(double nms_translation, double nms_angle, double* t2, double* trace_min)
+{
+    *t2 = nms_translation * nms_translation;
+    *trace_min = 1.0 + 2.0 * std::cos(nms_angle);
+}
+
+// cells of the seed grid: the size of the seed kernel's `cells` scratch
+inline size_t seed_cells(int rows, int cols, int stride)
+{
+    return (size_t)((rows + stride - 1) / stride) * (size_t)((cols + stride - 1) / stride);
+}
+
+// items a top-k of n items to k needs in each of its two ping-pong buffers (the first pass's output)
+inline size_t topk_items(long n, int k) { return (size_t)((n + kTopC - 1) / kTopC) * (size_t)k; }
+
+inline void launch_subsample(hipStream_t st, const float* src, int src_cols, float* dst, int rows, int cols, int f)
+{
+    const int cpx = rows * cols;
+    hipLaunchKernelGGL(rbs_find_subsample_kernel, dim3((unsigned)((cpx + 255) / 256)), dim3(256), 0, st, src, src_cols, dst, rows, cols, f);
+}
+
+inline void launch_seeds(hipStream_t st, const float* frame, int rows, int cols, int stride, double dmin, double dmax, int max_seeds,
+                         int* cells, double* seeds, int* info)
+{
+    hipLaunchKernelGGL(rbs_find_seed_kernel, dim3(1), dim3(kSeedThreads), 0, st, frame, rows, cols, stride, dmin, dmax, max_seeds, cells,
+                       seeds, info);
+}
+
+inline void launch_hyp(hipStream_t st, const HypParams& H, long h0, int n, double* poses)
+{
+    hipLaunchKernelGGL(rbs_find_hyp_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, H, h0, n, poses);
+}
+
+inline void launch_gather(hipStream_t st, const HypParams& H, const long long* idx, int n, double* poses)
+{
+    hipLaunchKernelGGL(rbs_find_gather_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, H, idx, n, poses);
+}
+
+// The best k of (score, idx) [n] -- idx == nullptr: positions -- in passes of kTopC-item chunks until one chunk is left;
+// tk_s / tk_i: the ping-pong buffers, topk_items(n, k) items each.  *out_s / *out_i: where the k results lie.
+inline hipError_t launch_topk(hipStream_t st, const double* score, const long long* idx, long n, int k, double* const tk_s[2],
+                              long long* const tk_i[2], const double** out_s, const long long** out_i)
+{
+    int buf = 0;
+    while (true) {
+        const long blocks = (n + kTopC - 1) / kTopC;
+        hipLaunchKernelGGL(rbs_find_topk_kernel, dim3((unsigned)blocks), dim3(kTopThreads), 0, st, score, idx, n, k, tk_s[buf], tk_i[buf]);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        score = tk_s[buf];
+        idx = tk_i[buf];
+        buf ^= 1;
+        n = blocks * k;
+        if (blocks == 1) break;
+    }
+    *out_s = score;
+    *out_i = idx;
+    return hipSuccess;
+}
+
+// the suppression over candidates [n] in order, then the kept ones' poses, scores and indices gathered; count: [1]
+inline void launch_nms_keep(hipStream_t st, const double* cand_pose, const double* cand_score, const long long* cand_idx, int n, double t2,
+                            double trace_min, int max_keep, int* kept, int* count, double* surv, double* surv_score, long long* surv_idx)
+{
+    hipLaunchKernelGGL(rbs_find_nms_kernel, dim3(1), dim3(64), 0, st, cand_pose, cand_score, n, t2, trace_min, max_keep, kept, count);
+    hipLaunchKernelGGL(rbs_find_keep_kernel, dim3(1), dim3(64), 0, st, cand_pose, cand_score, cand_idx, kept, count, surv, surv_score, surv_idx);
+}
+
+inline void launch_children(hipStream_t st, const double* surv, int S, int children, int round, unsigned long long seed, double sigma_t,
+                            double sigma_a, double* out)
+{
+    const int nch = S * children;
+    hipLaunchKernelGGL(rbs_find_children_kernel, dim3((unsigned)((nch + 255) / 256)), dim3(256), 0, st, surv, S, children, round, seed,
+                       sigma_t, sigma_a, out);
+}
+
+inline void launch_select(hipStream_t st, const double* child, const double* child_score, int S, int children, double* surv, double* surv_score)
+{
+    hipLaunchKernelGGL(rbs_find_select_kernel, dim3((unsigned)((S + 63) / 64)), dim3(64), 0, st, child, child_score, S, children, surv, surv_score);
+}
+
+inline void launch_order(hipStream_t st, const double* surv, const double* surv_score, const long long* order, int S, double* out_pose,
+                         double* out_score)
+{
+    hipLaunchKernelGGL(rbs_find_order_kernel, dim3(1), dim3(64), 0, st, surv, surv_score, order, S, out_pose, out_score);
+}
+
 }  // namespace rbf
 
 struct rbs_find {
@@ -321,7 +414,7 @@ struct rbs_find {
     int f = 1, crows = 0, ccols = 0;
     double cK[9] = {};
     double offset = 0.0;
-    double trace_min = 0.0;
+    double t2 = 0.0, trace_min = 0.0;   // the suppression's thresholds (rbf::nms_thresholds)
     hipStream_t st = nullptr;         // = coarse->stream: every kernel of a find
     float* d_full = nullptr;          // [rows*cols] the frame
     float* d_coarse = nullptr;        // [crows*ccols]
@@ -434,23 +527,9 @@ int32_t make_scorer(rbs_find* f, int rows, int cols, const double* K, int max_pa
     return RBS_OK;
 }
 
-int32_t launch_topk(rbs_find* f, const double* score, const long long* idx, long n, int k, const double** out_s,
-                    const long long** out_i)
+int32_t find_topk(rbs_find* f, const double* score, const long long* idx, long n, int k, const double** out_s, const long long** out_i)
 {
-    int buf = 0;
-    while (true) {
-        const long blocks = (n + rbf::kTopC - 1) / rbf::kTopC;
-        hipLaunchKernelGGL(rbf::rbs_find_topk_kernel, dim3((unsigned)blocks), dim3(rbf::kTopThreads), 0, f->st, score, idx, n, k,
-                           f->d_tk_s[buf], f->d_tk_i[buf]);
-        RBF_HIP(f, hipGetLastError());
-        score = f->d_tk_s[buf];
-        idx = f->d_tk_i[buf];
-        buf ^= 1;
-        n = blocks * k;
-        if (blocks == 1) break;
-    }
-    *out_s = score;
-    *out_i = idx;
+    RBF_HIP(f, rbf::launch_topk(f->st, score, idx, n, k, f->d_tk_s, f->d_tk_i, out_s, out_i));
     return RBS_OK;
 }
 
@@ -554,20 +633,19 @@ int32_t rbs_find_create(rbs_handle* sensor, const rbs_find_params* p, rbs_find**
         }
         f->offset = p->depth_offset < 0.0 ? m / (double)nv : p->depth_offset;
     }
-    f->trace_min = 1.0 + 2.0 * std::cos(p->nms_angle);
+    rbf::nms_thresholds(p->nms_translation, p->nms_angle, &f->t2, &f->trace_min);
     const int S = p->n_survivors, nch = S * p->children;
     if (int32_t rc = make_scorer(f, f->crows, f->ccols, f->cK, p->batch, &f->coarse)) return bail(rc);
     if (int32_t rc = make_scorer(f, rows, cols, sensor->cfg.K, nch, &f->full)) return bail(rc);
     f->st = f->coarse->stream;
     const long H = (long)p->max_seeds * p->n_rotations;
-    const int gr = (f->crows + p->seed_stride - 1) / p->seed_stride, gc = (f->ccols + p->seed_stride - 1) / p->seed_stride;
-    f->tk_cap = (size_t)((H + rbf::kTopC - 1) / rbf::kTopC) * p->n_candidates + rbf::kTopC;
+    f->tk_cap = rbf::topk_items(H, p->n_candidates) + rbf::kTopC;
     const size_t R = (size_t)std::max(1, p->rounds);
     if (hipSetDevice(sensor->device) != hipSuccess ||
         hipMalloc(&f->d_full, sizeof(float) * (size_t)rows * cols) != hipSuccess ||
         hipMalloc(&f->d_coarse, sizeof(float) * (size_t)f->crows * f->ccols) != hipSuccess ||
         hipHostMalloc(&f->h_frame, sizeof(float) * (size_t)rows * cols, hipHostMallocDefault) != hipSuccess ||
-        hipMalloc(&f->d_cells, sizeof(int) * (size_t)gr * gc) != hipSuccess ||
+        hipMalloc(&f->d_cells, sizeof(int) * rbf::seed_cells(f->crows, f->ccols, p->seed_stride)) != hipSuccess ||
         hipMalloc(&f->d_seeds, sizeof(double) * 4 * (size_t)p->max_seeds) != hipSuccess ||
         hipMalloc(&f->d_info, sizeof(int) * 4) != hipSuccess ||
         hipHostMalloc(&f->h_info, sizeof(int) * 4, hipHostMallocDefault) != hipSuccess ||
@@ -629,11 +707,9 @@ int32_t rbs_find_run(rbs_find* f, const float* frame, int32_t k, double* poses, 
     hipStream_t st = f->st;
     RBF_HIP(f, hipEventRecord(f->ev[0], st));
     RBF_HIP(f, hipMemcpyAsync(f->d_full, f->h_frame, sizeof(float) * npx, hipMemcpyHostToDevice, st));
-    const int cpx = f->crows * f->ccols;
-    hipLaunchKernelGGL(rbf::rbs_find_subsample_kernel, dim3((unsigned)((cpx + 255) / 256)), dim3(256), 0, st, f->d_full, s->cols,
-                       f->d_coarse, f->crows, f->ccols, f->f);
-    hipLaunchKernelGGL(rbf::rbs_find_seed_kernel, dim3(1), dim3(rbf::kSeedThreads), 0, st, f->d_coarse, f->crows, f->ccols,
-                       p.seed_stride, p.min_depth, p.max_depth, p.max_seeds, f->d_cells, f->d_seeds, f->d_info);
+    rbf::launch_subsample(st, f->d_full, s->cols, f->d_coarse, f->crows, f->ccols, f->f);
+    rbf::launch_seeds(st, f->d_coarse, f->crows, f->ccols, p.seed_stride, p.min_depth, p.max_depth, p.max_seeds, f->d_cells, f->d_seeds,
+                      f->d_info);
     RBF_HIP(f, hipGetLastError());
     RBF_RC(f, f->coarse, rbs_set_observation_device(f->coarse, f->d_coarse, st));
     RBF_RC(f, f->full, rbs_set_observation_device(f->full, f->d_full, st));
@@ -655,7 +731,7 @@ int32_t rbs_find_run(rbs_find* f, const float* frame, int32_t k, double* poses, 
     const rbf::HypParams HP = hyp_params(f);
     for (long h0 = 0; h0 < f->n_hyp; h0 += p.batch) {
         const int nb = (int)std::min<long>(p.batch, f->n_hyp - h0);
-        hipLaunchKernelGGL(rbf::rbs_find_hyp_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, HP, h0, nb, f->d_hyp);
+        rbf::launch_hyp(st, HP, h0, nb, f->d_hyp);
         RBF_HIP(f, hipGetLastError());
         RBF_RC(f, f->coarse, rbs_loglikes_device(f->coarse, f->d_hyp, f->d_zero, nb, 0, f->d_score + h0, st));
     }
@@ -664,15 +740,12 @@ int32_t rbs_find_run(rbs_find* f, const float* frame, int32_t k, double* poses, 
     const int nc = (int)std::min<long>(p.n_candidates, f->n_hyp);
     const double* ts;
     const long long* ti;
-    if (int32_t rc = launch_topk(f, f->d_score, nullptr, f->n_hyp, nc, &ts, &ti)) return rc;
+    if (int32_t rc = find_topk(f, f->d_score, nullptr, f->n_hyp, nc, &ts, &ti)) return rc;
     RBF_HIP(f, hipMemcpyAsync(f->d_cand_score, ts, sizeof(double) * nc, hipMemcpyDeviceToDevice, st));
     RBF_HIP(f, hipMemcpyAsync(f->d_cand_idx, ti, sizeof(long long) * nc, hipMemcpyDeviceToDevice, st));
-    hipLaunchKernelGGL(rbf::rbs_find_gather_kernel, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, st, HP, f->d_cand_idx, nc,
-                       f->d_cand_pose);
-    hipLaunchKernelGGL(rbf::rbs_find_nms_kernel, dim3(1), dim3(64), 0, st, f->d_cand_pose, f->d_cand_score, nc,
-                       p.nms_translation * p.nms_translation, f->trace_min, p.n_survivors, f->d_kept, f->d_info + 2);
-    hipLaunchKernelGGL(rbf::rbs_find_keep_kernel, dim3(1), dim3(64), 0, st, f->d_cand_pose, f->d_cand_score, f->d_cand_idx, f->d_kept,
-                       f->d_info + 2, f->d_surv0, f->d_surv0_score, f->d_surv0_idx);
+    rbf::launch_gather(st, HP, f->d_cand_idx, nc, f->d_cand_pose);
+    rbf::launch_nms_keep(st, f->d_cand_pose, f->d_cand_score, f->d_cand_idx, nc, f->t2, f->trace_min, p.n_survivors, f->d_kept,
+                         f->d_info + 2, f->d_surv0, f->d_surv0_score, f->d_surv0_idx);
     RBF_HIP(f, hipGetLastError());
     RBF_HIP(f, hipMemcpyAsync(f->h_info + 2, f->d_info + 2, sizeof(int), hipMemcpyDeviceToHost, st));
     RBF_HIP(f, hipEventRecord(f->ev[3], st));
@@ -695,12 +768,10 @@ int32_t rbs_find_run(rbs_find* f, const float* frame, int32_t k, double* poses, 
         for (int r = 0; r < p.rounds; ++r) {
             double* cp = f->d_child + (size_t)r * 12 * S * p.children;
             double* cs = f->d_child_score + (size_t)r * S * p.children;
-            hipLaunchKernelGGL(rbf::rbs_find_children_kernel, dim3((unsigned)((nch + 255) / 256)), dim3(256), 0, st, f->d_surv, S,
-                               p.children, r, (unsigned long long)p.seed, st_r, sa_r, cp);
+            rbf::launch_children(st, f->d_surv, S, p.children, r, (unsigned long long)p.seed, st_r, sa_r, cp);
             RBF_HIP(f, hipGetLastError());
             RBF_RC(f, f->full, rbs_loglikes_device(f->full, cp, f->d_zero, nch, 0, cs, st));
-            hipLaunchKernelGGL(rbf::rbs_find_select_kernel, dim3((unsigned)((S + 63) / 64)), dim3(64), 0, st, cp, cs, S, p.children,
-                               f->d_surv, f->d_surv_score);
+            rbf::launch_select(st, cp, cs, S, p.children, f->d_surv, f->d_surv_score);
             RBF_HIP(f, hipGetLastError());
             st_r *= p.decay;
             sa_r *= p.decay;
@@ -710,10 +781,9 @@ int32_t rbs_find_run(rbs_find* f, const float* frame, int32_t k, double* poses, 
         }
         const double* fs;
         const long long* fi;
-        if (int32_t rc = launch_topk(f, f->d_surv_score, nullptr, S, S, &fs, &fi)) return rc;
+        if (int32_t rc = find_topk(f, f->d_surv_score, nullptr, S, S, &fs, &fi)) return rc;
         RBF_HIP(f, hipMemcpyAsync(f->d_final_idx, fi, sizeof(long long) * S, hipMemcpyDeviceToDevice, st));
-        hipLaunchKernelGGL(rbf::rbs_find_order_kernel, dim3(1), dim3(64), 0, st, f->d_surv, f->d_surv_score, f->d_final_idx, S,
-                           f->d_final, f->d_final_score);
+        rbf::launch_order(st, f->d_surv, f->d_surv_score, f->d_final_idx, S, f->d_final, f->d_final_score);
         RBF_HIP(f, hipGetLastError());
     }
     RBF_HIP(f, hipEventRecord(f->ev[4], st));
@@ -765,7 +835,7 @@ int32_t rbs_find_get_stage(rbs_find* f, int32_t stage, int32_t round, double* po
                 const rbf::HypParams HP = hyp_params(f);
                 for (long h0 = 0; h0 < f->n_hyp; h0 += f->p.batch) {
                     const int nb = (int)std::min<long>(f->p.batch, f->n_hyp - h0);
-                    hipLaunchKernelGGL(rbf::rbs_find_hyp_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, f->st, HP, h0, nb, f->d_hyp);
+                    rbf::launch_hyp(f->st, HP, h0, nb, f->d_hyp);
                     RBF_HIP(f, hipGetLastError());
                     RBF_HIP(f, hipMemcpyAsync(poses + (size_t)h0 * 12, f->d_hyp, sizeof(double) * 12 * nb, hipMemcpyDeviceToHost, f->st));
                 }

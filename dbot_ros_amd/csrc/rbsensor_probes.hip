@@ -12,6 +12,11 @@
 // (rbsensor_capi.hip: no kernel body and no launch geometry is restated here), and hands every array back:
 // tests/test_gpu_filter_kernels.py.
 //
+// rbs_test_find_* do the same for the object finder's kernels (rbsensor_find.hip), one entry point per launch helper
+// (rbf::launch_*, the ones rbs_find_run itself calls): tests/test_gpu_finder_kernels.py.  Every output array there is IN and
+// OUT and `tail` elements (rows) longer than the kernel may write: the caller fills it with a sentinel, the probe copies it to
+// the device before the launch and back after it, so what the kernel left alone -- the tail included -- is seen.
+//
 // Entry points (rbs_test_*): host arrays in, host arrays out, synchronous on the current device.  Null pointers and n < 0 (or
 // n > kProbeMax) are RBS_ERR_INVALID_ARGUMENT, n == 0 is RBS_OK and touches nothing, a HIP failure is RBS_ERR_HIP.
 namespace rbs {
@@ -406,3 +411,218 @@ extern "C" int32_t rbs_test_filter(const rbs_test_filter_io* io, const rbs_test_
     if (h_flags) (void)hipHostFree(h_flags);
     return B.status();
 }
+
+// ---------------------------------------------------------------------------- the object finder's kernels
+extern "C" {
+
+// dst [(rows / f) * (cols / f) + tail]
+int32_t rbs_test_find_subsample(const float* src, int32_t rows, int32_t cols, int32_t f, float* dst, int64_t tail)
+{
+    namespace pr = rbs::probe;
+    if (!src || !dst || rows < 0 || cols < 0 || f < 1 || tail < 0 || pr::probe_refused((int64_t)rows * cols) || pr::probe_refused(tail))
+        return RBS_ERR_INVALID_ARGUMENT;
+    const int cr = rows / f, cc = cols / f;
+    if ((int64_t)cr * cc == 0) return RBS_OK;
+    const size_t n = (size_t)rows * cols, m = (size_t)cr * cc + (size_t)tail;
+    pr::Buffers B;
+    const float* dsrc = B.make<float>(n, src);
+    float* ddst = B.make<float>(m, dst);
+    if (B.err == hipSuccess) { rbf::launch_subsample(nullptr, dsrc, cols, ddst, cr, cc, f); B.ran(); }
+    B.fetch(dst, ddst, m);
+    return B.status();
+}
+
+// cells [ceil(rows / stride) * ceil(cols / stride) + tail], seeds [min(max_seeds, cells) + tail][4], info [2 + tail]
+int32_t rbs_test_find_seeds(const float* frame, int32_t rows, int32_t cols, int32_t stride, double dmin, double dmax, int32_t max_seeds,
+                            int32_t* cells, double* seeds, int32_t* info, int64_t tail)
+{
+    namespace pr = rbs::probe;
+    if (!frame || !cells || !seeds || !info || rows < 0 || cols < 0 || stride < 1 || max_seeds < 1 || tail < 0 ||
+        pr::probe_refused((int64_t)rows * cols) || pr::probe_refused(tail))
+        return RBS_ERR_INVALID_ARGUMENT;
+    if ((int64_t)rows * cols == 0) return RBS_OK;
+    const size_t n = (size_t)rows * cols, nc = rbf::seed_cells(rows, cols, stride), ns = std::min<size_t>((size_t)max_seeds, nc);
+    pr::Buffers B;
+    const float* dframe = B.make<float>(n, frame);
+    int* dcells = B.make<int>(nc + (size_t)tail, cells);
+    double* dseeds = B.make<double>(4 * (ns + (size_t)tail), seeds);
+    int* dinfo = B.make<int>(2 + (size_t)tail, info);
+    if (B.err == hipSuccess) { rbf::launch_seeds(nullptr, dframe, rows, cols, stride, dmin, dmax, max_seeds, dcells, dseeds, dinfo); B.ran(); }
+    B.fetch(cells, dcells, nc + (size_t)tail);
+    B.fetch(seeds, dseeds, 4 * (ns + (size_t)tail));
+    B.fetch(info, dinfo, 2 + (size_t)tail);
+    return B.status();
+}
+
+// idx == NULL: rbs_find_hyp_kernel over hypotheses h0 .. h0 + n - 1; else rbs_find_gather_kernel over idx [n].  Every
+// hypothesis must lie in [0, n_seeds * n_rot).  poses [n + tail][12]
+int32_t rbs_test_find_hyp(const double* seeds, int32_t n_seeds, int32_t n_rot, double fx, double fy, double cx, double cy, double offset,
+                          int64_t h0, const int64_t* idx, int32_t n, double* poses, int64_t tail)
+{
+    namespace pr = rbs::probe;
+    if (!seeds || !poses || n_seeds < 1 || n_rot < 1 || n < 0 || tail < 0 || pr::probe_refused(n) || pr::probe_refused(tail))
+        return RBS_ERR_INVALID_ARGUMENT;
+    const int64_t H = (int64_t)n_seeds * n_rot;
+    if (idx) {
+        for (int32_t i = 0; i < n; ++i)
+            if (idx[i] < 0 || idx[i] >= H) return RBS_ERR_INVALID_ARGUMENT;
+    } else if (h0 < 0 || h0 + n > H) {
+        return RBS_ERR_INVALID_ARGUMENT;
+    }
+    if (n == 0) return RBS_OK;
+    const size_t m = 12 * ((size_t)n + (size_t)tail);
+    pr::Buffers B;
+    rbf::HypParams HP;
+    HP.seeds = B.make<double>(4 * (size_t)n_seeds, seeds);
+    HP.n_rot = n_rot;
+    HP.fx = fx; HP.fy = fy; HP.cx = cx; HP.cy = cy;
+    HP.offset = offset;
+    const long long* didx = idx ? B.make<long long>((size_t)n, reinterpret_cast<const long long*>(idx)) : nullptr;
+    double* dposes = B.make<double>(m, poses);
+    if (B.err == hipSuccess) {
+        if (idx) rbf::launch_gather(nullptr, HP, didx, n, dposes);
+        else rbf::launch_hyp(nullptr, HP, (long)h0, n, dposes);
+        B.ran();
+    }
+    B.fetch(poses, dposes, m);
+    return B.status();
+}
+
+// The best k of (score, idx) [n] (idx may be NULL: positions) through rbf::launch_topk's own loop of passes, its ping-pong
+// buffers rbf::topk_items(n, k) + tail items each; tail_s / tail_i [2][tail]: those buffers' tails, in and out.
+// out_score / out_idx [k]; *passes (may be NULL) := the launches it took.
+int32_t rbs_test_find_topk(const double* score, const int64_t* idx, int64_t n, int32_t k, double* out_score, int64_t* out_idx,
+                           double* tail_s, int64_t* tail_i, int64_t tail, int32_t* passes)
+{
+    namespace pr = rbs::probe;
+    if (!score || !out_score || !out_idx || !tail_s || !tail_i || k < 1 || k > rbf::kMaxCandidates || tail < 0 || pr::probe_refused(n) ||
+        pr::probe_refused(tail))
+        return RBS_ERR_INVALID_ARGUMENT;
+    if (n == 0) return RBS_OK;
+    const size_t cap = rbf::topk_items(n, k), T = (size_t)tail;
+    pr::Buffers B;
+    const double* dscore = B.make<double>((size_t)n, score);
+    const long long* didx = idx ? B.make<long long>((size_t)n, reinterpret_cast<const long long*>(idx)) : nullptr;
+    double* tk_s[2] = {B.make<double>(cap + T), B.make<double>(cap + T)};
+    long long* tk_i[2] = {B.make<long long>(cap + T), B.make<long long>(cap + T)};
+    for (int b = 0; b < 2 && T > 0; ++b) {
+        if (B.err == hipSuccess) B.err = hipMemcpy(tk_s[b] + cap, tail_s + b * T, sizeof(double) * T, hipMemcpyHostToDevice);
+        if (B.err == hipSuccess) B.err = hipMemcpy(tk_i[b] + cap, tail_i + b * T, sizeof(long long) * T, hipMemcpyHostToDevice);
+    }
+    const double* rs = nullptr;
+    const long long* ri = nullptr;
+    if (B.err == hipSuccess) { B.err = rbf::launch_topk(nullptr, dscore, didx, (long)n, k, tk_s, tk_i, &rs, &ri); B.ran(); }
+    if (B.err == hipSuccess) {
+        B.fetch(out_score, rs, (size_t)k);
+        B.fetch(reinterpret_cast<long long*>(out_idx), ri, (size_t)k);
+        for (int b = 0; b < 2 && T > 0; ++b) {
+            B.fetch(tail_s + b * T, tk_s[b] + cap, T);
+            B.fetch(reinterpret_cast<long long*>(tail_i) + b * T, tk_i[b] + cap, T);
+        }
+        if (passes) {
+            int32_t np = 0;
+            for (long m = (long)n;;) { const long blocks = (m + rbf::kTopC - 1) / rbf::kTopC; ++np; if (blocks == 1) break; m = blocks * k; }
+            *passes = np;
+        }
+    }
+    return B.status();
+}
+
+// The suppression and the keep kernel over candidates [n] in order, the thresholds from (nms_translation, nms_angle) as
+// rbs_find_create derives them.  kept [64 + tail], count [1 + tail], surv [max_keep + tail][12], surv_score / surv_idx
+// [max_keep + tail]
+int32_t rbs_test_find_nms(const double* poses, const double* score, const int64_t* idx, int32_t n, double nms_translation, double nms_angle,
+                          int32_t max_keep, int32_t* kept, int32_t* count, double* surv, double* surv_score, int64_t* surv_idx, int64_t tail)
+{
+    namespace pr = rbs::probe;
+    if (!poses || !score || !idx || !kept || !count || !surv || !surv_score || !surv_idx || n < 0 || max_keep < 1 ||
+        max_keep > rbf::kMaxSurvivors || tail < 0 || pr::probe_refused(n) || pr::probe_refused(tail))
+        return RBS_ERR_INVALID_ARGUMENT;
+    if (n == 0) return RBS_OK;
+    const size_t T = (size_t)tail, K = (size_t)max_keep + T;
+    double t2, trace_min;
+    rbf::nms_thresholds(nms_translation, nms_angle, &t2, &trace_min);
+    pr::Buffers B;
+    const double* dposes = B.make<double>(12 * (size_t)n, poses);
+    const double* dscore = B.make<double>((size_t)n, score);
+    const long long* didx = B.make<long long>((size_t)n, reinterpret_cast<const long long*>(idx));
+    int* dkept = B.make<int>(rbf::kMaxSurvivors + T, kept);
+    int* dcount = B.make<int>(1 + T, count);
+    double* dsurv = B.make<double>(12 * K, surv);
+    double* dsurv_score = B.make<double>(K, surv_score);
+    long long* dsurv_idx = B.make<long long>(K, reinterpret_cast<const long long*>(surv_idx));
+    if (B.err == hipSuccess) {
+        rbf::launch_nms_keep(nullptr, dposes, dscore, didx, n, t2, trace_min, max_keep, dkept, dcount, dsurv, dsurv_score, dsurv_idx);
+        B.ran();
+    }
+    B.fetch(kept, dkept, rbf::kMaxSurvivors + T);
+    B.fetch(count, dcount, 1 + T);
+    B.fetch(surv, dsurv, 12 * K);
+    B.fetch(surv_score, dsurv_score, K);
+    B.fetch(reinterpret_cast<long long*>(surv_idx), dsurv_idx, K);
+    return B.status();
+}
+
+// out [S * children + tail][12]
+int32_t rbs_test_find_children(const double* surv, int32_t S, int32_t children, int32_t round, uint64_t seed, double sigma_t, double sigma_a,
+                               double* out, int64_t tail)
+{
+    namespace pr = rbs::probe;
+    if (!surv || !out || S < 0 || S > rbf::kMaxSurvivors || children < 1 || children > 4096 || round < 0 || round > 63 || tail < 0 ||
+        pr::probe_refused(tail))
+        return RBS_ERR_INVALID_ARGUMENT;
+    if (S == 0) return RBS_OK;
+    const size_t m = 12 * ((size_t)S * children + (size_t)tail);
+    pr::Buffers B;
+    const double* dsurv = B.make<double>(12 * (size_t)S, surv);
+    double* dout = B.make<double>(m, out);
+    if (B.err == hipSuccess) { rbf::launch_children(nullptr, dsurv, S, children, round, (unsigned long long)seed, sigma_t, sigma_a, dout); B.ran(); }
+    B.fetch(out, dout, m);
+    return B.status();
+}
+
+// child [S * children][12], child_score [S * children] -> surv [S + tail][12], surv_score [S + tail]
+int32_t rbs_test_find_select(const double* child, const double* child_score, int32_t S, int32_t children, double* surv, double* surv_score,
+                             int64_t tail)
+{
+    namespace pr = rbs::probe;
+    if (!child || !child_score || !surv || !surv_score || S < 0 || S > rbf::kMaxSurvivors || children < 1 || children > 4096 || tail < 0 ||
+        pr::probe_refused(tail))
+        return RBS_ERR_INVALID_ARGUMENT;
+    if (S == 0) return RBS_OK;
+    const size_t nch = (size_t)S * children, K = (size_t)S + (size_t)tail;
+    pr::Buffers B;
+    const double* dchild = B.make<double>(12 * nch, child);
+    const double* dscore = B.make<double>(nch, child_score);
+    double* dsurv = B.make<double>(12 * K, surv);
+    double* dsurv_score = B.make<double>(K, surv_score);
+    if (B.err == hipSuccess) { rbf::launch_select(nullptr, dchild, dscore, S, children, dsurv, dsurv_score); B.ran(); }
+    B.fetch(surv, dsurv, 12 * K);
+    B.fetch(surv_score, dsurv_score, K);
+    return B.status();
+}
+
+// surv [S][12], surv_score [S], order [S] (each in 0 .. S - 1) -> out_pose [S + tail][12], out_score [S + tail]
+int32_t rbs_test_find_order(const double* surv, const double* surv_score, const int64_t* order, int32_t S, double* out_pose, double* out_score,
+                            int64_t tail)
+{
+    namespace pr = rbs::probe;
+    if (!surv || !surv_score || !order || !out_pose || !out_score || S < 0 || S > rbf::kMaxSurvivors || tail < 0 || pr::probe_refused(tail))
+        return RBS_ERR_INVALID_ARGUMENT;
+    for (int32_t i = 0; i < S; ++i)
+        if (order[i] < 0 || order[i] >= S) return RBS_ERR_INVALID_ARGUMENT;
+    if (S == 0) return RBS_OK;
+    const size_t K = (size_t)S + (size_t)tail;
+    pr::Buffers B;
+    const double* dsurv = B.make<double>(12 * (size_t)S, surv);
+    const double* dscore = B.make<double>((size_t)S, surv_score);
+    const long long* dorder = B.make<long long>((size_t)S, reinterpret_cast<const long long*>(order));
+    double* dout = B.make<double>(12 * K, out_pose);
+    double* dout_score = B.make<double>(K, out_score);
+    if (B.err == hipSuccess) { rbf::launch_order(nullptr, dsurv, dscore, dorder, S, dout, dout_score); B.ran(); }
+    B.fetch(out_pose, dout, 12 * K);
+    B.fetch(out_score, dout_score, K);
+    return B.status();
+}
+
+}  // extern "C"

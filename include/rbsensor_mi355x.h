@@ -669,8 +669,11 @@ int32_t rbs_gauss_result(rbs_gauss* g, double* out_state, double* out_cov);
  *                   vector v, and (n, n') six standard normals: Box-Muller pairs p = 0, 1, 2 of Philox4x32-10
  *                   (key = seed, counter = (j << 2 | p, round << 32 | k)), u1 = 1 - u01(x, y), u2 = u01(z, w),
  *                   n_2p = sqrt(-2 log u1) cos(2 pi u2), n_2p+1 = ... sin(...).  A survivor keeps its best child,
- *                   ties to the lowest j, NaN never beats a number, so its score never goes down.  The survivors
- *                   are then sorted as in step 5 (by survivor index on ties).
+ *                   ties to the lowest j, NaN never beats a number, so its score never goes down.  A survivor whose
+ *                   children ALL score NaN (child 0, itself, included) stays as it is, with a NaN score.  The survivors
+ *                   are then sorted in step 5's order (by survivor index on ties); none is dropped here: those with a
+ *                   NaN score come last, in survivor order, so poses [i] may carry scores [i] = NaN at the end, and
+ *                   found is 0 when even the best score is NaN.
  *   7 output        the k <= n_survivors best poses [k][12] (R row-major | t, the sensor's mesh frame) and their
  *                   scores; found = (best score >= min_score).  A frame without a valid seed: RBS_OK, found = 0,
  *                   *n_out = 0.

@@ -223,6 +223,7 @@ def test_release_library_carries_no_fault_injection_hook():
     """RBS_TEST_FAULT is read by the test build (librbsensor_mi355x_hooks.so, -DRBS_TEST_HOOKS) only.  So are the per-pixel
     likelihood's probes (rbsensor_probes.hip, tests/test_gpu_pixel_math.py): the hooks build exports every one, the release build none."""
     from filter_probes import FILTER_SYMBOLS
+    from find_probes import FIND_SYMBOLS
     from pixel_probes import PROBE_SYMBOLS
     lib = os.path.join(ROOT, "dbot_ros_amd", "lib")
     release = open(os.path.join(lib, "librbsensor_mi355x.so"), "rb").read()
@@ -234,8 +235,9 @@ def test_release_library_carries_no_fault_injection_hook():
     assert len(PROBE_SYMBOLS) == 8
     assert b"rbs_test_" not in release and b"rbs5probe" not in release        # no entry point, no probe kernel (rbs::probe::*)
     assert FILTER_SYMBOLS == ("rbs_test_filter",)                             # the particle filter's probe (tests/test_gpu_filter_kernels.py)
-    for s in PROBE_SYMBOLS + FILTER_SYMBOLS:
+    assert len(FIND_SYMBOLS) == 8 and all(s.startswith("rbs_test_find_") for s in FIND_SYMBOLS)   # the object finder's (tests/test_gpu_finder_kernels.py)
+    for s in PROBE_SYMBOLS + FILTER_SYMBOLS + FIND_SYMBOLS:
         assert s.encode() + b"\0" in test_build, s                            # (a name in the dynamic symbol table)
         assert s.encode() not in release, s
     exported = C.CDLL(hooks) if os.path.abspath(_capi.LIB_PATH) == os.path.abspath(hooks) else None
-    assert exported is None or all(hasattr(exported, s) for s in PROBE_SYMBOLS + FILTER_SYMBOLS)
+    assert exported is None or all(hasattr(exported, s) for s in PROBE_SYMBOLS + FILTER_SYMBOLS + FIND_SYMBOLS)

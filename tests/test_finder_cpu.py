@@ -88,6 +88,93 @@ def test_perturbation_formula():
     assert tw.best_child(np.array([[1.0, 2.0, 2.0], [np.nan, np.nan, 0.5], [3.0, np.nan, 3.0]])).tolist() == [1, 2, 0]
 
 
+def _before(a, b):
+    """rbs_find_topk_kernel's `before`: larger score first, NaN last, then smaller index."""
+    (sa, ia), (sb, ib) = a, b
+    na, nb = sa != sa, sb != sb
+    if na != nb:
+        return nb
+    if not na and sa != sb:
+        return sa > sb
+    return ia < ib
+
+
+def test_topk_is_a_sort_by_the_kernels_order():
+    import functools
+    rng = np.random.default_rng(2)
+    values = np.array([np.nan, -np.inf, np.inf, -0.0, 0.0, 1.0, 1.0 + 2.0 ** -52, -3.5])
+    for n in (1, 2, 5, 64, 300):
+        for index in (None, rng.permutation(n).astype(np.int64) * 5 + (1 << 31)):
+            s = rng.choice(values, n)
+            items = list(zip(s.tolist(), (range(n) if index is None else index.tolist())))
+            ref = sorted(items, key=functools.cmp_to_key(lambda a, b: -1 if _before(a, b) else 1 if _before(b, a) else 0))
+            for k in (1, n, n + 3):
+                ts, ti = tw.topk(s, index, k)
+                want = ref[:k] + [(math.nan, tw.INT64_MAX)] * max(0, k - n)
+                assert ti.tolist() == [i for _, i in want], (n, k)
+                ws = np.array([v for v, _ in want])
+                assert np.array_equal(np.isnan(ts), np.isnan(ws)) and np.array_equal(np.signbit(ts), np.signbit(ws))
+                assert np.array_equal(ts[~np.isnan(ts)], ws[~np.isnan(ws)])
+    # NaN items stay, in index order at the end; select_order drops them; the final sort keeps them
+    s = np.array([1.0, np.nan, 3.0, 3.0, np.nan, -np.inf])
+    assert tw.topk(s)[1].tolist() == [2, 3, 0, 5, 1, 4] and tw.result_order(s).tolist() == [2, 3, 0, 5, 1, 4]
+    assert tw.select_order(s).tolist() == [2, 3, 0, 5]
+
+
+def test_philox_reproduces_the_random123_known_answers():
+    from test_filter_twin_cpu import KNOWN_ANSWERS, _words
+    for ctr, key, out in KNOWN_ANSWERS:
+        c, k = _words(ctr), _words(key)
+        assert tw.philox(k[1] << 32 | k[0], c[3] << 32 | c[2], c[1] << 32 | c[0]) == _words(out)
+    # the finder's counter: (round << 32 | k) above (j << 2 | pair); the array form draws the integer form's normals
+    nz = tw.child_normals_array(0xC0FFEE1234ABCDEF, 63, 3, 70)
+    for k, j in ((0, 1), (2, 69), (1, 33)):
+        np.testing.assert_allclose(nz[k, j], tw.child_normals(0xC0FFEE1234ABCDEF, 63, k, j), rtol=0, atol=4e-15)
+    assert not np.allclose(tw.child_normals(5, 1, 2, 3), tw.child_normals(5, 2, 1, 3))
+
+
+def test_extended_precision_twin_against_the_binary64_one():
+    """The extended evaluation (mpmath where installed, long double otherwise) and the binary64 one are the same formulas: they
+    agree to the binary64 one's rounding, and the two extended back ends agree to long double's."""
+    rng = np.random.default_rng(4)
+    idx = np.array([0, 1, 63, 64, 127])
+    for use_mp in (True, False):
+        R = tw.sf_rotations_ext(128, idx, use_mpmath=use_mp)
+        assert R.dtype == np.longdouble and np.abs(R - tw.sf_rotations(128)[idx]).max() < 2e-13
+    assert np.abs(tw.sf_rotations_ext(128, idx) - tw.sf_rotations_ext(128, idx, use_mpmath=False)).max() < 1e-16
+    # at 2^20 rotations the angles reach 4.7e6 rad: the binary64 path is 1e-9 off, not 1e-15
+    big = np.array([0, (1 << 20) - 1])
+    err = np.abs(tw.sf_rotations_ext(1 << 20, big) - tw.sf_rotations(1 << 20)[big]).max()
+    assert err < 4e-9, err
+    seeds = np.stack([rng.integers(0, 160, 9), rng.integers(0, 120, 9), rng.uniform(0.3, 2.0, 9), np.zeros(9)], -1).astype(np.float64)
+    K = tw.coarse_K(np.array([[570.3, 0, 159.5], [0, 570.3, 119.5], [0, 0, 1.0]]), 2)
+    h = np.array([0, 7, 8, 71])
+    ext = tw.hypotheses_ext(seeds, 8, K, 0.05, h)
+    # (the angles reach 33 rad at 8 rotations: three roundings of one are 1e-14 rad)
+    assert np.abs(ext - tw.hypotheses(seeds, 8, K, 0.05, h)).max() < 5e-14
+    assert np.abs(ext[:, 9:] - tw.hypotheses(seeds, 8, K, 0.05, h)[:, 9:]).max() < 1e-15
+    surv = tw.hypotheses(seeds, 8, K, 0.05, h)
+    ch = tw.children(surv, 5, 3, 77, 0.01, 0.2)
+    for use_mp in (True, False):
+        ext = tw.children_ext(surv, 5, 3, 77, 0.01, 0.2, use_mpmath=use_mp).reshape(4, 5, 12)
+        assert np.abs(ext - ch).max() < 1e-14
+        assert np.array_equal(ext[:, 0], surv.astype(np.longdouble))
+    assert np.abs(tw.children_array(surv, 5, 3, 77, 0.01, 0.2) - ch).max() < 1e-14
+    assert np.abs(tw.child_normals_ext(77, 3, 1, 2) - tw.child_normals(77, 3, 1, 2)).max() < 1e-14
+
+
+def test_suppression_stops_at_a_nan_score_and_best_child_rules():
+    poses = np.zeros((4, 12))
+    poses[:, [0, 4, 8]] = 1.0
+    poses[:, 9] = [0.0, 1.0, 2.0, 3.0]
+    assert tw.nms(poses, 0.02, 0.5, 10) == [0, 1, 2, 3]
+    assert tw.nms(poses, 0.02, 0.5, 10, np.array([3.0, 2.0, np.nan, 1.0])) == [0, 1]
+    assert tw.nms(poses, 0.02, 0.5, 10, np.array([np.nan, 2.0, 1.0, 0.0])) == []
+    nan, ninf = np.nan, -np.inf
+    rows = np.array([[nan, nan, nan], [nan, ninf, ninf], [ninf, nan, 1.0], [ninf, ninf, ninf], [nan, 2.0, 2.0], [np.inf, nan, np.inf]])
+    assert tw.best_child(rows).tolist() == [0, 1, 2, 0, 1, 0]
+
+
 def test_finder_kernels_do_not_spill():
     txt = open(os.path.join(ROOT, "dbot_ros_amd", "lib", "resource_usage.txt")).read()
     blocks = re.split(r"remark: Function Name: ", txt)[1:]

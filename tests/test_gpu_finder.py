@@ -299,3 +299,135 @@ def test_errors_and_min_score(gpu_lib):
         with pytest.raises(RbSensorError) as e:
             ObjectFinder(s2, om2)
         assert e.value.code == _capi.RBS_ERR_UNSUPPORTED
+
+
+# ---------------------------------------------------------------- the other routes of rbs_find_run
+TINY = dict(max_seeds=16, n_rotations=32, n_candidates=64, n_survivors=8, rounds=2, children=8, batch=256)
+
+
+def _one_pixel(frame, cam, stride=4):
+    """The frame with every pixel NaN but the valid seed-grid pixel nearest the image centre."""
+    img = np.asarray(frame, dtype=np.float32).reshape(cam.rows, cam.cols)
+    vv, uu = np.meshgrid(np.arange(0, cam.rows, stride), np.arange(0, cam.cols, stride), indexing="ij")
+    ok = np.isfinite(img[vv, uu]) & (img[vv, uu] >= 0.2) & (img[vv, uu] <= 3.0)
+    dist = np.where(ok, (vv - cam.rows / 2) ** 2 + (uu - cam.cols / 2) ** 2, np.inf)
+    q = np.unravel_index(np.argmin(dist), dist.shape)
+    out = np.full_like(img, np.nan)
+    out[vv[q], uu[q]] = img[vv[q], uu[q]]
+    return out.ravel()
+
+
+def _assert_same_find(a, b):
+    assert a.found == b.found
+    np.testing.assert_array_equal(a.poses, b.poses)
+    np.testing.assert_array_equal(a.scores, b.scores)
+
+
+def test_no_valid_depth_then_a_good_frame(gpu_lib):
+    om, cam, P, sensor, truth, frame = _scene("m1_l2", 160, 120, seed=4)
+    p = _params(**TINY)
+    with sensor:
+        with ObjectFinder(sensor, om, p) as fresh:
+            want = fresh.find(frame)
+            assert want.found and len(want.poses) > 0
+        with ObjectFinder(sensor, om, p) as fnd:
+            for empty in (np.full(cam.rows * cam.cols, np.nan, dtype=np.float32),
+                          np.full(cam.rows * cam.cols, np.nextafter(np.float32(p.max_depth), np.float32(9)), dtype=np.float32)):
+                r = fnd.find(empty)
+                assert not r.found and len(r.poses) == 0 and len(r.scores) == 0 and len(r.states) == 0
+                for st in ("seeds", "coarse", "candidates", "survivors", "children", "result"):
+                    sp, ss, si, info = fnd.stage(st)
+                    assert len(sp) == len(ss) == len(si) == 0 and info[3] == 0 and info[4] == 0, st
+                _assert_same_find(fnd.find(frame), want)      # the bits of a fresh finder
+
+
+@pytest.mark.parametrize("rounds", [0, 1])
+def test_one_seed_one_rotation_one_survivor(gpu_lib, rounds):
+    """Every count 1 on a frame with one valid seed pixel; rounds = 0 is the route that scores the survivors once."""
+    om, cam, P, sensor, truth, frame = _scene("m1_l2", 160, 120, seed=4)
+    lone = _one_pixel(frame, cam)
+    p = _params(max_seeds=1, n_rotations=1, n_candidates=1, n_survivors=1, children=1, rounds=rounds, batch=64)
+    with sensor, ObjectFinder(sensor, om, p) as fnd:
+        r = fnd.find(lone)
+        seeds, _, _, info = fnd.stage("seeds")
+        assert len(seeds) == 1 and info[4] == 1 and info[2] == 1 and r.found and len(r.poses) == 1
+        want = tw.hypotheses(seeds, 1, tw.coarse_K(cam.camera_matrix, 1), info[5])
+        np.testing.assert_allclose(r.poses, want, rtol=0, atol=1e-15)
+        ref = _reference_scores(om, cam.camera_matrix, cam.rows, cam.cols, P, lone, r.poses)
+        np.testing.assert_array_equal(r.scores, ref)
+        sp, ss, si, _ = fnd.stage("survivors")
+        np.testing.assert_array_equal(sp, r.poses)
+        assert si.tolist() == [0]
+        if rounds:
+            kp, ks, _, _ = fnd.stage("children", 0)
+            np.testing.assert_array_equal(kp, r.poses)
+            np.testing.assert_array_equal(ks, r.scores)
+
+
+@pytest.mark.parametrize("cols, rows, f", [(322, 241, 2), (322, 241, 4), (80, 60, 1)])
+def test_frames_the_coarse_factor_does_not_divide(gpu_lib, cols, rows, f):
+    om, cam, P, sensor, truth, frame = _scene("m1_l2", cols, rows, seed=6)
+    p = _params(**TINY, coarse_downsampling=f)
+    with sensor, ObjectFinder(sensor, om, p) as fnd:
+        fnd.find(frame)
+        seeds, _, _, info = fnd.stage("seeds")
+        coarse, cr, cc = tw.subsample(frame, rows, cols, f)
+        assert (cr, cc) == (rows // f, cols // f) and info[2] == f
+        tseeds, nvalid = tw.seeds(coarse, p.seed_stride, p.min_depth, p.max_depth, p.max_seeds)
+        assert (info[0], info[1], info[4]) == (cr, cc, nvalid) and nvalid > p.max_seeds
+        np.testing.assert_array_equal(seeds, tseeds)
+        hp, hs, hi, _ = fnd.stage("coarse")
+        assert len(hp) == len(tseeds) * p.n_rotations == info[3]
+        np.testing.assert_allclose(hp, tw.hypotheses(tseeds, p.n_rotations, tw.coarse_K(cam.camera_matrix, f), info[5]), rtol=0, atol=1e-15)
+        cp, cs, ci, _ = fnd.stage("candidates")
+        order = tw.select_order(hs)[: p.n_candidates]
+        np.testing.assert_array_equal(ci, order)
+        np.testing.assert_array_equal(cs, hs[order])
+        np.testing.assert_array_equal(cp, hp[order])
+
+
+def test_find_on_the_sensors_own_observation(gpu_lib):
+    om, cam, P, sensor, truth, frame = _scene("m1_l2", 160, 120, seed=4)
+    with sensor, ObjectFinder(sensor, om, _params(**TINY)) as fnd:
+        want = fnd.find(frame)
+        sensor.set_observation(np.asarray(frame, dtype=np.float32).ravel())
+        _assert_same_find(fnd.find(None), want)
+
+
+def test_fewer_survivors_on_the_second_find(gpu_lib):
+    """nms_angle pi: hypotheses of one seed suppress each other, so the one-pixel frame leaves one survivor where the
+    whole frame left eight; the second find's children are those of ITS survivors."""
+    om, cam, P, sensor, truth, frame = _scene("m1_l2", 160, 120, seed=4)
+    p = _params(**TINY, nms_angle=math.pi, nms_translation=0.005, seed=5)
+    with sensor, ObjectFinder(sensor, om, p) as fnd:
+        first = fnd.find(frame)
+        assert len(first.poses) == 8
+        second = fnd.find(_one_pixel(frame, cam))
+        sp, _, _, _ = fnd.stage("survivors")
+        S = len(sp)
+        assert S == len(second.poses) == 1
+        cur, st, sa = sp.copy(), p.sigma_translation, p.sigma_angle
+        for r in range(p.rounds):
+            kp, ks, ki, _ = fnd.stage("children", r)
+            assert len(kp) == len(ks) == S * p.children and ki.tolist() == list(range(S * p.children))
+            kp = kp.reshape(S, p.children, 12)
+            np.testing.assert_allclose(kp, tw.children(cur, p.children, r, p.seed, st, sa), rtol=0, atol=1e-14)
+            np.testing.assert_array_equal(kp[:, 0], cur)
+            cur = kp[np.arange(S), tw.best_child(ks.reshape(S, p.children))]
+            st, sa = st * p.decay, sa * p.decay
+        np.testing.assert_array_equal(second.poses, cur)
+
+
+def test_output_counts(gpu_lib):
+    om, cam, P, sensor, truth, frame = _scene("m1_l2", 160, 120, seed=4)
+    with sensor, ObjectFinder(sensor, om, _params(**TINY)) as fnd:
+        full = fnd.find(frame)
+        S = len(fnd.stage("survivors")[0])
+        assert len(full.poses) == S and full.found
+        none = fnd.find(frame, k=0)
+        assert none.found and len(none.poses) == 0 and len(none.scores) == 0
+        many = fnd.find(frame, k=S + 50)
+        _assert_same_find(many, full)
+        three = fnd.find(frame, k=min(3, S))
+        assert three.found
+        np.testing.assert_array_equal(three.poses, full.poses[: min(3, S)])
