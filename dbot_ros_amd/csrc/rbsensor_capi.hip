@@ -11,6 +11,7 @@
 #include "rbsensor_kernels.hip"
 #include "rbsensor_tracker.hip"
 #include "rbsensor_peers.hip"
+#include "rbs_mesh.h"
 
 #include "../../include/rbsensor_mi355x.h"
 
@@ -321,6 +322,18 @@ int32_t fail(rbs_handle* h, int32_t code, const std::string& msg)
     h->err = msg;
     return code;
 }
+
+// One host array to a new device allocation of at least min_count elements.
+template <class T>
+int32_t upload(rbs_handle* h, T** dst, const std::vector<T>& src, size_t min_count = 0)
+{
+    RBS_HIP(h, hipMalloc(dst, sizeof(T) * std::max(src.size(), min_count)));
+    RBS_HIP(h, hipMemcpy(*dst, src.data(), sizeof(T) * src.size(), hipMemcpyHostToDevice));
+    return RBS_OK;
+}
+
+static_assert(rbs::kMeshMaxBodies == rbs::kMaxBodies, "rbs_mesh.h keeps its own copy of the kernels' body limit");
+static_assert(rbs::kMeshOk == RBS_OK && rbs::kMeshInvalidArgument == RBS_ERR_INVALID_ARGUMENT, "rbs_mesh.h returns the C-ABI's codes");
 #define RBS_REFUSE_POISONED(h)                                                                \
     do {                                                                                      \
         if ((h)->poisoned)                                                                    \
@@ -1769,19 +1782,22 @@ int32_t create_impl(const rbs_config* cfg, rbs_handle* h)
     B.bands = copy_bands_for(h->rows, h->cols);
     B.band_rows = (h->rows + B.bands - 1) / B.bands;
 
-    // triangle soup (SoA) + bounding spheres.  Per body the triangles are ordered along a
-    // bisection of positions and normals (below) and padded to a multiple of 64 with NaN triangles, so
-    // that every aligned run of 64 is a compact surface patch ("cluster") one wave rasterizes.
-    long n_tri = 0;
-    B.tri_begin[0] = 0;
-    for (int b = 0; b < h->n_bodies; ++b) {
-        if (cfg->vertex_counts[b] <= 0 || cfg->triangle_counts[b] < 0)
-            return fail(h, RBS_ERR_INVALID_ARGUMENT, fmt("object %d: bad mesh counts", b));
-        n_tri += ((long)cfg->triangle_counts[b] + 63) / 64 * 64;
-        B.tri_begin[b + 1] = (int)n_tri;
+    // the meshes -> what the raster kernels read (rbs_mesh.h: host only, checked on a CPU by tests/test_mesh_prep_cpu.py)
+    rbs::PreparedMesh mesh;
+    {
+        const rbs::MeshInput in = {cfg->n_objects, cfg->vertices, cfg->vertex_counts, cfg->triangles, cfg->triangle_counts};
+        const bool allow_cull = !(std::getenv("RBS_NO_CULL") && std::atoi(std::getenv("RBS_NO_CULL")));
+        std::string why;
+        if (const int rc = rbs::prepare_mesh(in, allow_cull, &mesh, &why)) return fail(h, rc, why);
+        std::copy(std::begin(mesh.tri_begin), std::end(mesh.tri_begin), B.tri_begin);
+        std::copy(std::begin(mesh.tri_end), std::end(mesh.tri_end), B.tri_end);
+        std::copy(std::begin(mesh.vtx_begin), std::end(mesh.vtx_begin), B.vtx_begin);
+        for (int b = 0; b < h->n_bodies; ++b) {
+            B.body_cull[b] = mesh.body_cull[b];
+            std::copy(mesh.sphere[b], mesh.sphere[b] + 4, B.sphere[b]);
+        }
+        B.n_tri = (int)mesh.n_alloc;
     }
-    for (int b = h->n_bodies; b < rbs::kMaxBodies; ++b) B.tri_begin[b + 1] = (int)n_tri;
-    for (int b = 0; b < rbs::kMaxBodies; ++b) B.tri_end[b] = B.tri_begin[b];
     {   // (the object finder re-creates this configuration at other resolutions: keep it with copies of the mesh)
         size_t nv = 0, nt = 0;
         for (int b = 0; b < cfg->n_objects; ++b) { nv += (size_t)cfg->vertex_counts[b]; nt += (size_t)cfg->triangle_counts[b]; }
@@ -1797,245 +1813,8 @@ int32_t create_impl(const rbs_config* cfg, rbs_handle* h)
         h->cfg.n_devices = 0;
         h->cfg.device_ids = nullptr;
     }
-    for (int b = 0; b < h->n_bodies; ++b) {
-        const int clusters = (B.tri_begin[b + 1] - B.tri_begin[b]) >> 6;
-        h->many_clusters |= clusters > 64 * (rbs::kBlock / 64);   // (more steps of 64 clusters than the block has waves)
-    }
+    h->many_clusters |= mesh.max_clusters > 64 * (rbs::kBlock / 64);   // (more steps of 64 clusters than the block has waves)
     if (const char* e = std::getenv("RBS_SHARED_CULL")) h->many_clusters = std::atoi(e) != 0;   // (A/B: the other set of kernels)
-    if (n_tri > (1L << 30)) return fail(h, RBS_ERR_INVALID_ARGUMENT, "too many triangles");
-    B.n_tri = (int)n_tri;
-    const size_t n_alloc = (size_t)(n_tri > 0 ? n_tri : 64);
-    std::vector<double> soup((size_t)9 * n_alloc, std::nan(""));
-    std::vector<float> cluster_sphere(4 * (n_alloc / 64), 0.f);
-    std::vector<float> cluster_cone(4 * (n_alloc / 64), -2.f);   // min cos -2: never culled
-    std::vector<float> tri_plane(4 * n_alloc, std::nanf(""));    // NaN: never pre-culled
-    std::vector<double> cluster_vtx((size_t)192 * (n_alloc / 64), 0.0);
-    std::vector<int> cluster_nv(n_alloc / 64, 0);
-    std::vector<unsigned> tri_local(n_alloc, 0xffffffffu);
-    const bool allow_cull = !(std::getenv("RBS_NO_CULL") && std::atoi(std::getenv("RBS_NO_CULL")));
-    size_t voff = 0, toff = 0;
-    for (int b = 0; b < h->n_bodies; ++b) {
-        const int nv = cfg->vertex_counts[b], nt = cfg->triangle_counts[b];
-        const double* V = cfg->vertices + 3 * voff;
-        const int32_t* T = cfg->triangles + 3 * toff;
-        double lo[3] = {V[0], V[1], V[2]}, hi[3] = {V[0], V[1], V[2]};
-        for (int i = 0; i < nv; ++i)
-            for (int c3 = 0; c3 < 3; ++c3) {
-                const double x = V[3 * i + c3];
-                if (!std::isfinite(x))
-                    return fail(h, RBS_ERR_INVALID_ARGUMENT, fmt("object %d: non-finite vertex", b));
-                lo[c3] = std::fmin(lo[c3], x);
-                hi[c3] = std::fmax(hi[c3], x);
-            }
-        double ctr[3] = {0.5 * (lo[0] + hi[0]), 0.5 * (lo[1] + hi[1]), 0.5 * (lo[2] + hi[2])};
-        double r2 = 0.0;
-        for (int i = 0; i < nv; ++i) {
-            const double dx = V[3 * i] - ctr[0], dy = V[3 * i + 1] - ctr[1], dz = V[3 * i + 2] - ctr[2];
-            r2 = std::fmax(r2, dx * dx + dy * dy + dz * dz);
-        }
-        B.sphere[b][0] = ctr[0]; B.sphere[b][1] = ctr[1]; B.sphere[b][2] = ctr[2];
-        B.sphere[b][3] = std::sqrt(r2) * (1.0 + 1e-9) + 1e-12;
-        for (int t = 0; t < nt; ++t)
-            for (int k = 0; k < 3; ++k)
-                if (T[3 * t + k] < 0 || T[3 * t + k] >= nv)
-                    return fail(h, RBS_ERR_INVALID_ARGUMENT,
-                                fmt("object %d triangle %d: vertex index %d out of range", b, t, T[3 * t + k]));
-        // Back-face culling is exact only for a closed, consistently oriented surface: after
-        // welding vertices by position and dropping degenerate triangles every directed edge
-        // must occur exactly once, and its reverse exactly once.  The sign of the signed volume
-        // tells which winding is outward.
-        B.body_cull[b] = 0;
-        if (allow_cull && nt >= 4) {
-            std::map<std::array<double, 3>, int> weld;
-            std::vector<int> wid(nv);
-            for (int i = 0; i < nv; ++i) {
-                const std::array<double, 3> key = {V[3 * i] + 0.0, V[3 * i + 1] + 0.0, V[3 * i + 2] + 0.0};  // -0 -> +0
-                wid[i] = weld.emplace(key, (int)weld.size()).first->second;
-            }
-            std::map<std::pair<int, int>, int> edges;
-            double vol6 = 0.0, avol6 = 0.0;
-            bool ok = true;
-            // connected components (shells) over the welded vertices: every shell must be wound the
-            // same way -- an inside-out shell beside an outward one would pass the edge test and
-            // still show the camera its "back" faces first
-            std::vector<int> comp(weld.size());
-            for (size_t i = 0; i < comp.size(); ++i) comp[i] = (int)i;
-            auto find = [&](int x) { while (comp[x] != x) { comp[x] = comp[comp[x]]; x = comp[x]; } return x; };
-            std::vector<double> tri_vol(nt, 0.0);
-            for (int t = 0; t < nt && ok; ++t) {
-                const int a = wid[T[3 * t]], bb = wid[T[3 * t + 1]], c3 = wid[T[3 * t + 2]];
-                if (a == bb || bb == c3 || a == c3) continue;
-                for (const auto& e : {std::make_pair(a, bb), std::make_pair(bb, c3), std::make_pair(c3, a)})
-                    if (++edges[e] > 1) ok = false;
-                const double* p0 = V + 3 * T[3 * t]; const double* p1 = V + 3 * T[3 * t + 1]; const double* p2 = V + 3 * T[3 * t + 2];
-                const double d = (p0[0] - ctr[0]) * ((p1[1] - ctr[1]) * (p2[2] - ctr[2]) - (p1[2] - ctr[2]) * (p2[1] - ctr[1])) -
-                                 (p0[1] - ctr[1]) * ((p1[0] - ctr[0]) * (p2[2] - ctr[2]) - (p1[2] - ctr[2]) * (p2[0] - ctr[0])) +
-                                 (p0[2] - ctr[2]) * ((p1[0] - ctr[0]) * (p2[1] - ctr[1]) - (p1[1] - ctr[1]) * (p2[0] - ctr[0]));
-                vol6 += d;
-                avol6 += std::fabs(d);
-                tri_vol[t] = d;
-                comp[find(a)] = find(bb);
-                comp[find(bb)] = find(c3);
-            }
-            if (ok) {
-                std::map<int, std::pair<double, double>> shell;   // root -> (signed, absolute) volume * 6
-                for (int t = 0; t < nt; ++t) {
-                    if (tri_vol[t] == 0.0) continue;
-                    auto& sv = shell[find(wid[T[3 * t]])];
-                    sv.first += tri_vol[t];
-                    sv.second += std::fabs(tri_vol[t]);
-                }
-                for (const auto& sv : shell)
-                    if (!(std::fabs(sv.second.first) > 1e-6 * sv.second.second) || (sv.second.first > 0.0) != (vol6 > 0.0)) ok = false;
-            }
-            if (ok)
-                for (const auto& e : edges)
-                    if (edges.find({e.first.second, e.first.first}) == edges.end()) { ok = false; break; }
-            if (ok && !edges.empty() && std::fabs(vol6) > 1e-6 * avol6) B.body_cull[b] = vol6 > 0.0 ? 1 : -1;
-        }
-        // Cluster order: recursive median bisection of the triangles in (centroid / extent,
-        // 0.5 * unit normal) space, always along the widest of the six axes, left halves a whole
-        // number of 64-triangle clusters.  Every aligned run of 64 is then a compact surface
-        // patch with a narrow normal cone (a plain Morton order of the centroids mixes the two
-        // sides of thin parts and gives cones too wide to cull by).
-        std::vector<std::pair<uint32_t, int>> order(nt);
-        {
-            const double ext = std::fmax(std::fmax(hi[0] - lo[0], hi[1] - lo[1]), std::fmax(hi[2] - lo[2], 1e-300));
-            std::vector<std::array<double, 6>> feat(nt);
-            for (int t = 0; t < nt; ++t) {
-                const double* p0 = V + 3 * T[3 * t]; const double* p1 = V + 3 * T[3 * t + 1]; const double* p2 = V + 3 * T[3 * t + 2];
-                const double e1[3] = {p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2]};
-                const double e2[3] = {p2[0] - p0[0], p2[1] - p0[1], p2[2] - p0[2]};
-                const double n3[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
-                const double len = std::sqrt(n3[0] * n3[0] + n3[1] * n3[1] + n3[2] * n3[2]);
-                for (int c3 = 0; c3 < 3; ++c3) {
-                    feat[t][c3] = (p0[c3] + p1[c3] + p2[c3]) / (3.0 * ext);
-                    feat[t][3 + c3] = len > 0.0 ? 0.5 * n3[c3] / len : 0.0;
-                }
-            }
-            std::vector<int> idx(nt);
-            for (int t = 0; t < nt; ++t) idx[t] = t;
-            std::vector<std::pair<int, int>> stack;   // [begin, end) ranges still to split
-            stack.push_back({0, nt});
-            while (!stack.empty()) {
-                const auto rg = stack.back();
-                stack.pop_back();
-                const int cnt = rg.second - rg.first;
-                if (cnt <= 64) continue;
-                int dim = 0;
-                double best = -1.0;
-                for (int d = 0; d < 6; ++d) {
-                    double mn = 1e300, mx = -1e300;
-                    for (int i = rg.first; i < rg.second; ++i) { mn = std::fmin(mn, feat[idx[i]][d]); mx = std::fmax(mx, feat[idx[i]][d]); }
-                    if (mx - mn > best) { best = mx - mn; dim = d; }
-                }
-                std::stable_sort(idx.begin() + rg.first, idx.begin() + rg.second,
-                                 [&](int x, int y) { return feat[x][dim] < feat[y][dim]; });
-                const int left = ((cnt + 63) / 64 / 2) * 64;
-                stack.push_back({rg.first, rg.first + left});
-                stack.push_back({rg.first + left, rg.second});
-            }
-            for (int j = 0; j < nt; ++j) order[j] = {0u, idx[j]};
-        }
-        const size_t base = (size_t)B.tri_begin[b];
-        for (int j = 0; j < nt; ++j) {
-            const int t = order[j].second;
-            for (int k = 0; k < 3; ++k)
-                for (int c3 = 0; c3 < 3; ++c3)
-                    soup[(size_t)(3 * k + c3) * n_alloc + base + j] = V[3 * T[3 * t + k] + c3];
-        }
-        B.tri_end[b] = (int)base + nt;
-        // vertex sharing: the unique vertices (by index) of every cluster of 64 and, per triangle, where
-        // its three sit in that list; a cluster with more than 64 of them is set up per triangle
-        for (size_t c = base / 64; c < (size_t)B.tri_begin[b + 1] / 64; ++c) {
-            const size_t j0 = c * 64 - base, j1 = std::min<size_t>(j0 + 64, (size_t)nt);
-            std::map<int, int> local;
-            bool fits = true;
-            for (size_t j = j0; j < j1 && fits; ++j)
-                for (int k = 0; k < 3; ++k) {
-                    const int vi = T[3 * order[j].second + k];
-                    if (local.find(vi) == local.end()) {
-                        if (local.size() == 64) { fits = false; break; }
-                        const int pos = (int)local.size();
-                        local[vi] = pos;
-                        for (int c3 = 0; c3 < 3; ++c3) cluster_vtx[c * 192 + 64 * c3 + pos] = V[3 * vi + c3];
-                    }
-                }
-            if (!fits || local.empty()) continue;
-            cluster_nv[c] = (int)local.size();
-            for (size_t j = j0; j < j1; ++j) {
-                unsigned pk = 0;
-                for (int k = 0; k < 3; ++k) pk |= (unsigned)local[T[3 * order[j].second + k]] << (8 * k);
-                tri_local[base + j] = pk;
-            }
-        }
-        // model-space plane of each triangle, unit normal of its winding (float32 pre-cull only)
-        for (int j = 0; j < nt; ++j) {
-            double p[3][3];
-            for (int k = 0; k < 3; ++k)
-                for (int c3 = 0; c3 < 3; ++c3) p[k][c3] = soup[(size_t)(3 * k + c3) * n_alloc + base + j];
-            const double e1[3] = {p[1][0] - p[0][0], p[1][1] - p[0][1], p[1][2] - p[0][2]};
-            const double e2[3] = {p[2][0] - p[0][0], p[2][1] - p[0][1], p[2][2] - p[0][2]};
-            const double n3[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
-            const double len = std::sqrt(n3[0] * n3[0] + n3[1] * n3[1] + n3[2] * n3[2]);
-            if (!(len > 0.0) || !std::isfinite(len)) continue;   // zero area: stays NaN = kept (the setup rejects it)
-            // offset from the triangle's centroid (the three vertices give the same plane up to rounding)
-            const double cx3 = (p[0][0] + p[1][0] + p[2][0]) / 3.0, cy3 = (p[0][1] + p[1][1] + p[2][1]) / 3.0,
-                         cz3 = (p[0][2] + p[1][2] + p[2][2]) / 3.0;
-            float* pl = &tri_plane[4 * (base + j)];
-            pl[0] = (float)(n3[0] / len); pl[1] = (float)(n3[1] / len); pl[2] = (float)(n3[2] / len);
-            pl[3] = (float)(-(n3[0] * cx3 + n3[1] * cy3 + n3[2] * cz3) / len);
-        }
-        // bounding sphere of each cluster of 64 (centre = bbox centre of its vertices)
-        for (size_t c = base / 64; c < (size_t)B.tri_begin[b + 1] / 64; ++c) {
-            double clo[3] = {1e300, 1e300, 1e300}, chi[3] = {-1e300, -1e300, -1e300};
-            const size_t j0 = c * 64 - base, j1 = std::min<size_t>(j0 + 64, (size_t)nt);
-            for (size_t j = j0; j < j1; ++j)
-                for (int k = 0; k < 3; ++k)
-                    for (int c3 = 0; c3 < 3; ++c3) {
-                        const double x = soup[(size_t)(3 * k + c3) * n_alloc + base + j];
-                        clo[c3] = std::fmin(clo[c3], x); chi[c3] = std::fmax(chi[c3], x);
-                    }
-            double cc[3] = {0.5 * (clo[0] + chi[0]), 0.5 * (clo[1] + chi[1]), 0.5 * (clo[2] + chi[2])}, cr2 = 0.0;
-            for (size_t j = j0; j < j1; ++j)
-                for (int k = 0; k < 3; ++k) {
-                    double d2 = 0.0;
-                    for (int c3 = 0; c3 < 3; ++c3) {
-                        const double d = soup[(size_t)(3 * k + c3) * n_alloc + base + j] - cc[c3];
-                        d2 += d * d;
-                    }
-                    cr2 = std::fmax(cr2, d2);
-                }
-            for (int c3 = 0; c3 < 3; ++c3) cluster_sphere[4 * c + c3] = (float)cc[c3];
-            cluster_sphere[4 * c + 3] = (float)(std::sqrt(cr2) * 1.0001 + 1e-6);
-            if (B.body_cull[b] != 0) {   // cone of the cluster's outward unit normals
-                std::vector<std::array<double, 3>> nrm;
-                double ax[3] = {0, 0, 0};
-                for (size_t j = j0; j < j1; ++j) {
-                    double p[3][3];
-                    for (int k = 0; k < 3; ++k)
-                        for (int c3 = 0; c3 < 3; ++c3) p[k][c3] = soup[(size_t)(3 * k + c3) * n_alloc + base + j];
-                    const double e1[3] = {p[1][0] - p[0][0], p[1][1] - p[0][1], p[1][2] - p[0][2]};
-                    const double e2[3] = {p[2][0] - p[0][0], p[2][1] - p[0][1], p[2][2] - p[0][2]};
-                    double n3[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
-                    const double len = std::sqrt(n3[0] * n3[0] + n3[1] * n3[1] + n3[2] * n3[2]);
-                    if (!(len > 0.0)) continue;   // zero area: never rendered
-                    for (int c3 = 0; c3 < 3; ++c3) { n3[c3] *= (double)B.body_cull[b] / len; ax[c3] += n3[c3]; }
-                    nrm.push_back({n3[0], n3[1], n3[2]});
-                }
-                const double al = std::sqrt(ax[0] * ax[0] + ax[1] * ax[1] + ax[2] * ax[2]);
-                if (al > 1e-9 && !nrm.empty()) {
-                    double mindp = 1.0;
-                    for (const auto& n3 : nrm) mindp = std::fmin(mindp, (n3[0] * ax[0] + n3[1] * ax[1] + n3[2] * ax[2]) / al);
-                    for (int c3 = 0; c3 < 3; ++c3) cluster_cone[4 * c + c3] = (float)(ax[c3] / al);
-                    cluster_cone[4 * c + 3] = (float)(mindp - 1e-4);   // <= 0: the cone is too wide to cull by
-                }
-            }
-        }
-        voff += nv;
-        toff += nt;
-    }
-    B.n_tri = (int)n_alloc;
 
     const size_t plane = (size_t)h->npx * sizeof(float);
     RBS_HIP(h, hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
@@ -2092,8 +1871,7 @@ int32_t create_impl(const rbs_config* cfg, rbs_handle* h)
         // blocks per CU hold 504 of a SIMD's 512 VGPRs -- two leave room for the copy waves
         if (!h->windowed && !std::getenv("RBS_RASTER_BLOCKS")) h->raster_blocks = 2 * std::max(1, prop.multiProcessorCount);
     }
-    RBS_HIP(h, hipMalloc(&h->d_soup, soup.size() * sizeof(double)));
-    RBS_HIP(h, hipMemcpy(h->d_soup, soup.data(), soup.size() * sizeof(double), hipMemcpyHostToDevice));
+    if (int32_t rc = upload(h, &h->d_soup, mesh.soup)) return rc;
     B.soup = h->d_soup;
     RBS_HIP(h, hipMalloc(&h->d_frame, plane));
     if (h->precision == RBS_PRECISION_F64) {   // F32 derives the per-pixel terms from the observation on the fly
@@ -2189,43 +1967,20 @@ int32_t create_impl(const rbs_config* cfg, rbs_handle* h)
     RBS_HIP(h, hipMalloc(&h->d_ctr, sizeof(int) * 8));
     RBS_HIP(h, hipMemset(h->d_ctr, 0, sizeof(int) * 8));
     RBS_HIP(h, hipMalloc(&h->d_done, sizeof(int) * (size_t)h->max_particles));
-    RBS_HIP(h, hipMalloc(&h->d_cluster_sphere, sizeof(float) * cluster_sphere.size()));
-    RBS_HIP(h, hipMemcpy(h->d_cluster_sphere, cluster_sphere.data(), sizeof(float) * cluster_sphere.size(),
-                         hipMemcpyHostToDevice));
+    if (int32_t rc = upload(h, &h->d_cluster_sphere, mesh.cluster_sphere)) return rc;
     B.cluster_sphere = h->d_cluster_sphere;
-    RBS_HIP(h, hipMalloc(&h->d_cluster_cone, sizeof(float) * cluster_cone.size()));
-    RBS_HIP(h, hipMemcpy(h->d_cluster_cone, cluster_cone.data(), sizeof(float) * cluster_cone.size(),
-                         hipMemcpyHostToDevice));
+    if (int32_t rc = upload(h, &h->d_cluster_cone, mesh.cluster_cone)) return rc;
     B.cluster_cone = h->d_cluster_cone;
-    RBS_HIP(h, hipMalloc(&h->d_cluster_vtx, sizeof(double) * cluster_vtx.size()));
-    RBS_HIP(h, hipMemcpy(h->d_cluster_vtx, cluster_vtx.data(), sizeof(double) * cluster_vtx.size(), hipMemcpyHostToDevice));
+    if (int32_t rc = upload(h, &h->d_cluster_vtx, mesh.cluster_vtx)) return rc;
     B.cluster_vtx = h->d_cluster_vtx;
-    RBS_HIP(h, hipMalloc(&h->d_cluster_nv, sizeof(int) * cluster_nv.size()));
-    RBS_HIP(h, hipMemcpy(h->d_cluster_nv, cluster_nv.data(), sizeof(int) * cluster_nv.size(), hipMemcpyHostToDevice));
+    if (int32_t rc = upload(h, &h->d_cluster_nv, mesh.cluster_nv)) return rc;
     B.cluster_nv = h->d_cluster_nv;
-    RBS_HIP(h, hipMalloc(&h->d_tri_local, sizeof(unsigned) * tri_local.size()));
-    RBS_HIP(h, hipMemcpy(h->d_tri_local, tri_local.data(), sizeof(unsigned) * tri_local.size(), hipMemcpyHostToDevice));
+    if (int32_t rc = upload(h, &h->d_tri_local, mesh.tri_local)) return rc;
     B.tri_local = h->d_tri_local;
-    RBS_HIP(h, hipMalloc(&h->d_tri_plane, sizeof(float) * tri_plane.size()));
-    RBS_HIP(h, hipMemcpy(h->d_tri_plane, tri_plane.data(), sizeof(float) * tri_plane.size(), hipMemcpyHostToDevice));
+    if (int32_t rc = upload(h, &h->d_tri_plane, mesh.tri_plane)) return rc;
     B.tri_plane = reinterpret_cast<const rbs::floatx4*>(h->d_tri_plane);
-    {   // float32 copy of the vertices, per body (screen rectangles)
-        std::vector<float> vtx;
-        size_t vo = 0;
-        B.vtx_begin[0] = 0;
-        for (int b = 0; b < h->n_bodies; ++b) {
-            for (int i = 0; i < cfg->vertex_counts[b]; ++i) {
-                for (int c3 = 0; c3 < 3; ++c3) vtx.push_back((float)cfg->vertices[3 * (vo + i) + c3]);
-                vtx.push_back(0.f);
-            }
-            vo += (size_t)cfg->vertex_counts[b];
-            B.vtx_begin[b + 1] = (int)vo;
-        }
-        for (int b = h->n_bodies; b < rbs::kMaxBodies; ++b) B.vtx_begin[b + 1] = (int)vo;
-        RBS_HIP(h, hipMalloc(&h->d_vtx, sizeof(float) * std::max<size_t>(vtx.size(), 4)));
-        RBS_HIP(h, hipMemcpy(h->d_vtx, vtx.data(), sizeof(float) * vtx.size(), hipMemcpyHostToDevice));
-        B.vtx = reinterpret_cast<const rbs::floatx4*>(h->d_vtx);
-    }
+    if (int32_t rc = upload(h, &h->d_vtx, mesh.vtx, 4)) return rc;   // float32 copy of the vertices, per body (screen rectangles)
+    B.vtx = reinterpret_cast<const rbs::floatx4*>(h->d_vtx);
     if (const char* e = std::getenv("RBS_FRAME_PULL_BYTES")) h->frame_pull_bytes = (size_t)std::max(0L, std::atol(e));
     RBS_HIP(h, hipStreamCreateWithFlags(&h->up_stream, hipStreamNonBlocking));
     for (int k = 0; k < 2; ++k) {

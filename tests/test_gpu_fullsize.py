@@ -15,6 +15,7 @@ import pytest
 import oracle_binding as ob
 import scenarios as sc
 from dbot_ros_amd import CameraData, ObjectModel, RbSensor, RbSensorBuilder, pose, synth
+from mesh_cases import box_variant
 
 pytestmark = pytest.mark.gpu
 
@@ -231,15 +232,6 @@ def test_vga_long_sequence_against_reference_semantics(gpu_lib, precision):
         assert len(over) <= 3 and all(abs(ll_) < 1e-2 * s_ for _, _, ll_, s_, _ in over), over
 
 
-def _box(x0, x1, y0, y1, z0, z1):
-    v = np.array([[x, y, z] for z in (z0, z1) for y in (y0, y1) for x in (x0, x1)], dtype=np.float64)
-    quads = [(0, 2, 3, 1), (4, 5, 7, 6), (0, 1, 5, 4), (2, 6, 7, 3), (0, 4, 6, 2), (1, 3, 7, 5)]   # outward
-    t = []
-    for a, b, c, d in quads:
-        t += [(a, b, c), (a, c, d)]
-    return v, np.array(t, dtype=np.int32)
-
-
 @pytest.mark.parametrize("variant", ["closed", "closed_inward", "with_holes", "mixed_winding", "two_shells",
                                      "unwelded", "one_shell_inside_out"])
 def test_samples_exactly_on_silhouette_edges(gpu_lib, variant):
@@ -248,24 +240,9 @@ def test_samples_exactly_on_silhouette_edges(gpu_lib, variant):
     x, y = k/256 on the planes z = 1 and z = 2 project onto integer pixel coordinates in binary64
     exactly, its edges run along pixel rows and columns, and every edge function of a boundary
     sample is exactly zero.  Seven mesh variants (the closed ones are culled, the others must not
-    be); the box is also moved so that side faces become visible with their edges still on
+    be: which are is asserted by tests/test_mesh_prep_cpu.py); the box is also moved so that side faces become visible with their edges still on
     integer coordinates."""
-    v, t = _box(-24 / 256, 40 / 256, -16 / 256, 32 / 256, 1.0, 2.0)
-    rng = np.random.default_rng(4)
-    if variant == "closed_inward":
-        t = t[:, ::-1].copy()
-    elif variant == "with_holes":
-        t = np.delete(t, [4, 5], axis=0)
-    elif variant == "mixed_winding":
-        t[::2] = t[::2][:, ::-1]
-    elif variant == "two_shells":
-        v2, t2 = _box(56 / 256, 88 / 256, -16 / 256, 32 / 256, 1.0, 2.0)
-        v, t = np.concatenate([v, v2]), np.concatenate([t, t2 + len(v)])
-    elif variant == "unwelded":
-        v, t = v[t].reshape(-1, 3), np.arange(3 * len(t), dtype=np.int32).reshape(-1, 3)
-    elif variant == "one_shell_inside_out":
-        v2, t2 = _box(56 / 256, 88 / 256, -16 / 256, 32 / 256, 1.0, 2.0)
-        v, t = np.concatenate([v, v2]), np.concatenate([t, t2[:, ::-1] + len(v)])
+    v, t = box_variant(variant)
     cols, rows = 640, 480
     K = np.array([[512.0, 0, 320.0], [0, 512.0, 240.0], [0, 0, 1.0]])
     om = ObjectModel([v], [t], center=False)

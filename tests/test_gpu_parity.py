@@ -14,6 +14,7 @@ import pytest
 import oracle_binding as ob
 import scenarios as sc
 from dbot_ros_amd import RbSensor, RbSensorError, synth
+from mesh_cases import mesh_variants
 
 pytestmark = pytest.mark.gpu
 
@@ -644,26 +645,6 @@ def test_windows_follow_the_object(gpu_lib, state_layout):
         assert a[31] < cols * rows
 
 
-def _mesh_variants():
-    v, t = synth.mesh_m1(level=2)
-    v = np.asarray(v, np.float64)
-    t = np.asarray(t, np.int32)
-    rng = np.random.default_rng(3)
-    flipped = t[:, ::-1].copy()
-    holes = np.delete(t, rng.choice(len(t), 40, replace=False), axis=0)
-    mixed = t.copy()
-    sel = rng.choice(len(t), len(t) // 2, replace=False)
-    mixed[sel] = mixed[sel][:, ::-1]
-    shells_v = np.concatenate([v, v * 0.5 + np.array([0.0, 0.0, 0.09])])
-    shells_t = np.concatenate([t, t + len(v)])
-    soup_v = v[t].reshape(-1, 3)                      # every triangle owns its three vertices
-    soup_t = np.arange(len(soup_v), dtype=np.int32).reshape(-1, 3)
-    inside_out_t = np.concatenate([t, flipped + len(v)])      # second shell wound the other way
-    return {"closed": (v, t), "closed_inward": (v, flipped), "with_holes": (v, holes),
-            "mixed_winding": (v, mixed), "two_shells": (shells_v, shells_t), "unwelded": (soup_v, soup_t),
-            "one_shell_inside_out": (shells_v, inside_out_t)}
-
-
 @pytest.mark.parametrize("variant", ["closed", "closed_inward", "with_holes", "mixed_winding", "two_shells",
                                      "unwelded", "one_shell_inside_out"])
 def test_backface_culling_never_changes_a_depth(gpu_lib, variant):
@@ -672,7 +653,7 @@ def test_backface_culling_never_changes_a_depth(gpu_lib, variant):
     inside, inconsistent winding, several shells, unwelded vertices -- and wherever it is (also
     around and across the camera plane), the rendered depth is the oracle's, bit for bit."""
     from dbot_ros_amd import CameraData, ObjectModel, RbSensorBuilder
-    v, t = _mesh_variants()[variant]
+    v, t = mesh_variants()[variant]
     cols, rows = 320, 240
     om = ObjectModel([v], [t], center=True)
     cam = CameraData(synth.camera_matrix(cols, rows), rows, cols)
