@@ -49,6 +49,7 @@ EXPORTS = (
     "rbs_gauss_kernel_ms", "rbs_gauss_submit", "rbs_gauss_submit_f64", "rbs_gauss_result",
     "rbs_find_default_params", "rbs_find_create", "rbs_find_destroy", "rbs_find_run", "rbs_find_get_stage",
     "rbs_find_stage_ms", "rbs_find_last_error",
+    "rbs_find_default_foreground", "rbs_find_set_foreground", "rbs_find_get_plane", "rbs_find_get_seed_frame",
 )
 RBS_FIND_SEEDS, RBS_FIND_COARSE, RBS_FIND_CANDIDATES, RBS_FIND_SURVIVORS, RBS_FIND_CHILDREN, RBS_FIND_RESULT = range(6)
 
@@ -99,6 +100,16 @@ class RbsFindParams(C.Structure):
         ("batch", C.c_int32),
         ("seed", C.c_uint64),
         ("min_score", C.c_double),
+    ]
+
+
+class RbsFindForeground(C.Structure):
+    _fields_ = [
+        ("enabled", C.c_int32),
+        ("plane_trials", C.c_int32),
+        ("ransac_sigmas", C.c_double),
+        ("mask_sigmas", C.c_double),
+        ("min_inlier_fraction", C.c_double),
     ]
 
 
@@ -308,6 +319,14 @@ def load():
     lib.rbs_find_get_stage.argtypes = [H, C.c_int32, C.c_int32, dp, dp, lp, lp, dp]
     lib.rbs_find_stage_ms.restype = C.c_int32
     lib.rbs_find_stage_ms.argtypes = [H, fp]
+    lib.rbs_find_default_foreground.restype = None
+    lib.rbs_find_default_foreground.argtypes = [C.POINTER(RbsFindForeground)]
+    lib.rbs_find_set_foreground.restype = C.c_int32
+    lib.rbs_find_set_foreground.argtypes = [H, C.POINTER(RbsFindForeground)]
+    lib.rbs_find_get_plane.restype = C.c_int32
+    lib.rbs_find_get_plane.argtypes = [H, dp]
+    lib.rbs_find_get_seed_frame.restype = C.c_int32
+    lib.rbs_find_get_seed_frame.argtypes = [H, fp, lp]
     lib.rbs_find_last_error.restype = C.c_char_p
     lib.rbs_find_last_error.argtypes = [H]
     _lib = lib

@@ -4,6 +4,9 @@
 //
 // Per find, on the coarse scoring handle's stream:
 //   rbs_find_subsample_kernel   every f-th pixel of every f-th row of the frame already on the device
+//   (rbs_findfg_*_kernel)       opt-in step 1b (rbs_find_set_foreground): the dominant inverse-depth plane of the coarse frame
+//                               from three-point trials, and the seeding frame -- the coarse frame with every pixel that is not
+//                               strictly in front of that plane NaN.  The seed kernel then reads the seeding frame.
 //   rbs_find_seed_kernel        one block: valid seed-grid pixels compacted in row-major order, then thinned
 //   rbs_find_hyp_kernel         hypothesis h -> pose (Super-Fibonacci rotation, seed translation), binary64
 //   (rbs_loglikes_device)       coarse scores, `batch` hypotheses per launch
@@ -312,6 +315,153 @@ __global__ __launch_bounds__(64) void rbs_find_keep_kernel(const double* __restr
     surv_idx[i] = cand_idx[c];
 }
 
+// ---------------------------------------------------------------------------- step 1b: the foreground (opt-in)
+// The dominant plane of the coarse frame in inverse depth, 1 / z = a u + b v + c, and the seeding frame.  Binary64, only
+// + - * / and comparisons in the order of include/rbsensor_mi355x.h (step 1b), so tests/find_fg_twin.py makes every decision
+// bit for bit.  The chosen plane is a trial's three-point plane: there is no least-squares refit.
+// (Named rbs_findfg_*: the rbs_find_*_kernel names are a closed list, tests/test_finder_cpu.py.)
+constexpr int kFgThreads = 256;
+constexpr int kFgMaxTrials = 4096;
+constexpr int kFgRecord = 8;       // accepted, a, b, c, count, n_valid, trial, (pixels masked: the host's)
+
+struct FgModel {
+    double dmin, dmax;             // valid: dmin <= d <= dmax (the seed kernel's test)
+    double ms, sf;                 // sigma(z) = ms + sf (z z)
+};
+
+__device__ inline bool fg_valid(const FgModel& M, double d) { return d >= M.dmin && d <= M.dmax; }
+__device__ inline double fg_sigma(const FgModel& M, double z) { return M.ms + M.sf * (z * z); }
+
+// One thread per trial t: three pixels from Philox4x32-10 (key = seed, counter words (t, 0, 0, 0xFFFFFFFF): the refinement's
+// word 3 is a round <= 64), planes [t][4] := (a, b, c, void); a void trial is (0, 0, 0, 1).
+__global__ __launch_bounds__(kFgThreads) void rbs_findfg_trials_kernel(const float* __restrict__ frame, int npx, int cols, const FgModel M,
+                                                                       unsigned long long seed, int trials, double* __restrict__ planes)
+{
+    const int t = blockIdx.x * kFgThreads + threadIdx.x;
+    if (t >= trials) return;
+    const uint4 r = philox(seed, 0xFFFFFFFF00000000ull, (unsigned long long)(unsigned)t);
+    const unsigned word[3] = {r.x, r.y, r.z};
+    double u[3], v[3], d[3];
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int i = (int)(((unsigned long long)word[k] * (unsigned long long)npx) >> 32);   // < npx
+        const int row = i / cols;
+        u[k] = (double)(i - row * cols);
+        v[k] = (double)row;
+        d[k] = (double)frame[i];
+        ok = ok && fg_valid(M, d[k]);
+    }
+    const double D = (u[1] - u[0]) * (v[2] - v[0]) - (u[2] - u[0]) * (v[1] - v[0]);
+    double a = 0.0, b = 0.0, c = 0.0;
+    ok = ok && D != 0.0;
+    if (ok) {
+        const double q0 = 1.0 / d[0], q1 = 1.0 / d[1], q2 = 1.0 / d[2];
+        a = ((q1 - q0) * (v[2] - v[0]) - (q2 - q0) * (v[1] - v[0])) / D;
+        b = ((u[1] - u[0]) * (q2 - q0) - (u[2] - u[0]) * (q1 - q0)) / D;
+        c = (q0 - a * u[0]) - b * v[0];
+    }
+    double* o = planes + 4 * (size_t)t;
+    o[0] = a; o[1] = b; o[2] = c; o[3] = ok ? 0.0 : 1.0;
+}
+
+// One block per trial, pixels strided over the block: counts[t] := the valid pixels within rs sigma of trial t's plane (-1: a
+// void trial).  Block `trials` counts the valid pixels: counts[trials] := n_valid.  Integer sums: exact in any order.
+__global__ __launch_bounds__(kFgThreads) void rbs_findfg_count_kernel(const float* __restrict__ frame, int npx, int cols, const FgModel M,
+                                                                      const double* __restrict__ planes, int trials, double rs,
+                                                                      int* __restrict__ counts)
+{
+    __shared__ int wave_sum[kFgThreads / 64];
+    const int t = blockIdx.x;
+    const bool all = t == trials;
+    double a = 0.0, b = 0.0, c = 0.0;
+    if (!all) {
+        if (planes[4 * (size_t)t + 3] != 0.0) {
+            if (threadIdx.x == 0) counts[t] = -1;
+            return;
+        }
+        a = planes[4 * (size_t)t]; b = planes[4 * (size_t)t + 1]; c = planes[4 * (size_t)t + 2];
+    }
+    int mine = 0;   // (lane 0 of each wave carries the wave's sum)
+    for (int p0 = 0; p0 < npx; p0 += kFgThreads) {
+        const int p = p0 + (int)threadIdx.x;
+        bool in = false;
+        if (p < npx) {
+            const double d = (double)frame[p];
+            in = fg_valid(M, d);
+            if (in && !all) {
+                const int row = p / cols;
+                const double w = (a * (double)(p - row * cols) + b * (double)row) + c;
+                in = w > 0.0;
+                if (in) {
+                    const double z = 1.0 / w;
+                    in = fabs(d - z) <= rs * fg_sigma(M, z);
+                }
+            }
+        }
+        mine += __popcll(__ballot(in));
+    }
+    if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int tot = 0;
+        for (int w = 0; w < kFgThreads / 64; ++w) tot += wave_sum[w];
+        counts[t] = tot;
+    }
+}
+
+// One wave: the highest count, ties to the lowest trial; accepted when count >= 3 and count >= min_fraction n_valid.
+// rec [kFgRecord] := accepted, a, b, c, count, n_valid, trial, 0.
+__global__ __launch_bounds__(64) void rbs_findfg_best_kernel(const double* __restrict__ planes, const int* __restrict__ counts, int trials,
+                                                             double min_fraction, double* __restrict__ rec)
+{
+    __shared__ int best_c[64], best_t[64];
+    const int lane = threadIdx.x;
+    int bc = INT_MIN, bt = INT_MAX;
+    for (int t = lane; t < trials; t += 64) {   // (ascending t: a later equal count never replaces)
+        const int c = counts[t];
+        if (c > bc) { bc = c; bt = t; }
+    }
+    best_c[lane] = bc;
+    best_t[lane] = bt;
+    __syncthreads();
+    if (lane != 0) return;
+    for (int l = 1; l < 64; ++l)
+        if (best_c[l] > bc || (best_c[l] == bc && best_t[l] < bt)) { bc = best_c[l]; bt = best_t[l]; }
+    const int n_valid = counts[trials];
+    const bool accepted = bc >= 3 && (double)bc >= min_fraction * (double)n_valid;
+    rec[0] = accepted ? 1.0 : 0.0;
+    rec[1] = planes[4 * (size_t)bt];
+    rec[2] = planes[4 * (size_t)bt + 1];
+    rec[3] = planes[4 * (size_t)bt + 2];
+    rec[4] = (double)bc;
+    rec[5] = (double)n_valid;
+    rec[6] = (double)bt;
+    rec[7] = 0.0;
+}
+
+// One thread per coarse pixel: the seeding frame.  A pixel keeps its depth (its bits) when the plane is not accepted, or the
+// plane is behind the camera there (w <= 0), or the pixel is strictly in front: z - d > mask_sigmas sigma(z); else NaN.
+__global__ __launch_bounds__(kFgThreads) void rbs_findfg_mask_kernel(const float* __restrict__ frame, int npx, int cols, const FgModel M,
+                                                                     const double* __restrict__ rec, double mask_sigmas,
+                                                                     float* __restrict__ out)
+{
+    const int p = blockIdx.x * kFgThreads + threadIdx.x;
+    if (p >= npx) return;
+    const float f = frame[p];
+    bool keep = rec[0] == 0.0;
+    if (!keep) {
+        const int row = p / cols;
+        const double w = (rec[1] * (double)(p - row * cols) + rec[2] * (double)row) + rec[3];
+        keep = w <= 0.0;
+        if (!keep) {
+            const double z = 1.0 / w;
+            keep = z - (double)f > mask_sigmas * fg_sigma(M, z);
+        }
+    }
+    out[p] = keep ? f : __builtin_nanf("");
+}
+
 // ---------------------------------------------------------------------------- launches
 // One helper per launch of a find: a stream and raw device pointers, nothing of an rbs_find.  rbs_find_run and
 // rbs_find_get_stage launch through these, and so do the probes of the test build (rbsensor_probes.hip).
@@ -404,6 +554,37 @@ inline void launch_order(hipStream_t st, const double* surv, const double* surv_
     hipLaunchKernelGGL(rbs_find_order_kernel, dim3(1), dim3(64), 0, st, surv, surv_score, order, S, out_pose, out_score);
 }
 
+// step 1b: planes [trials][4]
+inline void launch_plane_trials(hipStream_t st, const float* frame, int rows, int cols, const FgModel& M, unsigned long long seed, int trials,
+                                double* planes)
+{
+    hipLaunchKernelGGL(rbs_findfg_trials_kernel, dim3((unsigned)((trials + kFgThreads - 1) / kFgThreads)), dim3(kFgThreads), 0, st, frame,
+                       rows * cols, cols, M, seed, trials, planes);
+}
+
+// counts [trials + 1]: every trial's inliers, then the valid pixels.  trials == 0: the valid pixels alone (planes unused)
+inline void launch_plane_count(hipStream_t st, const float* frame, int rows, int cols, const FgModel& M, const double* planes, int trials,
+                               double ransac_sigmas, int* counts)
+{
+    hipLaunchKernelGGL(rbs_findfg_count_kernel, dim3((unsigned)(trials + 1)), dim3(kFgThreads), 0, st, frame, rows * cols, cols, M, planes,
+                       trials, ransac_sigmas, counts);
+}
+
+// rec [kFgRecord]
+inline void launch_plane_best(hipStream_t st, const double* planes, const int* counts, int trials, double min_fraction, double* rec)
+{
+    hipLaunchKernelGGL(rbs_findfg_best_kernel, dim3(1), dim3(64), 0, st, planes, counts, trials, min_fraction, rec);
+}
+
+// out [rows * cols]: the seeding frame
+inline void launch_mask(hipStream_t st, const float* frame, int rows, int cols, const FgModel& M, const double* rec, double mask_sigmas,
+                        float* out)
+{
+    const int npx = rows * cols;
+    hipLaunchKernelGGL(rbs_findfg_mask_kernel, dim3((unsigned)((npx + kFgThreads - 1) / kFgThreads)), dim3(kFgThreads), 0, st, frame, npx,
+                       cols, M, rec, mask_sigmas, out);
+}
+
 }  // namespace rbf
 
 struct rbs_find {
@@ -421,8 +602,14 @@ struct rbs_find {
     float* h_frame = nullptr;         // pinned staging of a host frame
     int* d_cells = nullptr;           // seed-grid compaction
     double* d_seeds = nullptr;        // [max_seeds][4]
-    int* d_info = nullptr;            // [2] kept, valid  (+ [2] suppression count)
-    int* h_info = nullptr;            // pinned
+    int* d_info = nullptr;            // [2] kept, valid  (+ [2] suppression count, [3] valid pixels of the seeding frame),
+    int* h_info = nullptr;            //   then step 1b's record, kFgRecord doubles (info_bytes in all); h_info: pinned
+    // step 1b (rbs_find_set_foreground): allocated when first switched on
+    rbs_find_foreground fg{};         // the setting of the next find
+    float* d_seedframe = nullptr;     // [crows*ccols] the seeding frame
+    double* d_planes = nullptr;       // [fg_cap][4]
+    int* d_counts = nullptr;          // [fg_cap + 1]
+    int fg_cap = 0;
     double* d_hyp = nullptr;          // [batch][12]
     int* d_zero = nullptr;            // [max(batch, S*children)] parent indices: all 0
     double* d_score = nullptr;        // [max_seeds * n_rotations] coarse scores
@@ -446,6 +633,8 @@ struct rbs_find {
     hipEvent_t ev[5] = {};
     // the last find
     bool have = false;
+    bool fg_ran = false;              // with step 1b
+    double plane[rbf::kFgRecord] = {};
     int n_seeds = 0, n_valid = 0, n_cand = 0, n_surv = 0;
     long n_hyp = 0;
     float ms[5] = {};
@@ -470,6 +659,22 @@ int32_t ffail(rbs_find* f, int32_t code, const std::string& msg) { f->err = msg;
         const int32_t rc_ = (call);                                                                               \
         if (rc_ != RBS_OK) { (f)->err = std::string("scoring handle: ") + (h)->err; return rc_; }                 \
     } while (0)
+
+constexpr size_t info_bytes = sizeof(int) * 4 + sizeof(double) * rbf::kFgRecord;
+
+const char* foreground_check(const rbs_find_foreground* g)
+{
+    if (g->plane_trials < 1 || g->plane_trials > rbf::kFgMaxTrials) return "find: plane_trials outside 1..4096";
+    if (!(g->ransac_sigmas >= 0.0) || !std::isfinite(g->ransac_sigmas) || !(g->mask_sigmas >= 0.0) || !std::isfinite(g->mask_sigmas))
+        return "find: ransac_sigmas and mask_sigmas must be finite and >= 0";
+    if (!(g->min_inlier_fraction >= 0.0) || !(g->min_inlier_fraction <= 1.0)) return "find: min_inlier_fraction outside [0, 1]";
+    return nullptr;
+}
+
+rbf::FgModel fg_model(const rbs_find* f)
+{
+    return rbf::FgModel{f->p.min_depth, f->p.max_depth, f->s->cfg.model_sigma, f->s->cfg.sigma_factor};
+}
 
 const char* find_check(const rbs_find_params* p)
 {
@@ -582,7 +787,8 @@ void rbs_find_destroy(rbs_find* f)
                     (void*)f->d_zero, (void*)f->d_score, (void*)f->d_tk_s[0], (void*)f->d_tk_s[1], (void*)f->d_tk_i[0],
                     (void*)f->d_tk_i[1], (void*)f->d_cand_pose, (void*)f->d_cand_score, (void*)f->d_cand_idx, (void*)f->d_kept,
                     (void*)f->d_surv, (void*)f->d_surv_score, (void*)f->d_surv0, (void*)f->d_surv0_score, (void*)f->d_surv0_idx,
-                    (void*)f->d_child, (void*)f->d_child_score, (void*)f->d_final, (void*)f->d_final_score, (void*)f->d_final_idx})
+                    (void*)f->d_child, (void*)f->d_child_score, (void*)f->d_final, (void*)f->d_final_score, (void*)f->d_final_idx,
+                    (void*)f->d_seedframe, (void*)f->d_planes, (void*)f->d_counts})
         if (q) (void)hipFree(q);
     if (f->h_frame) (void)hipHostFree(f->h_frame);
     if (f->h_info) (void)hipHostFree(f->h_info);
@@ -647,8 +853,8 @@ int32_t rbs_find_create(rbs_handle* sensor, const rbs_find_params* p, rbs_find**
         hipHostMalloc(&f->h_frame, sizeof(float) * (size_t)rows * cols, hipHostMallocDefault) != hipSuccess ||
         hipMalloc(&f->d_cells, sizeof(int) * rbf::seed_cells(f->crows, f->ccols, p->seed_stride)) != hipSuccess ||
         hipMalloc(&f->d_seeds, sizeof(double) * 4 * (size_t)p->max_seeds) != hipSuccess ||
-        hipMalloc(&f->d_info, sizeof(int) * 4) != hipSuccess ||
-        hipHostMalloc(&f->h_info, sizeof(int) * 4, hipHostMallocDefault) != hipSuccess ||
+        hipMalloc(&f->d_info, info_bytes) != hipSuccess ||
+        hipHostMalloc(&f->h_info, info_bytes, hipHostMallocDefault) != hipSuccess ||
         hipMalloc(&f->d_hyp, sizeof(double) * 12 * (size_t)p->batch) != hipSuccess ||
         hipMalloc(&f->d_zero, sizeof(int) * (size_t)std::max(p->batch, nch)) != hipSuccess ||
         hipMemset(f->d_zero, 0, sizeof(int) * (size_t)std::max(p->batch, nch)) != hipSuccess ||
@@ -708,16 +914,33 @@ int32_t rbs_find_run(rbs_find* f, const float* frame, int32_t k, double* poses, 
     RBF_HIP(f, hipEventRecord(f->ev[0], st));
     RBF_HIP(f, hipMemcpyAsync(f->d_full, f->h_frame, sizeof(float) * npx, hipMemcpyHostToDevice, st));
     rbf::launch_subsample(st, f->d_full, s->cols, f->d_coarse, f->crows, f->ccols, f->f);
-    rbf::launch_seeds(st, f->d_coarse, f->crows, f->ccols, p.seed_stride, p.min_depth, p.max_depth, p.max_seeds, f->d_cells, f->d_seeds,
-                      f->d_info);
+    const bool fg = f->fg.enabled != 0;
+    double* d_rec = reinterpret_cast<double*>(f->d_info + 4);
+    if (fg) {   // step 1b: the seeds come from what stands in front of the dominant plane (scoring keeps the whole frames)
+        const rbf::FgModel M = fg_model(f);
+        const int T = f->fg.plane_trials;
+        rbf::launch_plane_trials(st, f->d_coarse, f->crows, f->ccols, M, (unsigned long long)p.seed, T, f->d_planes);
+        rbf::launch_plane_count(st, f->d_coarse, f->crows, f->ccols, M, f->d_planes, T, f->fg.ransac_sigmas, f->d_counts);
+        rbf::launch_plane_best(st, f->d_planes, f->d_counts, T, f->fg.min_inlier_fraction, d_rec);
+        rbf::launch_mask(st, f->d_coarse, f->crows, f->ccols, M, d_rec, f->fg.mask_sigmas, f->d_seedframe);
+        rbf::launch_plane_count(st, f->d_seedframe, f->crows, f->ccols, M, nullptr, 0, 0.0, f->d_info + 3);
+    }
+    rbf::launch_seeds(st, fg ? f->d_seedframe : f->d_coarse, f->crows, f->ccols, p.seed_stride, p.min_depth, p.max_depth, p.max_seeds,
+                      f->d_cells, f->d_seeds, f->d_info);
     RBF_HIP(f, hipGetLastError());
     RBF_RC(f, f->coarse, rbs_set_observation_device(f->coarse, f->d_coarse, st));
     RBF_RC(f, f->full, rbs_set_observation_device(f->full, f->d_full, st));
-    RBF_HIP(f, hipMemcpyAsync(f->h_info, f->d_info, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+    RBF_HIP(f, hipMemcpyAsync(f->h_info, f->d_info, fg ? info_bytes : 2 * sizeof(int), hipMemcpyDeviceToHost, st));
     RBF_HIP(f, hipEventRecord(f->ev[1], st));
     RBF_HIP(f, hipStreamSynchronize(st));
     f->n_seeds = f->h_info[0];
     f->n_valid = f->h_info[1];
+    f->fg_ran = fg;
+    for (double& v : f->plane) v = 0.0;
+    if (fg) {
+        std::memcpy(f->plane, f->h_info + 4, sizeof(f->plane));
+        f->plane[7] = f->plane[5] - (double)f->h_info[3];   // valid coarse pixels that the seeding frame no longer has
+    }
     f->n_hyp = (long)f->n_seeds * p.n_rotations;
     f->n_cand = f->n_surv = 0;
     for (float& m : f->ms) m = 0.f;
@@ -871,6 +1094,68 @@ int32_t rbs_find_get_stage(rbs_find* f, int32_t stage, int32_t round, double* po
         default:
             return ffail(f, RBS_ERR_INVALID_ARGUMENT, "find_get_stage: bad stage");
     }
+}
+
+void rbs_find_default_foreground(rbs_find_foreground* g)
+{
+    if (!g) return;
+    g->enabled = 1;
+    g->plane_trials = 256;
+    g->ransac_sigmas = 2.0;
+    g->mask_sigmas = 5.0;
+    g->min_inlier_fraction = 0.2;
+}
+
+int32_t rbs_find_set_foreground(rbs_find* f, const rbs_find_foreground* g)
+{
+    if (!f) return RBS_ERR_INVALID_ARGUMENT;
+    if (!g || g->enabled == 0) {
+        f->fg.enabled = 0;
+        return RBS_OK;
+    }
+    if (const char* bad = foreground_check(g)) return ffail(f, RBS_ERR_INVALID_ARGUMENT, bad);
+    RBF_HIP(f, hipSetDevice(f->s->device));
+    if (!f->d_seedframe) RBF_HIP(f, hipMalloc(&f->d_seedframe, sizeof(float) * (size_t)f->crows * f->ccols));
+    if (g->plane_trials > f->fg_cap) {   // (the old arrays may still be read by a find's kernels: none is in flight after rbs_find_run)
+        double* planes = nullptr;
+        int* counts = nullptr;
+        hipError_t e = hipMalloc(&planes, sizeof(double) * 4 * (size_t)g->plane_trials);
+        if (e == hipSuccess) e = hipMalloc(&counts, sizeof(int) * ((size_t)g->plane_trials + 1));
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            if (planes) (void)hipFree(planes);
+            return ffail(f, RBS_ERR_OUT_OF_MEMORY, "find_set_foreground: device memory");
+        }
+        RBF_HIP(f, hipStreamSynchronize(f->st));
+        if (f->d_planes) (void)hipFree(f->d_planes);
+        if (f->d_counts) (void)hipFree(f->d_counts);
+        f->d_planes = planes;
+        f->d_counts = counts;
+        f->fg_cap = g->plane_trials;
+    }
+    f->fg = *g;
+    f->fg.enabled = 1;
+    return RBS_OK;
+}
+
+int32_t rbs_find_get_plane(rbs_find* f, double* out8)
+{
+    if (!f) return RBS_ERR_INVALID_ARGUMENT;
+    if (!out8 || !f->have) return ffail(f, RBS_ERR_INVALID_ARGUMENT, "find_get_plane: no find yet, or a null pointer");
+    for (int i = 0; i < rbf::kFgRecord; ++i) out8[i] = f->plane[i];
+    return RBS_OK;
+}
+
+int32_t rbs_find_get_seed_frame(rbs_find* f, float* out, int64_t* n)
+{
+    if (!f) return RBS_ERR_INVALID_ARGUMENT;
+    if (!n) return ffail(f, RBS_ERR_INVALID_ARGUMENT, "find_get_seed_frame: n is NULL");
+    if (!f->have) return ffail(f, RBS_ERR_INVALID_ARGUMENT, "find_get_seed_frame: no find yet");
+    *n = (int64_t)f->crows * f->ccols;
+    if (!out) return RBS_OK;
+    RBF_HIP(f, hipSetDevice(f->s->device));
+    RBF_HIP(f, hipMemcpy(out, f->fg_ran ? f->d_seedframe : f->d_coarse, sizeof(float) * (size_t)*n, hipMemcpyDeviceToHost));
+    return RBS_OK;
 }
 
 int32_t rbs_find_stage_ms(rbs_find* f, float* out5)

@@ -16,6 +16,7 @@
 // (rbf::launch_*, the ones rbs_find_run itself calls): tests/test_gpu_finder_kernels.py.  Every output array there is IN and
 // OUT and `tail` elements (rows) longer than the kernel may write: the caller fills it with a sentinel, the probe copies it to
 // the device before the launch and back after it, so what the kernel left alone -- the tail included -- is seen.
+// rbs_test_findfg_* are the same for step 1b's four launch helpers: tests/test_gpu_find_foreground_kernels.py.
 //
 // Entry points (rbs_test_*): host arrays in, host arrays out, synchronous on the current device.  Null pointers and n < 0 (or
 // n > kProbeMax) are RBS_ERR_INVALID_ARGUMENT, n == 0 is RBS_OK and touches nothing, a HIP failure is RBS_ERR_HIP.
@@ -622,6 +623,82 @@ int32_t rbs_test_find_order(const double* surv, const double* surv_score, const 
     if (B.err == hipSuccess) { rbf::launch_order(nullptr, dsurv, dscore, dorder, S, dout, dout_score); B.ran(); }
     B.fetch(out_pose, dout, 12 * K);
     B.fetch(out_score, dout_score, K);
+    return B.status();
+}
+
+// ---- step 1b, the foreground (rbs_findfg_*_kernel): tests/find_fg_probes.py, tests/test_gpu_find_foreground_kernels.py
+// planes [trials + tail][4]
+int32_t rbs_test_findfg_trials(const float* frame, int32_t rows, int32_t cols, double dmin, double dmax, uint64_t seed, int32_t trials,
+                               double* planes, int64_t tail)
+{
+    namespace pr = rbs::probe;
+    if (!frame || !planes || rows < 0 || cols < 0 || trials < 0 || trials > rbf::kFgMaxTrials || tail < 0 ||
+        pr::probe_refused((int64_t)rows * cols) || pr::probe_refused(tail))
+        return RBS_ERR_INVALID_ARGUMENT;
+    if ((int64_t)rows * cols == 0 || trials == 0) return RBS_OK;
+    const size_t m = 4 * ((size_t)trials + (size_t)tail);
+    pr::Buffers B;
+    const float* dframe = B.make<float>((size_t)rows * cols, frame);
+    double* dplanes = B.make<double>(m, planes);
+    const rbf::FgModel M{dmin, dmax, 0.0, 0.0};
+    if (B.err == hipSuccess) { rbf::launch_plane_trials(nullptr, dframe, rows, cols, M, (unsigned long long)seed, trials, dplanes); B.ran(); }
+    B.fetch(planes, dplanes, m);
+    return B.status();
+}
+
+// planes [trials][4]; counts [trials + 1 + tail].  trials == 0: the valid pixels alone (planes may be NULL)
+int32_t rbs_test_findfg_count(const float* frame, int32_t rows, int32_t cols, double dmin, double dmax, double model_sigma,
+                              double sigma_factor, const double* planes, int32_t trials, double ransac_sigmas, int32_t* counts, int64_t tail)
+{
+    namespace pr = rbs::probe;
+    if (!frame || !counts || (trials > 0 && !planes) || rows < 0 || cols < 0 || trials < 0 || trials > rbf::kFgMaxTrials || tail < 0 ||
+        pr::probe_refused((int64_t)rows * cols) || pr::probe_refused(tail))
+        return RBS_ERR_INVALID_ARGUMENT;
+    if ((int64_t)rows * cols == 0) return RBS_OK;
+    const size_t m = (size_t)trials + 1 + (size_t)tail;
+    pr::Buffers B;
+    const float* dframe = B.make<float>((size_t)rows * cols, frame);
+    const double* dplanes = trials > 0 ? B.make<double>(4 * (size_t)trials, planes) : nullptr;
+    int* dcounts = B.make<int>(m, counts);
+    const rbf::FgModel M{dmin, dmax, model_sigma, sigma_factor};
+    if (B.err == hipSuccess) { rbf::launch_plane_count(nullptr, dframe, rows, cols, M, dplanes, trials, ransac_sigmas, dcounts); B.ran(); }
+    B.fetch(counts, dcounts, m);
+    return B.status();
+}
+
+// planes [trials][4], counts [trials + 1]; rec [8 + tail]
+int32_t rbs_test_findfg_best(const double* planes, const int32_t* counts, int32_t trials, double min_inlier_fraction, double* rec, int64_t tail)
+{
+    namespace pr = rbs::probe;
+    if (!planes || !counts || !rec || trials < 0 || trials > rbf::kFgMaxTrials || tail < 0 || pr::probe_refused(tail))
+        return RBS_ERR_INVALID_ARGUMENT;
+    if (trials == 0) return RBS_OK;
+    const size_t m = (size_t)rbf::kFgRecord + (size_t)tail;
+    pr::Buffers B;
+    const double* dplanes = B.make<double>(4 * (size_t)trials, planes);
+    const int* dcounts = B.make<int>((size_t)trials + 1, counts);
+    double* drec = B.make<double>(m, rec);
+    if (B.err == hipSuccess) { rbf::launch_plane_best(nullptr, dplanes, dcounts, trials, min_inlier_fraction, drec); B.ran(); }
+    B.fetch(rec, drec, m);
+    return B.status();
+}
+
+// rec [8]; out [rows * cols + tail]
+int32_t rbs_test_findfg_mask(const float* frame, int32_t rows, int32_t cols, double model_sigma, double sigma_factor, const double* rec,
+                             double mask_sigmas, float* out, int64_t tail)
+{
+    namespace pr = rbs::probe;
+    if (!frame || !rec || !out || rows < 0 || cols < 0 || tail < 0 || pr::probe_refused((int64_t)rows * cols) || pr::probe_refused(tail))
+        return RBS_ERR_INVALID_ARGUMENT;
+    if ((int64_t)rows * cols == 0) return RBS_OK;
+    const size_t n = (size_t)rows * cols, m = n + (size_t)tail;
+    pr::Buffers B;
+    const float* dframe = B.make<float>(n, frame);
+    const double* drec = B.make<double>((size_t)rbf::kFgRecord, rec);
+    float* dout = B.make<float>(m, out);
+    const rbf::FgModel M{0.0, 0.0, model_sigma, sigma_factor};
+    if (B.err == hipSuccess) { rbf::launch_mask(nullptr, dframe, rows, cols, M, drec, mask_sigmas, dout); B.ran(); }
+    B.fetch(out, dout, m);
     return B.status();
 }
 

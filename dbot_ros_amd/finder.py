@@ -8,7 +8,9 @@ class undoes center_object_frame, so its states go straight into tracker.initial
 """
 import ctypes as C
 import math
+from collections import namedtuple
 from dataclasses import dataclass, fields
+from typing import Optional
 
 import numpy as np
 
@@ -25,8 +27,38 @@ class FindResult:
     scores: np.ndarray    # [K] log-likelihoods at the sensor's resolution
 
 
+# the dominant plane of the last find (step 1b): 1 / z = a u + b v + c over the coarse pixels (u, v)
+Plane = namedtuple("Plane", "accepted a b c count n_valid trial masked")
+
+
 class ObjectFinder:
-    """ObjectFinder(sensor, object_model, params).find(frame=None) -> FindResult."""
+    """ObjectFinder(sensor, object_model, params, foreground=None).find(frame=None) -> FindResult."""
+
+    @dataclass
+    class Foreground:
+        """Step 1b (rbs_find_foreground): seeds only from what stands in front of the frame's dominant depth plane."""
+        enabled: bool = True
+        plane_trials: int = 256
+        ransac_sigmas: float = 2.0
+        mask_sigmas: float = 5.0
+        min_inlier_fraction: float = 0.2
+
+        @classmethod
+        def from_mapping(cls, m):
+            g = cls()
+            names = [f.name for f in fields(cls)]
+            for k, v in dict(m or {}).items():
+                if k not in names:
+                    raise ValueError(f"object_finder/foreground/{k}: unknown key (one of {sorted(names)})")
+                cur = getattr(g, k)
+                setattr(g, k, bool(v) if isinstance(cur, bool) else int(v) if isinstance(cur, int) else float(v))
+            return g
+
+        def c_params(self):
+            g = _capi.RbsFindForeground()
+            for f in fields(self):
+                setattr(g, f.name, int(getattr(self, f.name)) if f.name in ("enabled", "plane_trials") else getattr(self, f.name))
+            return g
 
     @dataclass
     class Parameters:
@@ -49,13 +81,16 @@ class ObjectFinder:
         batch: int = 65536
         seed: int = 0
         min_score: float = -math.inf
+        foreground: Optional["ObjectFinder.Foreground"] = None   # step 1b; None: off
 
         @classmethod
         def from_rosparam(cls, tree):
             """From the optional `object_finder:` mapping of the merged rosparam tree; every key is
-            optional (angles in degrees: nms_angle_deg, sigma_angle_deg)."""
+            optional (angles in degrees: nms_angle_deg, sigma_angle_deg; foreground: a mapping of Foreground's fields)."""
             m = dict((tree or {}).get("object_finder") or {})
             p = cls()
+            if "foreground" in m:
+                p.foreground = ObjectFinder.Foreground.from_mapping(m.pop("foreground"))
             for k in ("nms_angle", "sigma_angle"):
                 if k + "_deg" in m:
                     m[k] = math.radians(float(m.pop(k + "_deg")))
@@ -69,10 +104,11 @@ class ObjectFinder:
         def c_params(self):
             p = _capi.RbsFindParams()
             for f in fields(self):
-                setattr(p, f.name, getattr(self, f.name))
+                if f.name != "foreground":
+                    setattr(p, f.name, getattr(self, f.name))
             return p
 
-    def __init__(self, sensor, object_model, params=None):
+    def __init__(self, sensor, object_model, params=None, foreground=None):
         self._lib = _capi.load()
         self.sensor = sensor
         self.params = params or ObjectFinder.Parameters()
@@ -84,6 +120,14 @@ class ObjectFinder:
             self._f = C.c_void_p()
             sensor._check(rc)
         sensor._register_dependent(self)   # the finder borrows the sensor handle
+        self.foreground = None
+        foreground = self.params.foreground if foreground is None else foreground
+        if foreground is not None:
+            try:
+                self.set_foreground(foreground)
+            except Exception:
+                self.close()
+                raise
 
     def close(self):
         if getattr(self, "_f", None) is not None and self._f.value:
@@ -147,6 +191,32 @@ class ObjectFinder:
         self._check(self._lib.rbs_find_get_stage(self._f, stage, round, poses.ctypes.data_as(dp), scores.ctypes.data_as(dp),
                                                  idx.ctypes.data_as(lp), C.byref(n), None))
         return poses, scores, idx, info
+
+    def set_foreground(self, foreground=None):
+        """Step 1b for the finds from the next one on; None (or enabled = False): off.  Bad values raise, and the
+        previous setting stays."""
+        if foreground is None or not foreground.enabled:
+            self._check(self._lib.rbs_find_set_foreground(self._f, None))
+            self.foreground = None
+            return
+        g = foreground.c_params()
+        self._check(self._lib.rbs_find_set_foreground(self._f, C.byref(g)))
+        self.foreground = foreground
+
+    def plane(self):
+        """The last find's dominant plane (rbs_find_get_plane); the stage off: all zeros."""
+        out = np.zeros(8)
+        self._check(self._lib.rbs_find_get_plane(self._f, out.ctypes.data_as(C.POINTER(C.c_double))))
+        return Plane(bool(out[0]), float(out[1]), float(out[2]), float(out[3]), int(out[4]), int(out[5]), int(out[6]), int(out[7]))
+
+    def seed_frame(self):
+        """The last find's seeding frame [coarse rows, coarse cols] float32 (the stage off: the coarse frame)."""
+        n = C.c_int64()
+        self._check(self._lib.rbs_find_get_seed_frame(self._f, None, C.byref(n)))
+        out = np.zeros(int(n.value), dtype=np.float32)
+        self._check(self._lib.rbs_find_get_seed_frame(self._f, out.ctypes.data_as(C.POINTER(C.c_float)), C.byref(n)))
+        _, _, _, info = self.stage(_capi.RBS_FIND_SEEDS)
+        return out.reshape(int(info[0]), int(info[1]))
 
     def stage_ms(self):
         """Device ms of the last find: frame + seeds, coarse scoring, selection, refinement, whole find."""

@@ -32,6 +32,18 @@ public:
         Parameters() { rbs_find_default_params(this); }
     };
 
+    /// rbs_find_foreground with the library's defaults, enabled (step 1b: seeds from what stands in front of the dominant plane).
+    struct Foreground : rbs_find_foreground {
+        Foreground() { rbs_find_default_foreground(this); }
+    };
+
+    /// The last find's dominant plane, 1 / z = a u + b v + c over the coarse pixels (rbs_find_get_plane).
+    struct Plane {
+        bool accepted = false;
+        Real a = 0, b = 0, c = 0;
+        long count = 0, n_valid = 0, trial = 0, masked = 0;
+    };
+
     struct Result {
         bool found = false;
         std::vector<State> states;       // best first
@@ -70,6 +82,37 @@ public:
             r.states.push_back(s);
         }
         return r;
+    }
+
+    /// Step 1b for the finds from the next one on; nullptr (or enabled == 0): off.  Bad values throw, the previous setting stays.
+    void set_foreground(const rbs_find_foreground* g)
+    {
+        if (rbs_find_set_foreground(f_, g) != RBS_OK)
+            throw std::runtime_error(std::string("ObjectFinder::set_foreground: ") + rbs_find_last_error(f_));
+    }
+
+    Plane plane()
+    {
+        double o[8];
+        if (rbs_find_get_plane(f_, o) != RBS_OK) throw std::runtime_error(std::string("ObjectFinder::plane: ") + rbs_find_last_error(f_));
+        Plane p;
+        p.accepted = o[0] != 0.0;
+        p.a = o[1]; p.b = o[2]; p.c = o[3];
+        p.count = static_cast<long>(o[4]); p.n_valid = static_cast<long>(o[5]);
+        p.trial = static_cast<long>(o[6]); p.masked = static_cast<long>(o[7]);
+        return p;
+    }
+
+    /// The last find's seeding frame at the coarse resolution (the stage off: the coarse frame).
+    std::vector<float> seed_frame()
+    {
+        int64_t n = 0;
+        if (rbs_find_get_seed_frame(f_, nullptr, &n) != RBS_OK)
+            throw std::runtime_error(std::string("ObjectFinder::seed_frame: ") + rbs_find_last_error(f_));
+        std::vector<float> out(static_cast<size_t>(n));
+        if (rbs_find_get_seed_frame(f_, out.data(), &n) != RBS_OK)
+            throw std::runtime_error(std::string("ObjectFinder::seed_frame: ") + rbs_find_last_error(f_));
+        return out;
     }
 
     rbs_find* handle() { return f_; }

@@ -649,6 +649,23 @@ int32_t rbs_gauss_result(rbs_gauss* g, double* out_state, double* out_cov);
  *   1 coarse frame  the frame sub-sampled by f = coarse_downsampling (every f-th pixel of every f-th row, as
  *                   ri::to_eigen_vector; K's top two rows divided by f); 0: the largest of {1, 2, 4} that leaves
  *                   >= 160 columns.
+ *   1b foreground   opt-in (rbs_find_set_foreground; off by default): the dominant plane of the coarse frame is found and
+ *                   the seeds of step 2 are taken from a SEEDING FRAME, the coarse frame with every pixel that is not
+ *                   strictly in front of that plane set to NaN.  Scoring (steps 4, 6) still reads the whole frames.  All
+ *                   of it is binary64 with + - * / and comparisons only, in the order written, on the device.  (u, v) a
+ *                   coarse pixel's column and row, d its depth, valid: min_depth <= d <= max_depth (step 2's test),
+ *                   sigma(z) = model_sigma + sigma_factor (z z) of the sensor's rbs_config, npx the coarse pixels.
+ *                   Trial t < plane_trials draws pixels i_k = (uint64(word_k) npx) >> 32, k = 0, 1, 2, from the words of
+ *                   Philox4x32-10 (key = seed, counter words (t, 0, 0, 0xFFFFFFFF): step 6's last word is a round <= 64).
+ *                   D = (u1 - u0)(v2 - v0) - (u2 - u0)(v1 - v0).  A trial is void when a pixel is not valid or D == 0;
+ *                   else, q_k = 1 / d_k, its plane in inverse depth is a = ((q1 - q0)(v2 - v0) - (q2 - q0)(v1 - v0)) / D,
+ *                   b = ((u1 - u0)(q2 - q0) - (u2 - u0)(q1 - q0)) / D, c = (q0 - a u0) - b v0.  Its count: the valid coarse
+ *                   pixels (all, not the seed grid) with w = (a u + b v) + c > 0 and, z = 1 / w,
+ *                   |d - z| <= ransac_sigmas sigma(z); a void trial counts -1.  The highest count wins, ties to the lowest
+ *                   t; the plane is accepted when count >= 3 and count >= min_inlier_fraction n_valid.  The chosen plane
+ *                   IS that trial's three-point plane: there is no least-squares refit.  A pixel of the seeding frame
+ *                   keeps its depth when no plane is accepted, or w <= 0, or z - d > mask_sigmas sigma(z); every other
+ *                   pixel is NaN.  *info[4] of rbs_find_get_stage then counts the seed pixels of the seeding frame.
  *   2 seeds         coarse pixels (u, v) = (j s, i s), s = seed_stride, whose depth d is finite and inside
  *                   [min_depth, max_depth], in row-major order; n of them are thinned to every step-th,
  *                   step = ceil(n / max_seeds).  Seed -> t = d K^-1 (u, v, 1) + depth_offset r, r the unit
@@ -736,9 +753,28 @@ enum { RBS_FIND_SEEDS = 0, RBS_FIND_COARSE = 1, RBS_FIND_CANDIDATES = 2, RBS_FIN
        RBS_FIND_RESULT = 5 };
 int32_t rbs_find_get_stage(rbs_find* f, int32_t stage, int32_t round, double* poses, double* scores, int64_t* indices,
                            int64_t* n, double* info);
-/* Device time of the last find's stages in ms (HIP events): [0] frame + seeds, [1] coarse scoring, [2] selection
+/* Device time of the last find's stages in ms (HIP events): [0] frame + seeds (step 1b included), [1] coarse scoring, [2] selection
  * (top-k + suppression), [3] refinement, [4] the whole find. */
 int32_t rbs_find_stage_ms(rbs_find* f, float* out5);
+/* Step 1b, the foreground.  Memory: one coarse frame and plane_trials records of 36 bytes, allocated when the stage is
+ * first switched on. */
+typedef struct rbs_find_foreground {
+    int32_t enabled;               /* 0: the stage is off (a new finder)                                            */
+    int32_t plane_trials;          /* 256 (1 .. 4 096)                                                              */
+    double ransac_sigmas;          /* 2: a trial's inliers lie within this many sigma(z) of its plane               */
+    double mask_sigmas;            /* 5: a seed pixel stands more than this many sigma(z) in front of the plane     */
+    double min_inlier_fraction;    /* 0.2 of the valid coarse pixels, in [0, 1]                                     */
+} rbs_find_foreground;
+/* The defaults above with enabled = 1, stated once. */
+void rbs_find_default_foreground(rbs_find_foreground* g);
+/* The setting of the finds from the next rbs_find_run on.  NULL or enabled == 0: the stage is off, and a find is bit for
+ * bit that of a finder never configured.  Bad values: RBS_ERR_INVALID_ARGUMENT, and the previous setting stays. */
+int32_t rbs_find_set_foreground(rbs_find* f, const rbs_find_foreground* g);
+/* The last find's plane: out [8] := accepted (0 / 1), a, b, c, count, valid coarse pixels, trial, valid coarse pixels
+ * masked.  The stage off: all 0.  No trial with a plane: count -1, trial 0, a = b = c = 0. */
+int32_t rbs_find_get_plane(rbs_find* f, double* out8);
+/* The last find's seeding frame (the stage off: the coarse frame): *n := coarse rows * cols; out (may be NULL) [*n]. */
+int32_t rbs_find_get_seed_frame(rbs_find* f, float* out, int64_t* n);
 /* Message of the last error on this finder. Never NULL. */
 const char* rbs_find_last_error(const rbs_find* f);
 

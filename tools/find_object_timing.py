@@ -4,7 +4,8 @@ scoring.  Prints ONE JSON line:
     {"tool": "find_object_timing", "cases": [{"case", "size", "coarse", "hypotheses", "children", "ms_per_find",
       "stage_ms": {"frame_seeds", "coarse", "selection", "refinement"}, "hypotheses_per_s", "oracle_s",
       "found": {"dt_mm", "iou", "score", "truth_score"}, "nearest_candidate": {"dt_mm", "deg"},
-      "nearest_survivor": {"dt_mm", "deg"}}, ...]}
+      "nearest_survivor": {"dt_mm", "deg"}, "scene_seed", "seed_stride", "foreground", "plane": {...} | null,
+      "seeds_by_label": {"plane", "object", "occluder"}, "meets_bar"}, ...]}
 
 Cases: M1, M2, M3 at 640x480 and M4 at 1280x960, the header's default parameters; one synth.make_frame frame per case
 (background plane, occluder, noise, 5 % NaN) with the object at a seeded random rotation, z in 0.55-0.9 m.
@@ -13,7 +14,13 @@ library's HIP events of the last find.  oracle_s: the CPU oracle's (EAGER, one c
 resolution, measured on --oracle-poses poses, times the hypothesis count, plus the same at full resolution times the
 refinement's children.  nearest_candidate / nearest_survivor: the coarse stage's closest pose to the truth (translation,
 then rotation angle of that pose) -- whether the search had the object in hand before the refinement.
-Usage: python tools/find_object_timing.py [--finds N] [--oracle-poses P] [--cases m1,m2,m3,m4]
+--foreground switches step 1b on (the library's default setting) and --seed-stride sets seed_stride; --scene-seeds lists the
+scenes' seeds (the accuracy bar's six scenes: --cases m1,m2,m3 --scene-seeds 101,102).  plane: the dominant plane the find
+took away (rbs_find_get_plane); seeds_by_label: the find's seeds on the background plane, the object and the occluder (labels
+from the noise-free scene); meets_bar: translation < 1 cm, IoU >= 0.85, score >= 0.98 x the truth's.  --oracle-poses 0 skips
+the oracle's timing.
+Usage: python tools/find_object_timing.py [--finds N] [--oracle-poses P] [--cases m1,m2,m3,m4] [--foreground] [--seed-stride S]
+                                          [--scene-seeds 101,102]
 """
 import os
 
@@ -49,7 +56,18 @@ def scene(sensor, cam, seed):
     u, v = rng.uniform(0.3, 0.7) * cam.cols, rng.uniform(0.3, 0.7) * cam.rows
     truth = np.concatenate([R.ravel(), [(u - K[0, 2]) / K[0, 0] * z, (v - K[1, 2]) / K[1, 1] * z, z]])
     d = sensor.render_depth(truth)
-    return truth, synth.make_frame(np.where(np.isfinite(d), d, np.inf), cam.rows, cam.cols, rng)
+    d = np.where(np.isfinite(d), d, np.inf)
+    return truth, synth.make_frame(d, cam.rows, cam.cols, rng), scene_labels(d, cam.rows, cam.cols)
+
+
+def scene_labels(d, rows, cols):
+    """0 background plane, 1 object, 2 occluder, from the noise-free scene."""
+    clean = synth.make_frame(d, rows, cols, None, noise=False, nan_frac=0).reshape(rows, cols)
+    bare = synth.make_frame(d, rows, cols, None, noise=False, nan_frac=0, occluder=False).reshape(rows, cols)
+    lab = np.zeros((rows, cols), dtype=np.int8)
+    lab[np.isfinite(d.reshape(rows, cols))] = 1
+    lab[clean != bare] = 2
+    return lab
 
 
 def nearest(poses, truth):
@@ -72,20 +90,23 @@ def oracle_s_per_pose(om, K, rows, cols, P, frame, poses):
     return s
 
 
-def run_case(name, finds, oracle_poses, seed=101):
+def run_case(name, finds, oracle_poses, seed=101, foreground=False, seed_stride=None):
     mesh, cols, rows = CASES[name]
     om, cam, P = sc.make_scene((mesh,), cols, rows, max_particles=1)
     with RbSensor(om, cam, P, max_particles=1) as sensor:
-        truth, frame = scene(sensor, cam, seed)
+        truth, frame, labels = scene(sensor, cam, seed)
         p = ObjectFinder.Parameters()
-        with ObjectFinder(sensor, om, p) as fnd:
+        if seed_stride:
+            p.seed_stride = seed_stride
+        with ObjectFinder(sensor, om, p, foreground=ObjectFinder.Foreground() if foreground else None) as fnd:
             fnd.find(frame)                                       # warm-up
             t0 = time.perf_counter()
             for _ in range(finds):
                 r = fnd.find(frame)
             ms = (time.perf_counter() - t0) / finds * 1e3
             st = fnd.stage_ms()
-            _, _, _, info = fnd.stage("seeds")
+            seeds, _, _, info = fnd.stage("seeds")
+            plane = fnd.plane()._asdict() if foreground else None
             cp, _, _, _ = fnd.stage("candidates")
             sp, _, _, _ = fnd.stage("survivors")
             kp, _, _, _ = fnd.stage("children", p.rounds - 1) if p.rounds else (np.zeros((0, 12)),) * 4
@@ -99,9 +120,12 @@ def run_case(name, finds, oracle_poses, seed=101):
     Kc = cam.camera_matrix.copy()
     Kc[:2] /= f
     coarse = frame.reshape(rows, cols)[: crows * f: f, : ccols * f: f].ravel()
-    sample = cp[:oracle_poses] if len(cp) else np.repeat(truth[None], oracle_poses, 0)
-    per_coarse = oracle_s_per_pose(om, Kc, crows, ccols, P, coarse, sample)
-    per_full = oracle_s_per_pose(om, cam.camera_matrix, rows, cols, P, frame, kp[: max(1, oracle_poses // 4)]) if len(kp) else 0.0
+    per_coarse = per_full = 0.0
+    if oracle_poses > 0:
+        sample = cp[:oracle_poses] if len(cp) else np.repeat(truth[None], oracle_poses, 0)
+        per_coarse = oracle_s_per_pose(om, Kc, crows, ccols, P, coarse, sample)
+        per_full = oracle_s_per_pose(om, cam.camera_matrix, rows, cols, P, frame, kp[: max(1, oracle_poses // 4)]) if len(kp) else 0.0
+    seed_labels = labels[: crows * f: f, : ccols * f: f].ravel()[seeds[:, 3].astype(np.int64)] if len(seeds) else np.zeros(0, dtype=np.int8)
     children = p.n_survivors * p.children * p.rounds
     found = None
     if best is not None:
@@ -109,12 +133,16 @@ def run_case(name, finds, oracle_poses, seed=101):
         found = {"dt_mm": round(float(np.linalg.norm(best[9:] - truth[9:])) * 1e3, 2),
                  "iou": round(float((a & b).sum() / max((a | b).sum(), 1)), 3),
                  "score": round(float(r.scores[0]), 1), "truth_score": round(truth_score, 1)}
+    meets = bool(found and found["dt_mm"] < 10.0 and found["iou"] >= 0.85 and r.scores[0] >= truth_score - 0.02 * abs(truth_score))
     return {"case": name, "size": [cols, rows], "coarse": [ccols, crows], "hypotheses": hyp, "children": children,
             "ms_per_find": round(ms, 2),
             "stage_ms": dict(zip(("frame_seeds", "coarse", "selection", "refinement"), (round(x, 3) for x in st[:4]))),
             "hypotheses_per_s": round(hyp / (st[1] * 1e-3)) if st[1] > 0 else None,
             "oracle_s": round(per_coarse * hyp + per_full * children, 1),
-            "found": found, "nearest_candidate": nearest(cp, truth), "nearest_survivor": nearest(sp, truth)}
+            "found": found, "nearest_candidate": nearest(cp, truth), "nearest_survivor": nearest(sp, truth),
+            "scene_seed": seed, "seed_stride": p.seed_stride, "foreground": bool(foreground), "plane": plane,
+            "seeds_by_label": dict(zip(("plane", "object", "occluder"), (int((seed_labels == k).sum()) for k in range(3)))),
+            "meets_bar": meets}
 
 
 def main():
@@ -122,8 +150,12 @@ def main():
     ap.add_argument("--finds", type=int, default=5)
     ap.add_argument("--oracle-poses", type=int, default=16)
     ap.add_argument("--cases", default="m1,m2,m3,m4")
+    ap.add_argument("--foreground", action="store_true")
+    ap.add_argument("--seed-stride", type=int, default=0)
+    ap.add_argument("--scene-seeds", default="101")
     a = ap.parse_args()
-    cases = [run_case(c, a.finds, a.oracle_poses) for c in a.cases.split(",")]
+    cases = [run_case(c, a.finds, a.oracle_poses, int(s), a.foreground, a.seed_stride) for c in a.cases.split(",")
+             for s in a.scene_seeds.split(",")]
     print(json.dumps({"tool": "find_object_timing", "cases": cases}))
 
 
