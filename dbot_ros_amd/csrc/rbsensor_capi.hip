@@ -392,6 +392,26 @@ size_t tiles_upper_bound(int cols, int rows, int max_w, int cap_px)
     return worst;
 }
 
+// The rectangles kernel of a call over P.n particles, one of its three launches (enqueue_loglikes and the test build's probe,
+// rbsensor_probes.hip, launch it through here).  frame_src: a device frame handed over right before the call -- its ingest
+// (keep: the copy to keep, or null; aux: its per-pixel terms, or null) rides on the same launch, aux_blocks blocks behind the
+// particles'; else deltas: the poses are composed from P.deltas_src first.
+void launch_prep(const DevParams& P, int* d_rects, int update, bool deltas, const float* frame_src, double* aux, float* pbg, float* keep,
+                 hipStream_t s)
+{
+    constexpr int ptb = 64 * rbs::kPrepPerBlock;
+    const unsigned prep_blocks = (unsigned)((P.n + rbs::kPrepPerBlock - 1) / rbs::kPrepPerBlock);
+    if (frame_src) {
+        const int aux_blocks = (aux || keep) ? (P.npx + ptb - 1) / ptb : 0;
+        hipLaunchKernelGGL(rbs::rbs_frame_prep_kernel, dim3((unsigned)aux_blocks + prep_blocks), dim3(ptb), 0, s, P, d_rects, update, frame_src,
+                           aux, pbg, keep, aux_blocks);
+    } else if (deltas) {
+        hipLaunchKernelGGL(rbs::rbs_prep_deltas_kernel, dim3(prep_blocks), dim3(ptb), 0, s, P, d_rects, update);
+    } else {
+        hipLaunchKernelGGL(rbs::rbs_prep_kernel, dim3(prep_blocks), dim3(ptb), 0, s, P, d_rects, update);
+    }
+}
+
 // ----------------------------------------------------------------------------- the frame section (rbs_handle::fr)
 // A hand-over: frame_begin, the entry point's own checks, frame_ready, one hand_over_*.  A reader: make_current (or, in
 // enqueue_loglikes, its pieces), then obs_frame / obs_aux.
@@ -1108,7 +1128,6 @@ int32_t enqueue_loglikes(rbs_handle* h, const double* d_poses, const int* d_indi
 #endif
     if (timed) RBS_HIP(h, hipEventRecord(h->ev_start[tslot], s));
     const dim3 block(rbs::kBlock);
-    const dim3 pgrid((unsigned)((n + rbs::kPrepPerBlock - 1) / rbs::kPrepPerBlock));
     // dense planes: prep + scan read only the poses and run ahead of the previous call's copy
     // kernel (which reads the other rectangle buffer); windowed planes: prep reads the windows
     // that copy kernel is still growing, so the join comes first (that copy is short)
@@ -1143,14 +1162,10 @@ int32_t enqueue_loglikes(rbs_handle* h, const double* d_poses, const int* d_indi
                        (h->precision == RBS_PRECISION_F32 || h->one_body_kernel);
     if (timed && fused) h->ring_update[tslot] = false;   // (no copy kernel to time: timing_summary's copy_kernel_ms is 0)
     if (const float* df = take_device_frame(h, s)) {   // a device frame pending on this stream rides on the rectangles kernel
-        constexpr int ptb = 64 * rbs::kPrepPerBlock;
-        const int aux_blocks = (h->d_aux || df != h->d_frame) ? (h->npx + ptb - 1) / ptb : 0;
-        hipLaunchKernelGGL(rbs::rbs_frame_prep_kernel, dim3((unsigned)(aux_blocks + (n + rbs::kPrepPerBlock - 1) / rbs::kPrepPerBlock)), dim3(ptb), 0, s, P,
-                           d_rects, update ? 1 : 0, df, h->d_aux, h->d_pbg, df == h->d_frame ? (float*)nullptr : h->d_frame, aux_blocks);
+        launch_prep(P, d_rects, update ? 1 : 0, false, df, h->d_aux, h->d_pbg, df == h->d_frame ? (float*)nullptr : h->d_frame, s);
     } else {
         if (int32_t rc = flush_device_frame(h, s)) return rc;
-        if (host_deltas) hipLaunchKernelGGL(rbs::rbs_prep_deltas_kernel, pgrid, dim3(64 * rbs::kPrepPerBlock), 0, s, P, d_rects, update ? 1 : 0);
-        else hipLaunchKernelGGL(rbs::rbs_prep_kernel, pgrid, dim3(64 * rbs::kPrepPerBlock), 0, s, P, d_rects, update ? 1 : 0);
+        launch_prep(P, d_rects, update ? 1 : 0, host_deltas, nullptr, nullptr, nullptr, nullptr, s);
     }
     RBS_HIP(h, hipGetLastError());
     if (sample_area) {

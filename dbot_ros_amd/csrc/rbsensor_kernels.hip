@@ -389,12 +389,17 @@ __device__ inline Rect bodies_rect(const DevParams& P, const double* __restrict_
     const int lane = threadIdx.x & 63, stride = 64;
     const float fx = (float)P.fx, fy = (float)P.fy, cx = (float)P.cx, cy = (float)P.cy;
     float umin = INFINITY, umax = -INFINITY, vmin = INFINITY, vmax = -INFINITY, zmin = INFINITY, tabs = 0.f;
+    bool finite = true;
     for (int b = b_first; b < b_last; ++b) {
         const double* Rt = pose + 12 * b;
         const float r0 = (float)Rt[0], r1 = (float)Rt[1], r2 = (float)Rt[2], r3 = (float)Rt[3], r4 = (float)Rt[4],
                     r5 = (float)Rt[5], r6 = (float)Rt[6], r7 = (float)Rt[7], r8 = (float)Rt[8];
         const float tx = (float)Rt[9], ty = (float)Rt[10], tz = (float)Rt[11];
         tabs = fmaxf(tabs, fabsf(tx) + fabsf(ty) + fabsf(tz));
+        // (a NaN entry does not survive fmaxf, and one in the X or Y row alone leaves zmin finite and the extents at their
+        // initial +inf / -inf, whose difference -inf passes the tests below: every entry is asked directly)
+        finite = finite && (fabsf(r0) + fabsf(r1) + fabsf(r2) + fabsf(r3) + fabsf(r4) + fabsf(r5) + fabsf(r6) + fabsf(r7) + fabsf(r8) +
+                            fabsf(tx) + fabsf(ty) + fabsf(tz) < INFINITY);
         // eight vertex loads in flight per lane (the vertices sit in L2; one dependent load per
         // trip would leave this kernel, which the raster kernel waits for, latency bound)
 #ifndef RBS_RECT_LOADS
@@ -430,7 +435,7 @@ __device__ inline Rect bodies_rect(const DevParams& P, const double* __restrict_
     Rect r;
     // a vertex at or behind the camera plane (the rasterizer drops such triangles, but their
     // neighbours may project anywhere), or a pose that is not finite: the whole frame
-    const bool full = !(zmin > 1e-4f) || !(zmin < INFINITY) || !(tabs < INFINITY) ||
+    const bool full = !finite || !(zmin > 1e-4f) || !(zmin < INFINITY) || !(tabs < INFINITY) ||
                       !(umax - umin < INFINITY) || !(vmax - vmin < INFINITY);   // ... and the extents are -inf
     if (full) {
         r.x0 = 0; r.y0 = 0; r.x1 = P.cols; r.y1 = P.rows;

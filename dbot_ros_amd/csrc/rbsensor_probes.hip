@@ -18,6 +18,11 @@
 // the device before the launch and back after it, so what the kernel left alone -- the tail included -- is seen.
 // rbs_test_findfg_* are the same for step 1b's four launch helpers: tests/test_gpu_find_foreground_kernels.py.
 //
+// rbs_test_prep does the same for the rectangles kernel (rbsensor_kernels.hip prep_particles): it builds a DevParams from host
+// arrays -- no sensor handle, no mesh: the rectangle reads the vertices only -- and launches rbs_prep_kernel,
+// rbs_prep_deltas_kernel or rbs_frame_prep_kernel through launch_prep, the helper enqueue_loglikes itself calls:
+// tests/test_gpu_prep_kernels.py.
+//
 // Entry points (rbs_test_*): host arrays in, host arrays out, synchronous on the current device.  Null pointers and n < 0 (or
 // n > kProbeMax) are RBS_ERR_INVALID_ARGUMENT, n == 0 is RBS_OK and touches nothing, a HIP failure is RBS_ERR_HIP.
 namespace rbs {
@@ -699,6 +704,171 @@ int32_t rbs_test_findfg_mask(const float* frame, int32_t rows, int32_t cols, dou
     const rbf::FgModel M{0.0, 0.0, model_sigma, sigma_factor};
     if (B.err == hipSuccess) { rbf::launch_mask(nullptr, dframe, rows, cols, M, drec, mask_sigmas, dout); B.ran(); }
     B.fetch(out, dout, m);
+    return B.status();
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------- the rectangles kernel
+// One call's arrays.  Inputs are const; every output is IN and OUT, `tail` elements (rows) longer than the kernel may write, and
+// filled by the caller (sentinels; ctr_this, err and area_sum with the values the call starts from).
+//   route 0: poses_in [n][bodies][12] is copied to the device array `poses`
+//   route 1: ... to pinned host memory the kernel pulls it from (DevParams::poses_src)
+//   route 2: poses_in is [n + 1][bodies][6], the state deltas followed by the default poses, pinned (DevParams::deltas_src)
+// frame != null: the frame launch, whose other blocks write aux [rows * cols][4] (null: none) and keep [rows * cols] (null: none).
+// groups / strips / area_sum null: not allocated (DevParams::groups / strips / area_sum null).
+struct rbs_test_prep_io {
+    int32_t rows, cols, n_bodies, n;
+    double fx, fy, cx, cy;
+    const int32_t* vtx_begin;       // [n_bodies + 1]
+    const float* vtx;               // [vtx_begin[n_bodies]][4]
+    int32_t rect_align, tile_w, tile_h, tile_px;
+    int32_t windowed, slab_px, slots, update;
+    const int32_t* win_src;         // [slots][4]
+    const int32_t* rebase_box;      // [4] or null
+    int32_t route, pad0;
+    const double* poses_in;
+    const int32_t* indices;         // [n]
+    const float* frame;             // [rows * cols] or null
+    double tw, ms, sf, lam;
+    int64_t tail;
+    double* poses;                  // [n * bodies * 12 + tail]
+    int32_t* rects;                 // [n + tail][4]
+    int32_t* groups;                // [n + tail][sizeof(Groups) / 4] or null
+    int32_t* strips;                // [n + tail][sizeof(Strips) / 4] or null
+    int32_t* parents;               // [n + tail]
+    int32_t* item_range;            // [n + tail][2]
+    int32_t* item_particle;         // [n * tiles_ub * (groups ? kMaxGroups : 1) + tail]: as enqueue_loglikes sizes it
+    int32_t* ctr_this;              // [2 + tail]
+    int32_t* done;                  // [n + tail]
+    int32_t* win_used;              // [n + tail][4]
+    int32_t* win_dst;               // [n + tail][4]
+    int32_t* reg_dst;               // [n + tail][4]
+    int32_t* err;                   // [2 + tail]
+    uint64_t* area_sum;             // [1] or null
+    double* aux;                    // [rows * cols + tail][4] or null
+    float* keep;                    // [rows * cols + tail] or null
+};
+
+extern "C" {
+
+// {sizeof(Groups), sizeof(Strips), kMaxGroups, kMaxStrips, kPrepPerBlock, kMaxBodies}: what the caller's view of the arrays rests on
+int32_t rbs_test_prep_layout(int32_t* out6)
+{
+    if (!out6) return RBS_ERR_INVALID_ARGUMENT;
+    out6[0] = (int32_t)sizeof(rbs::Groups); out6[1] = (int32_t)sizeof(rbs::Strips); out6[2] = rbs::kMaxGroups; out6[3] = rbs::kMaxStrips;
+    out6[4] = rbs::kPrepPerBlock; out6[5] = rbs::kMaxBodies;
+    return RBS_OK;
+}
+
+// tiles_upper_bound(cols, rows, tile_w, min(tile_w * tile_h, tile_px)) as enqueue_loglikes computes it (host only)
+int64_t rbs_test_prep_tiles_ub(int32_t cols, int32_t rows, int32_t tile_w, int32_t tile_h, int32_t tile_px)
+{
+    if (cols < 1 || rows < 1 || tile_w < 16 || tile_h < 1 || tile_px < 1) return -1;
+    return (int64_t)tiles_upper_bound(cols, rows, tile_w, std::min(tile_w * tile_h, tile_px));
+}
+
+int32_t rbs_test_prep(const rbs_test_prep_io* io)
+{
+    namespace pr = rbs::probe;
+    if (!io) return RBS_ERR_INVALID_ARGUMENT;
+    // (columns and rows <= 8 192: Strips::box; whole float4 columns: the strips' cells)
+    if (io->rows < 1 || io->rows > 8192 || io->cols < 4 || io->cols > 8192 || (io->cols & 3) || io->n < 1 || io->n > (1 << 16) ||
+        io->n_bodies < 1 || io->n_bodies > rbs::kMaxBodies || io->tail < 0 || io->tail > 4096 || io->slots < 0 || io->slab_px < 0)
+        return RBS_ERR_INVALID_ARGUMENT;
+    if (io->rect_align < 4 || (io->rect_align & (io->rect_align - 1)) || io->tile_w < 16 || (io->tile_w & 15) || io->tile_h < 1 || io->tile_px < 1 ||
+        io->tile_w > 8192 || io->tile_h > 8192 || io->route < 0 || io->route > 2 || (io->frame && io->route != 0))
+        return RBS_ERR_INVALID_ARGUMENT;
+    if (!io->vtx_begin || !io->vtx || !io->poses_in || !io->indices || !io->poses || !io->rects || !io->parents || !io->item_range ||
+        !io->item_particle || !io->ctr_this || !io->done || !io->win_used || !io->win_dst || !io->reg_dst || !io->err || (io->slots && !io->win_src) ||
+        (io->strips && !io->groups))
+        return RBS_ERR_INVALID_ARGUMENT;
+    if (io->vtx_begin[0] != 0) return RBS_ERR_INVALID_ARGUMENT;
+    for (int b = 0; b < io->n_bodies; ++b)
+        if (io->vtx_begin[b + 1] < io->vtx_begin[b]) return RBS_ERR_INVALID_ARGUMENT;
+    const size_t nv = (size_t)io->vtx_begin[io->n_bodies];
+    if (nv < 1 || pr::probe_refused((int64_t)nv)) return RBS_ERR_INVALID_ARGUMENT;
+    const size_t n = (size_t)io->n, B_ = (size_t)io->n_bodies, tail = (size_t)io->tail, npx = (size_t)io->rows * io->cols;
+    constexpr size_t kG = sizeof(rbs::Groups) / 4, kS = sizeof(rbs::Strips) / 4;
+    DevParams P = pr::probe_params(io->tw, io->ms, io->sf, io->lam);
+    P.rows = io->rows; P.cols = io->cols; P.npx = (int)npx;
+    P.n_bodies = io->n_bodies;
+    for (int b = 0; b <= io->n_bodies; ++b) P.vtx_begin[b] = io->vtx_begin[b];
+    P.rect_align = io->rect_align; P.tile_w = io->tile_w; P.tile_h = io->tile_h; P.tile_px = io->tile_px;
+    P.fx = io->fx; P.fy = io->fy; P.cx = io->cx; P.cy = io->cy;
+    P.windowed = io->windowed; P.slab_px = io->slab_px; P.plane_stride = io->slab_px ? io->slab_px : (int)npx; P.slots = io->slots;
+    P.n = io->n;
+    const size_t tiles_max = tiles_upper_bound(io->cols, io->rows, P.tile_w, std::min(P.tile_w * P.tile_h, P.tile_px));
+    const size_t items = n * tiles_max * (io->groups ? rbs::kMaxGroups : 1);   // (enqueue_loglikes: `need`)
+    if (pr::probe_refused((int64_t)items)) return RBS_ERR_INVALID_ARGUMENT;
+    pr::Buffers B;
+    P.vtx = reinterpret_cast<const rbs::floatx4*>(B.make<float>(4 * nv, io->vtx));
+    if (io->slots) P.win_src = reinterpret_cast<const int4*>(B.make<int>(4 * (size_t)io->slots, io->win_src));
+    if (io->rebase_box) P.rebase_box = reinterpret_cast<const int4*>(B.make<int>(4, io->rebase_box));
+    P.indices = B.make<int>(n, io->indices);
+    double* dposes = B.make<double>(n * B_ * 12 + tail, io->poses);
+    P.poses = dposes;
+    // the host-pointer routes: pinned memory of this call's own, as the handle maps its staging buffers
+    double* h_src = nullptr;
+    const size_t n_src = io->route == 2 ? (n + 1) * B_ * 6 : n * B_ * 12;
+    if (io->route == 0) {
+        if (B.err == hipSuccess) B.err = hipMemcpy(dposes, io->poses_in, sizeof(double) * n_src, hipMemcpyHostToDevice);
+    } else {
+        const double* d_src = nullptr;
+        if (B.err == hipSuccess) B.err = hipHostMalloc(&h_src, sizeof(double) * n_src, hipHostMallocDefault);
+        if (B.err == hipSuccess) {
+            std::memcpy(h_src, io->poses_in, sizeof(double) * n_src);
+            B.err = hipHostGetDevicePointer(reinterpret_cast<void**>(const_cast<double**>(&d_src)), h_src, 0);
+        }
+        if (io->route == 1) P.poses_src = d_src; else P.deltas_src = d_src;
+    }
+    int* drects = B.make<int>(4 * (n + tail), io->rects);
+    P.rects = drects;
+    int* dgroups = io->groups ? B.make<int>(kG * (n + tail), io->groups) : nullptr;
+    int* dstrips = io->strips ? B.make<int>(kS * (n + tail), io->strips) : nullptr;
+    P.groups = reinterpret_cast<rbs::Groups*>(dgroups);
+    P.strips = reinterpret_cast<rbs::Strips*>(dstrips);
+    P.parents = B.make<int>(n + tail, io->parents);
+    int* drange = B.make<int>(2 * (n + tail), io->item_range);
+    P.item_range = reinterpret_cast<int2*>(drange);
+    // (device side only: room behind the tail, so that a particle whose items exceeded the host's bound -- what the test is there
+    // to find -- would overwrite the tail's sentinels and nobody else's memory)
+    const size_t guard = n * 64;
+    P.item_particle = B.make<int>(items + tail + guard);
+    if (B.err == hipSuccess) B.err = hipMemcpy(P.item_particle, io->item_particle, sizeof(int) * (items + tail), hipMemcpyHostToDevice);
+    P.ctr_this = B.make<int>(2 + tail, io->ctr_this);
+    P.done = B.make<int>(n + tail, io->done);
+    int* dused = B.make<int>(4 * (n + tail), io->win_used);
+    int* dwdst = B.make<int>(4 * (n + tail), io->win_dst);
+    int* drdst = B.make<int>(4 * (n + tail), io->reg_dst);
+    P.win_used = reinterpret_cast<int4*>(dused); P.win_dst = reinterpret_cast<int4*>(dwdst); P.reg_dst = reinterpret_cast<int4*>(drdst);
+    P.err = B.make<int>(2 + tail, io->err);
+    unsigned long long* darea = io->area_sum ? B.make<unsigned long long>(1, reinterpret_cast<const unsigned long long*>(io->area_sum)) : nullptr;
+    P.area_sum = darea;
+    const float* dframe = io->frame ? B.make<float>(npx, io->frame) : nullptr;
+    double* daux = io->frame && io->aux ? B.make<double>(4 * (npx + tail), io->aux) : nullptr;
+    float* dkeep = io->frame && io->keep ? B.make<float>(npx + tail, io->keep) : nullptr;
+    if (B.err == hipSuccess) {
+        launch_prep(P, drects, io->update ? 1 : 0, io->route == 2, dframe, daux, nullptr, dkeep, nullptr);
+        B.ran();
+    }
+    B.fetch(io->poses, dposes, n * B_ * 12 + tail);
+    B.fetch(io->rects, drects, 4 * (n + tail));
+    if (dgroups) B.fetch(io->groups, dgroups, kG * (n + tail));
+    if (dstrips) B.fetch(io->strips, dstrips, kS * (n + tail));
+    B.fetch(io->parents, P.parents, n + tail);
+    B.fetch(io->item_range, drange, 2 * (n + tail));
+    B.fetch(io->item_particle, P.item_particle, items + tail);
+    B.fetch(io->ctr_this, P.ctr_this, 2 + tail);
+    B.fetch(io->done, P.done, n + tail);
+    B.fetch(io->win_used, dused, 4 * (n + tail));
+    B.fetch(io->win_dst, dwdst, 4 * (n + tail));
+    B.fetch(io->reg_dst, drdst, 4 * (n + tail));
+    B.fetch(io->err, P.err, 2 + tail);
+    if (darea) B.fetch(reinterpret_cast<unsigned long long*>(io->area_sum), darea, 1);
+    if (daux) B.fetch(io->aux, daux, 4 * (npx + tail));
+    if (dkeep) B.fetch(io->keep, dkeep, npx + tail);
+    if (h_src) (void)hipHostFree(h_src);
     return B.status();
 }
 

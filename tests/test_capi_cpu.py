@@ -225,6 +225,7 @@ def test_release_library_carries_no_fault_injection_hook():
     from filter_probes import FILTER_SYMBOLS
     from find_probes import FIND_SYMBOLS
     from pixel_probes import PROBE_SYMBOLS
+    from prep_probes import PREP_SYMBOLS
     lib = os.path.join(ROOT, "dbot_ros_amd", "lib")
     release = open(os.path.join(lib, "librbsensor_mi355x.so"), "rb").read()
     assert b"RBS_TEST_FAULT" not in release
@@ -236,8 +237,9 @@ def test_release_library_carries_no_fault_injection_hook():
     assert b"rbs_test_" not in release and b"rbs5probe" not in release        # no entry point, no probe kernel (rbs::probe::*)
     assert FILTER_SYMBOLS == ("rbs_test_filter",)                             # the particle filter's probe (tests/test_gpu_filter_kernels.py)
     assert len(FIND_SYMBOLS) == 8 and all(s.startswith("rbs_test_find_") for s in FIND_SYMBOLS)   # the object finder's (tests/test_gpu_finder_kernels.py)
-    for s in PROBE_SYMBOLS + FILTER_SYMBOLS + FIND_SYMBOLS:
+    assert PREP_SYMBOLS[0] == "rbs_test_prep" and all(s.startswith("rbs_test_prep") for s in PREP_SYMBOLS)   # the rectangles kernel's (tests/test_gpu_prep_kernels.py)
+    for s in PROBE_SYMBOLS + FILTER_SYMBOLS + FIND_SYMBOLS + PREP_SYMBOLS:
         assert s.encode() + b"\0" in test_build, s                            # (a name in the dynamic symbol table)
         assert s.encode() not in release, s
     exported = C.CDLL(hooks) if os.path.abspath(_capi.LIB_PATH) == os.path.abspath(hooks) else None
-    assert exported is None or all(hasattr(exported, s) for s in PROBE_SYMBOLS + FILTER_SYMBOLS + FIND_SYMBOLS)
+    assert exported is None or all(hasattr(exported, s) for s in PROBE_SYMBOLS + FILTER_SYMBOLS + FIND_SYMBOLS + PREP_SYMBOLS)
