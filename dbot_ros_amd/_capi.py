@@ -50,6 +50,7 @@ EXPORTS = (
     "rbs_find_default_params", "rbs_find_create", "rbs_find_destroy", "rbs_find_run", "rbs_find_get_stage",
     "rbs_find_stage_ms", "rbs_find_last_error",
     "rbs_find_default_foreground", "rbs_find_set_foreground", "rbs_find_get_plane", "rbs_find_get_seed_frame",
+    "rbs_find_default_refinement", "rbs_find_set_refinement", "rbs_find_get_covariance", "rbs_find_get_perturbations",
 )
 RBS_FIND_SEEDS, RBS_FIND_COARSE, RBS_FIND_CANDIDATES, RBS_FIND_SURVIVORS, RBS_FIND_CHILDREN, RBS_FIND_RESULT = range(6)
 
@@ -110,6 +111,16 @@ class RbsFindForeground(C.Structure):
         ("ransac_sigmas", C.c_double),
         ("mask_sigmas", C.c_double),
         ("min_inlier_fraction", C.c_double),
+    ]
+
+
+class RbsFindRefinement(C.Structure):
+    _fields_ = [
+        ("enabled", C.c_int32),
+        ("elite", C.c_int32),
+        ("mix", C.c_double),
+        ("shrink", C.c_double),
+        ("jitter", C.c_double),
     ]
 
 
@@ -327,6 +338,14 @@ def load():
     lib.rbs_find_get_plane.argtypes = [H, dp]
     lib.rbs_find_get_seed_frame.restype = C.c_int32
     lib.rbs_find_get_seed_frame.argtypes = [H, fp, lp]
+    lib.rbs_find_default_refinement.restype = None
+    lib.rbs_find_default_refinement.argtypes = [C.POINTER(RbsFindRefinement)]
+    lib.rbs_find_set_refinement.restype = C.c_int32
+    lib.rbs_find_set_refinement.argtypes = [H, C.POINTER(RbsFindRefinement)]
+    lib.rbs_find_get_covariance.restype = C.c_int32
+    lib.rbs_find_get_covariance.argtypes = [H, C.c_int32, dp, lp]
+    lib.rbs_find_get_perturbations.restype = C.c_int32
+    lib.rbs_find_get_perturbations.argtypes = [H, C.c_int32, dp, lp]
     lib.rbs_find_last_error.restype = C.c_char_p
     lib.rbs_find_last_error.argtypes = [H]
     _lib = lib

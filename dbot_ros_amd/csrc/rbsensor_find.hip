@@ -14,6 +14,9 @@
 //   rbs_find_nms_kernel         one wave: greedy suppression in candidate order
 //   rbs_find_children_kernel    a round's children (Philox4x32-10 normals), then (rbs_loglikes_device) their scores
 //   rbs_find_select_kernel      each survivor keeps its best child
+//   (rbs_findr_*_kernel)        opt-in step 6b (rbs_find_set_refinement) in place of step 6's fixed schedule: every survivor
+//                               carries a 6 x 6 search covariance; its children are drawn through the covariance's factor and
+//                               the covariance is re-estimated from the round's best children, all on the device
 // Every order is fixed: the same frame gives the same bits, whatever `batch`.
 #include <climits>
 
@@ -231,6 +234,19 @@ __device__ inline void rotvec_matrix(const double* v, double* R)
     R[6] = 2.0 * (x * z - w * y);       R[7] = 2.0 * (y * z + w * x);       R[8] = 1.0 - 2.0 * (x * x + y * y);
 }
 
+// the six standard normals of child j of survivor k in round `round`: Box-Muller pairs of three Philox blocks
+__device__ inline void child_normals(unsigned long long seed, int round, int k, int j, double* nz)
+{
+#pragma unroll
+    for (int pr = 0; pr < 3; ++pr) {
+        const uint4 r = philox(seed, ((unsigned long long)(unsigned)round << 32) | (unsigned)k, ((unsigned long long)(unsigned)j << 2) | pr);
+        const double u1 = 1.0 - rbt::u01(r.x, r.y), u2 = rbt::u01(r.z, r.w);
+        const double rad = sqrt(-2.0 * log(u1));
+        nz[2 * pr] = rad * cos(kTwoPi * u2);
+        nz[2 * pr + 1] = rad * sin(kTwoPi * u2);
+    }
+}
+
 // One thread per child of round r: [S][children][12].
 __global__ __launch_bounds__(256) void rbs_find_children_kernel(const double* __restrict__ surv, int S, int children, int round,
                                                                 unsigned long long seed, double st, double sa,
@@ -247,14 +263,7 @@ __global__ __launch_bounds__(256) void rbs_find_children_kernel(const double* __
         return;
     }
     double nz[6];
-#pragma unroll
-    for (int pr = 0; pr < 3; ++pr) {
-        const uint4 r = philox(seed, ((unsigned long long)(unsigned)round << 32) | (unsigned)k, ((unsigned long long)(unsigned)j << 2) | pr);
-        const double u1 = 1.0 - rbt::u01(r.x, r.y), u2 = rbt::u01(r.z, r.w);
-        const double rad = sqrt(-2.0 * log(u1));
-        nz[2 * pr] = rad * cos(kTwoPi * u2);
-        nz[2 * pr + 1] = rad * sin(kTwoPi * u2);
-    }
+    child_normals(seed, round, k, j, nz);
     const double v[3] = {sa * nz[0], sa * nz[1], sa * nz[2]};
     double A[9];
     rotvec_matrix(v, A);
@@ -462,6 +471,170 @@ __global__ __launch_bounds__(kFgThreads) void rbs_findfg_mask_kernel(const float
     out[p] = keep ? f : __builtin_nanf("");
 }
 
+// ---------------------------------------------------------------------------- step 6b: the adaptive refinement (opt-in)
+// Every survivor carries a symmetric 6 x 6 covariance C over (rotation vector, translation) and its lower factor L.  A round's
+// children are d = L n around the survivor; after the round C is re-estimated from the perturbations of the round's best children
+// (a cross-entropy step) and factored again.  Binary64; apart from the normals and the rotation of step 6 only + - * / and sqrt,
+// in the order of include/rbsensor_mi355x.h (step 6b), so tests/find_refine_twin.py reproduces every covariance bit for bit
+// from the device's own perturbations.  (Named rbs_findr_*: the rbs_find_*_kernel names are a closed list.)
+constexpr int kRefMaxElite = 64;
+
+struct RefineRule {
+    int elite;
+    double mix, shrink, jitter;
+};
+
+// Lane 0 of a wave: sL [36] := the lower Cholesky factor of sC [36] by rows (the upper part 0); a pivot that is not > 0 or not
+// finite: sL := diag(sqrt(max(C_ii, jitter))), max(x, y) = x > y ? x : y.  sC and sL in LDS.
+__device__ inline void factor6(const double* sC, double jitter, double* sL)
+{
+    double L[6][6];
+    bool ok = true;
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int j = 0; j < 6; ++j) L[i][j] = 0.0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int j = 0; j <= i; ++j) {
+            double s = sC[6 * i + j];
+#pragma unroll
+            for (int k = 0; k < j; ++k) s = s - L[i][k] * L[j][k];
+            if (j == i) {
+                ok = ok && s > 0.0 && s <= 1.7976931348623157e308;
+                L[i][i] = sqrt(s);
+            } else {
+                L[i][j] = s / L[j][j];
+            }
+        }
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+            double v = L[i][j];
+            if (!ok) {
+                const double c = sC[6 * i + i];
+                v = i == j ? sqrt(c > jitter ? c : jitter) : 0.0;
+            }
+            sL[6 * i + j] = v;
+        }
+}
+
+// One wave per survivor: cov [S][36] := diag(sa^2 x 3, st^2 x 3), fac [S][36] := its factor.
+__global__ __launch_bounds__(64) void rbs_findr_init_kernel(double sa, double st, double jitter, double* __restrict__ cov,
+                                                            double* __restrict__ fac)
+{
+    __shared__ double sC[36], sL[36];
+    const int k = blockIdx.x, lane = threadIdx.x;
+    if (lane < 36) {
+        const int a = lane / 6, b = lane - 6 * a;
+        const double v = a != b ? 0.0 : a < 3 ? sa * sa : st * st;
+        sC[lane] = v;
+        cov[(size_t)k * 36 + lane] = v;
+    }
+    __syncthreads();
+    if (lane == 0) factor6(sC, jitter, sL);
+    __syncthreads();
+    if (lane < 36) fac[(size_t)k * 36 + lane] = sL[lane];
+}
+
+// One thread per child of round r through the survivors' factors fac [S][36]: out [S][children][12] and the perturbations
+// dd [S][children][6] (child 0: the survivor, d = 0).  d_a = sum over b <= a, ascending, of L_ab n_b; n: step 6's normals.
+__global__ __launch_bounds__(256) void rbs_findr_children_kernel(const double* __restrict__ surv, const double* __restrict__ fac, int S,
+                                                                 int children, int round, unsigned long long seed,
+                                                                 double* __restrict__ out, double* __restrict__ dd)
+{
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    if (g >= S * children) return;
+    const int k = g / children, j = g - k * children;
+    const double* P = surv + (size_t)k * 12;
+    double* o = out + (size_t)g * 12;
+    double* od = dd + (size_t)g * 6;
+    if (j == 0) {
+#pragma unroll
+        for (int e = 0; e < 12; ++e) o[e] = P[e];
+#pragma unroll
+        for (int e = 0; e < 6; ++e) od[e] = 0.0;
+        return;
+    }
+    double nz[6], d[6];
+    child_normals(seed, round, k, j, nz);
+    const double* L = fac + (size_t)k * 36;
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+        double s = L[6 * a] * nz[0];
+#pragma unroll
+        for (int b = 1; b <= a; ++b) s = s + L[6 * a + b] * nz[b];
+        d[a] = s;
+        od[a] = s;
+    }
+    double A[9];
+    rotvec_matrix(d, A);
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+            o[3 * r + c] = A[3 * r] * P[c] + A[3 * r + 1] * P[3 + c] + A[3 * r + 2] * P[6 + c];
+    o[9] = P[9] + d[3];
+    o[10] = P[10] + d[4];
+    o[11] = P[11] + d[5];
+}
+
+// One wave per survivor k, after the round's scores.  Lane l holds children l, l + 64, ...  The elite is taken one at a time in
+// step 5's order (score descending, j ascending, NaN never): every lane's best child that comes after the last one taken, then a
+// butterfly over the lanes; it ends early when no child with a number is left (m of them).  Lane 6 a + b sums M_ab = d_a d_b in
+// that order, then C_ab := shrink ((1 - mix) C_ab + mix (M_ab / m)) (+ jitter on the diagonal); m == 0: C unchanged.
+// cov_out [S][36] := C (cov_in may be cov_out), fac [S][36] := its factor.
+__global__ __launch_bounds__(64) void rbs_findr_update_kernel(const double* __restrict__ child_score, const double* __restrict__ dd,
+                                                              int children, const RefineRule U, const double* cov_in,
+                                                              double* cov_out, double* __restrict__ fac)
+{
+    __shared__ double sC[36], sL[36];
+    const int k = blockIdx.x, lane = threadIdx.x;
+    const double* score = child_score + (size_t)k * children;
+    const double* D = dd + (size_t)k * children * 6;
+    const int a = lane < 36 ? lane / 6 : 0, b = lane < 36 ? lane - 6 * a : 0;
+    double acc = 0.0;
+    double ps = 0.0;
+    int pj = -1, m = 0;
+    for (int e = 0; e < U.elite; ++e) {
+        double bs = __builtin_nan("");
+        int bj = INT_MAX;                             // (NaN, INT_MAX): after every child
+        for (int j = lane; j < children; j += 64) {   // (ascending j: of equal scores the first stays)
+            const double s = score[j];
+            if (s != s) continue;
+            if (e > 0 && !before(ps, pj, s, j)) continue;
+            if (before(s, j, bs, bj)) { bs = s; bj = j; }
+        }
+#pragma unroll
+        for (int w = 1; w < 64; w <<= 1) {
+            const double os = __shfl_xor(bs, w, 64);
+            const int oj = __shfl_xor(bj, w, 64);
+            if (before(os, oj, bs, bj)) { bs = os; bj = oj; }
+        }
+        if (bj == INT_MAX) break;   // (the same in every lane: no child with a number is left)
+        if (lane < 36) acc = acc + D[(size_t)bj * 6 + a] * D[(size_t)bj * 6 + b];
+        ps = bs;
+        pj = bj;
+        ++m;
+    }
+    if (lane < 36) {
+        double c = cov_in[(size_t)k * 36 + lane];
+        if (m > 0) {
+            const double Mab = acc / (double)m;
+            c = U.shrink * ((1.0 - U.mix) * c + U.mix * Mab);
+            if (a == b) c = c + U.jitter;
+        }
+        sC[lane] = c;
+        cov_out[(size_t)k * 36 + lane] = c;
+    }
+    __syncthreads();
+    if (lane == 0) factor6(sC, U.jitter, sL);
+    __syncthreads();
+    if (lane < 36) fac[(size_t)k * 36 + lane] = sL[lane];
+}
+
 // ---------------------------------------------------------------------------- launches
 // One helper per launch of a find: a stream and raw device pointers, nothing of an rbs_find.  rbs_find_run and
 // rbs_find_get_stage launch through these, and so do the probes of the test build (rbsensor_probes.hip).
@@ -585,6 +758,28 @@ inline void launch_mask(hipStream_t st, const float* frame, int rows, int cols, 
                        cols, M, rec, mask_sigmas, out);
 }
 
+// step 6b: cov [S][36], fac [S][36]
+inline void launch_refine_init(hipStream_t st, int S, double sigma_a, double sigma_t, double jitter, double* cov, double* fac)
+{
+    hipLaunchKernelGGL(rbs_findr_init_kernel, dim3((unsigned)S), dim3(64), 0, st, sigma_a, sigma_t, jitter, cov, fac);
+}
+
+// out [S * children][12], dd [S * children][6]
+inline void launch_refine_children(hipStream_t st, const double* surv, const double* fac, int S, int children, int round,
+                                   unsigned long long seed, double* out, double* dd)
+{
+    const int nch = S * children;
+    hipLaunchKernelGGL(rbs_findr_children_kernel, dim3((unsigned)((nch + 255) / 256)), dim3(256), 0, st, surv, fac, S, children, round, seed,
+                       out, dd);
+}
+
+// child_score [S * children], dd [S * children][6], cov_in [S][36] -> cov_out [S][36] (may be cov_in), fac [S][36]
+inline void launch_refine_update(hipStream_t st, const double* child_score, const double* dd, int S, int children, const RefineRule& U,
+                                 const double* cov_in, double* cov_out, double* fac)
+{
+    hipLaunchKernelGGL(rbs_findr_update_kernel, dim3((unsigned)S), dim3(64), 0, st, child_score, dd, children, U, cov_in, cov_out, fac);
+}
+
 }  // namespace rbf
 
 struct rbs_find {
@@ -610,6 +805,11 @@ struct rbs_find {
     double* d_planes = nullptr;       // [fg_cap][4]
     int* d_counts = nullptr;          // [fg_cap + 1]
     int fg_cap = 0;
+    // step 6b (rbs_find_set_refinement): allocated when first switched on
+    rbs_find_refinement rf{};         // the setting of the next find
+    double* d_cov = nullptr;          // [rounds + 1][S][36] the covariances entering each round, then the final ones
+    double* d_fac = nullptr;          // [S][36] the current factors
+    double* d_dd = nullptr;           // [rounds][S*children][6] the children's perturbations
     double* d_hyp = nullptr;          // [batch][12]
     int* d_zero = nullptr;            // [max(batch, S*children)] parent indices: all 0
     double* d_score = nullptr;        // [max_seeds * n_rotations] coarse scores
@@ -634,6 +834,7 @@ struct rbs_find {
     // the last find
     bool have = false;
     bool fg_ran = false;              // with step 1b
+    bool rf_ran = false;              // with step 6b
     double plane[rbf::kFgRecord] = {};
     int n_seeds = 0, n_valid = 0, n_cand = 0, n_surv = 0;
     long n_hyp = 0;
@@ -668,6 +869,15 @@ const char* foreground_check(const rbs_find_foreground* g)
     if (!(g->ransac_sigmas >= 0.0) || !std::isfinite(g->ransac_sigmas) || !(g->mask_sigmas >= 0.0) || !std::isfinite(g->mask_sigmas))
         return "find: ransac_sigmas and mask_sigmas must be finite and >= 0";
     if (!(g->min_inlier_fraction >= 0.0) || !(g->min_inlier_fraction <= 1.0)) return "find: min_inlier_fraction outside [0, 1]";
+    return nullptr;
+}
+
+const char* refinement_check(const rbs_find_refinement* g, int children)
+{
+    if (g->elite < 1 || g->elite > rbf::kRefMaxElite || g->elite > children) return "find: elite outside 1..min(64, children)";
+    if (!(g->mix >= 0.0) || !(g->mix <= 1.0)) return "find: mix outside [0, 1]";
+    if (!(g->shrink > 0.0) || !(g->shrink <= 1.0)) return "find: shrink outside (0, 1]";
+    if (!(g->jitter >= 0.0) || !std::isfinite(g->jitter)) return "find: jitter must be finite and >= 0";
     return nullptr;
 }
 
@@ -788,7 +998,7 @@ void rbs_find_destroy(rbs_find* f)
                     (void*)f->d_tk_i[1], (void*)f->d_cand_pose, (void*)f->d_cand_score, (void*)f->d_cand_idx, (void*)f->d_kept,
                     (void*)f->d_surv, (void*)f->d_surv_score, (void*)f->d_surv0, (void*)f->d_surv0_score, (void*)f->d_surv0_idx,
                     (void*)f->d_child, (void*)f->d_child_score, (void*)f->d_final, (void*)f->d_final_score, (void*)f->d_final_idx,
-                    (void*)f->d_seedframe, (void*)f->d_planes, (void*)f->d_counts})
+                    (void*)f->d_seedframe, (void*)f->d_planes, (void*)f->d_counts, (void*)f->d_cov, (void*)f->d_fac, (void*)f->d_dd})
         if (q) (void)hipFree(q);
     if (f->h_frame) (void)hipHostFree(f->h_frame);
     if (f->h_info) (void)hipHostFree(f->h_info);
@@ -936,6 +1146,7 @@ int32_t rbs_find_run(rbs_find* f, const float* frame, int32_t k, double* poses, 
     f->n_seeds = f->h_info[0];
     f->n_valid = f->h_info[1];
     f->fg_ran = fg;
+    f->rf_ran = false;
     for (double& v : f->plane) v = 0.0;
     if (fg) {
         std::memcpy(f->plane, f->h_info + 4, sizeof(f->plane));
@@ -988,13 +1199,22 @@ int32_t rbs_find_run(rbs_find* f, const float* frame, int32_t k, double* poses, 
         // refinement at the sensor's resolution
         const int nch = S * p.children;
         double st_r = p.sigma_translation, sa_r = p.sigma_angle;
+        const bool rf = f->rf.enabled != 0;
+        const rbf::RefineRule U{f->rf.elite, f->rf.mix, f->rf.shrink, f->rf.jitter};
+        const size_t cov_stride = 36 * (size_t)p.n_survivors;   // (a round's covariances: a slot of n_survivors, S of them used)
+        if (rf) rbf::launch_refine_init(st, S, sa_r, st_r, U.jitter, f->d_cov, f->d_fac);
         for (int r = 0; r < p.rounds; ++r) {
             double* cp = f->d_child + (size_t)r * 12 * S * p.children;
             double* cs = f->d_child_score + (size_t)r * S * p.children;
-            rbf::launch_children(st, f->d_surv, S, p.children, r, (unsigned long long)p.seed, st_r, sa_r, cp);
+            double* dd = rf ? f->d_dd + (size_t)r * 6 * S * p.children : nullptr;
+            if (rf) rbf::launch_refine_children(st, f->d_surv, f->d_fac, S, p.children, r, (unsigned long long)p.seed, cp, dd);
+            else rbf::launch_children(st, f->d_surv, S, p.children, r, (unsigned long long)p.seed, st_r, sa_r, cp);
             RBF_HIP(f, hipGetLastError());
             RBF_RC(f, f->full, rbs_loglikes_device(f->full, cp, f->d_zero, nch, 0, cs, st));
             rbf::launch_select(st, cp, cs, S, p.children, f->d_surv, f->d_surv_score);
+            if (rf)   // step 6b: the covariances entering round r + 1 and their factors
+                rbf::launch_refine_update(st, cs, dd, S, p.children, U, f->d_cov + (size_t)r * cov_stride, f->d_cov + (size_t)(r + 1) * cov_stride,
+                                          f->d_fac);
             RBF_HIP(f, hipGetLastError());
             st_r *= p.decay;
             sa_r *= p.decay;
@@ -1009,6 +1229,7 @@ int32_t rbs_find_run(rbs_find* f, const float* frame, int32_t k, double* poses, 
         rbf::launch_order(st, f->d_surv, f->d_surv_score, f->d_final_idx, S, f->d_final, f->d_final_score);
         RBF_HIP(f, hipGetLastError());
     }
+    f->rf_ran = S > 0 && f->rf.enabled != 0;
     RBF_HIP(f, hipEventRecord(f->ev[4], st));
     RBF_HIP(f, hipStreamSynchronize(st));
     (void)hipEventElapsedTime(&f->ms[0], f->ev[0], f->ev[1]);
@@ -1155,6 +1376,74 @@ int32_t rbs_find_get_seed_frame(rbs_find* f, float* out, int64_t* n)
     if (!out) return RBS_OK;
     RBF_HIP(f, hipSetDevice(f->s->device));
     RBF_HIP(f, hipMemcpy(out, f->fg_ran ? f->d_seedframe : f->d_coarse, sizeof(float) * (size_t)*n, hipMemcpyDeviceToHost));
+    return RBS_OK;
+}
+
+void rbs_find_default_refinement(rbs_find_refinement* g)
+{
+    if (!g) return;
+    g->enabled = 1;
+    g->elite = 8;
+    g->mix = 0.5;
+    g->shrink = 1.0;
+    g->jitter = 1e-10;
+}
+
+int32_t rbs_find_set_refinement(rbs_find* f, const rbs_find_refinement* g)
+{
+    if (!f) return RBS_ERR_INVALID_ARGUMENT;
+    if (!g || g->enabled == 0) {
+        f->rf.enabled = 0;
+        return RBS_OK;
+    }
+    if (const char* bad = refinement_check(g, f->p.children)) return ffail(f, RBS_ERR_INVALID_ARGUMENT, bad);
+    RBF_HIP(f, hipSetDevice(f->s->device));
+    if (!f->d_cov) {
+        const size_t S = (size_t)f->p.n_survivors, R = (size_t)f->p.rounds;
+        double *cov = nullptr, *fac = nullptr, *dd = nullptr;
+        hipError_t e = hipMalloc(&cov, sizeof(double) * 36 * S * (R + 1));
+        if (e == hipSuccess) e = hipMalloc(&fac, sizeof(double) * 36 * S);
+        if (e == hipSuccess) e = hipMalloc(&dd, sizeof(double) * 6 * S * (size_t)f->p.children * std::max<size_t>(1, R));
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            if (cov) (void)hipFree(cov);
+            if (fac) (void)hipFree(fac);
+            return ffail(f, RBS_ERR_OUT_OF_MEMORY, "find_set_refinement: device memory");
+        }
+        f->d_cov = cov;
+        f->d_fac = fac;
+        f->d_dd = dd;
+    }
+    f->rf = *g;
+    f->rf.enabled = 1;
+    return RBS_OK;
+}
+
+int32_t rbs_find_get_covariance(rbs_find* f, int32_t round, double* cov, int64_t* n)
+{
+    if (!f) return RBS_ERR_INVALID_ARGUMENT;
+    if (!n) return ffail(f, RBS_ERR_INVALID_ARGUMENT, "find_get_covariance: n is NULL");
+    if (!f->have || !f->rf_ran) return ffail(f, RBS_ERR_INVALID_ARGUMENT, "find_get_covariance: no find with step 6b yet");
+    if (round < 0 || round > f->p.rounds) return ffail(f, RBS_ERR_INVALID_ARGUMENT, "find_get_covariance: round outside 0..rounds");
+    *n = f->n_surv;
+    if (!cov || f->n_surv == 0) return RBS_OK;
+    RBF_HIP(f, hipSetDevice(f->s->device));
+    RBF_HIP(f, hipMemcpy(cov, f->d_cov + (size_t)round * 36 * (size_t)f->p.n_survivors, sizeof(double) * 36 * (size_t)f->n_surv,
+                         hipMemcpyDeviceToHost));
+    return RBS_OK;
+}
+
+int32_t rbs_find_get_perturbations(rbs_find* f, int32_t round, double* d, int64_t* n)
+{
+    if (!f) return RBS_ERR_INVALID_ARGUMENT;
+    if (!n) return ffail(f, RBS_ERR_INVALID_ARGUMENT, "find_get_perturbations: n is NULL");
+    if (!f->have || !f->rf_ran) return ffail(f, RBS_ERR_INVALID_ARGUMENT, "find_get_perturbations: no find with step 6b yet");
+    if (round < 0 || round >= f->p.rounds) return ffail(f, RBS_ERR_INVALID_ARGUMENT, "find_get_perturbations: round outside 0..rounds-1");
+    const size_t nch = (size_t)f->n_surv * (size_t)f->p.children;
+    *n = (int64_t)nch;
+    if (!d || nch == 0) return RBS_OK;
+    RBF_HIP(f, hipSetDevice(f->s->device));
+    RBF_HIP(f, hipMemcpy(d, f->d_dd + (size_t)round * 6 * nch, sizeof(double) * 6 * nch, hipMemcpyDeviceToHost));
     return RBS_OK;
 }
 

@@ -17,6 +17,7 @@
 // OUT and `tail` elements (rows) longer than the kernel may write: the caller fills it with a sentinel, the probe copies it to
 // the device before the launch and back after it, so what the kernel left alone -- the tail included -- is seen.
 // rbs_test_findfg_* are the same for step 1b's four launch helpers: tests/test_gpu_find_foreground_kernels.py.
+// rbs_test_findr_* are the same for step 6b's launch helpers: tests/test_gpu_find_refinement_kernels.py.
 //
 // rbs_test_prep does the same for the rectangles kernel (rbsensor_kernels.hip prep_particles): it builds a DevParams from host
 // arrays -- no sensor handle, no mesh: the rectangle reads the vertices only -- and launches rbs_prep_kernel,
@@ -704,6 +705,57 @@ int32_t rbs_test_findfg_mask(const float* frame, int32_t rows, int32_t cols, dou
     const rbf::FgModel M{0.0, 0.0, model_sigma, sigma_factor};
     if (B.err == hipSuccess) { rbf::launch_mask(nullptr, dframe, rows, cols, M, drec, mask_sigmas, dout); B.ran(); }
     B.fetch(out, dout, m);
+    return B.status();
+}
+
+// ---- step 6b, the adaptive refinement (rbs_findr_*_kernel): tests/find_refine_probes.py, tests/test_gpu_find_refinement_kernels.py
+// fac == NULL: rbf::launch_refine_init makes the factors of diag(sigma_a^2 x 3, sigma_t^2 x 3) first (cov [S + tail][36] is then
+// written too); else fac [S][36] is read.  out [S * children + tail][12], dd [S * children + tail][6]
+int32_t rbs_test_findr_children(const double* surv, const double* fac, int32_t S, int32_t children, int32_t round, uint64_t seed,
+                                double sigma_a, double sigma_t, double jitter, double* cov, double* out, double* dd, int64_t tail)
+{
+    namespace pr = rbs::probe;
+    if (!surv || !out || !dd || (!fac && !cov) || S < 0 || S > rbf::kMaxSurvivors || children < 1 || children > 4096 || round < 0 ||
+        round > 63 || tail < 0 || pr::probe_refused(tail))
+        return RBS_ERR_INVALID_ARGUMENT;
+    if (S == 0) return RBS_OK;
+    const size_t nch = (size_t)S * children + (size_t)tail, K = (size_t)S + (size_t)tail;
+    pr::Buffers B;
+    const double* dsurv = B.make<double>(12 * (size_t)S, surv);
+    double* dfac = fac ? B.make<double>(36 * (size_t)S, fac) : B.make<double>(36 * (size_t)S, (const double*)nullptr);
+    double* dcov = fac ? nullptr : B.make<double>(36 * K, cov);
+    double* dout = B.make<double>(12 * nch, out);
+    double* ddd = B.make<double>(6 * nch, dd);
+    if (B.err == hipSuccess) {
+        if (!fac) rbf::launch_refine_init(nullptr, S, sigma_a, sigma_t, jitter, dcov, dfac);
+        rbf::launch_refine_children(nullptr, dsurv, dfac, S, children, round, (unsigned long long)seed, dout, ddd);
+        B.ran();
+    }
+    if (!fac) B.fetch(cov, dcov, 36 * K);
+    B.fetch(out, dout, 12 * nch);
+    B.fetch(dd, ddd, 6 * nch);
+    return B.status();
+}
+
+// child_score [S * children], dd [S * children][6], cov [S + tail][36] IN and OUT (updated in place), fac [S + tail][36] OUT
+int32_t rbs_test_findr_update(const double* child_score, const double* dd, int32_t S, int32_t children, int32_t elite, double mix,
+                              double shrink, double jitter, double* cov, double* fac, int64_t tail)
+{
+    namespace pr = rbs::probe;
+    if (!child_score || !dd || !cov || !fac || S < 0 || S > rbf::kMaxSurvivors || children < 1 || children > 4096 || elite < 1 ||
+        elite > rbf::kRefMaxElite || elite > children || tail < 0 || pr::probe_refused(tail))
+        return RBS_ERR_INVALID_ARGUMENT;
+    if (S == 0) return RBS_OK;
+    const size_t nch = (size_t)S * children, K = (size_t)S + (size_t)tail;
+    pr::Buffers B;
+    const double* dscore = B.make<double>(nch, child_score);
+    const double* ddd = B.make<double>(6 * nch, dd);
+    double* dcov = B.make<double>(36 * K, cov);
+    double* dfac = B.make<double>(36 * K, fac);
+    const rbf::RefineRule U{elite, mix, shrink, jitter};
+    if (B.err == hipSuccess) { rbf::launch_refine_update(nullptr, dscore, ddd, S, children, U, dcov, dcov, dfac); B.ran(); }
+    B.fetch(cov, dcov, 36 * K);
+    B.fetch(fac, dfac, 36 * K);
     return B.status();
 }
 

@@ -32,7 +32,7 @@ Plane = namedtuple("Plane", "accepted a b c count n_valid trial masked")
 
 
 class ObjectFinder:
-    """ObjectFinder(sensor, object_model, params, foreground=None).find(frame=None) -> FindResult."""
+    """ObjectFinder(sensor, object_model, params, foreground=None, refinement=None).find(frame=None) -> FindResult."""
 
     @dataclass
     class Foreground:
@@ -61,6 +61,32 @@ class ObjectFinder:
             return g
 
     @dataclass
+    class Refinement:
+        """Step 6b (rbs_find_refinement): every survivor's 6 x 6 search covariance adapts to its round's best children."""
+        enabled: bool = True
+        elite: int = 8
+        mix: float = 0.5
+        shrink: float = 1.0
+        jitter: float = 1e-10
+
+        @classmethod
+        def from_mapping(cls, m):
+            g = cls()
+            names = [f.name for f in fields(cls)]
+            for k, v in dict(m or {}).items():
+                if k not in names:
+                    raise ValueError(f"object_finder/refinement/{k}: unknown key (one of {sorted(names)})")
+                cur = getattr(g, k)
+                setattr(g, k, bool(v) if isinstance(cur, bool) else int(v) if isinstance(cur, int) else float(v))
+            return g
+
+        def c_params(self):
+            g = _capi.RbsFindRefinement()
+            for f in fields(self):
+                setattr(g, f.name, int(getattr(self, f.name)) if f.name in ("enabled", "elite") else getattr(self, f.name))
+            return g
+
+    @dataclass
     class Parameters:
         coarse_downsampling: int = 0          # 0: the largest of {1, 2, 4} leaving >= 160 columns
         seed_stride: int = 4
@@ -82,15 +108,21 @@ class ObjectFinder:
         seed: int = 0
         min_score: float = -math.inf
         foreground: Optional["ObjectFinder.Foreground"] = None   # step 1b; None: off
+        # step 6b, an ObjectFinder.Refinement; None: off (step 6's fixed schedule).  A plain attribute, not a dataclass field:
+        # the fields besides `foreground` are rbs_find_params' own, one to one.
+        refinement = None
 
         @classmethod
         def from_rosparam(cls, tree):
             """From the optional `object_finder:` mapping of the merged rosparam tree; every key is
-            optional (angles in degrees: nms_angle_deg, sigma_angle_deg; foreground: a mapping of Foreground's fields)."""
+            optional (angles in degrees: nms_angle_deg, sigma_angle_deg; foreground / refinement: mappings of Foreground's /
+            Refinement's fields)."""
             m = dict((tree or {}).get("object_finder") or {})
             p = cls()
             if "foreground" in m:
                 p.foreground = ObjectFinder.Foreground.from_mapping(m.pop("foreground"))
+            if "refinement" in m:
+                p.refinement = ObjectFinder.Refinement.from_mapping(m.pop("refinement"))
             for k in ("nms_angle", "sigma_angle"):
                 if k + "_deg" in m:
                     m[k] = math.radians(float(m.pop(k + "_deg")))
@@ -108,7 +140,7 @@ class ObjectFinder:
                     setattr(p, f.name, getattr(self, f.name))
             return p
 
-    def __init__(self, sensor, object_model, params=None, foreground=None):
+    def __init__(self, sensor, object_model, params=None, foreground=None, refinement=None):
         self._lib = _capi.load()
         self.sensor = sensor
         self.params = params or ObjectFinder.Parameters()
@@ -122,12 +154,16 @@ class ObjectFinder:
         sensor._register_dependent(self)   # the finder borrows the sensor handle
         self.foreground = None
         foreground = self.params.foreground if foreground is None else foreground
-        if foreground is not None:
-            try:
+        self.refinement = None
+        refinement = self.params.refinement if refinement is None else refinement
+        try:
+            if foreground is not None:
                 self.set_foreground(foreground)
-            except Exception:
-                self.close()
-                raise
+            if refinement is not None:
+                self.set_refinement(refinement)
+        except Exception:
+            self.close()
+            raise
 
     def close(self):
         if getattr(self, "_f", None) is not None and self._f.value:
@@ -202,6 +238,33 @@ class ObjectFinder:
         g = foreground.c_params()
         self._check(self._lib.rbs_find_set_foreground(self._f, C.byref(g)))
         self.foreground = foreground
+
+    def set_refinement(self, refinement=None):
+        """Step 6b for the finds from the next one on; None (or enabled = False): off, step 6's fixed schedule.  Bad values
+        raise, and the previous setting stays."""
+        if refinement is None or not refinement.enabled:
+            self._check(self._lib.rbs_find_set_refinement(self._f, None))
+            self.refinement = None
+            return
+        g = refinement.c_params()
+        self._check(self._lib.rbs_find_set_refinement(self._f, C.byref(g)))
+        self.refinement = refinement
+
+    def covariance(self, round):
+        """The last find's covariances entering `round` [survivors, 6, 6] (round = rounds: the final ones); step 6b only."""
+        n = C.c_int64()
+        self._check(self._lib.rbs_find_get_covariance(self._f, round, None, C.byref(n)))
+        out = np.zeros((int(n.value), 6, 6))
+        self._check(self._lib.rbs_find_get_covariance(self._f, round, out.ctypes.data_as(C.POINTER(C.c_double)), C.byref(n)))
+        return out
+
+    def perturbations(self, round):
+        """The perturbations d of round `round`'s children [survivors * children, 6]; step 6b only."""
+        n = C.c_int64()
+        self._check(self._lib.rbs_find_get_perturbations(self._f, round, None, C.byref(n)))
+        out = np.zeros((int(n.value), 6))
+        self._check(self._lib.rbs_find_get_perturbations(self._f, round, out.ctypes.data_as(C.POINTER(C.c_double)), C.byref(n)))
+        return out
 
     def plane(self):
         """The last find's dominant plane (rbs_find_get_plane); the stage off: all zeros."""

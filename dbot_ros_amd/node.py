@@ -84,7 +84,7 @@ def build_gaussian_tracker(params, native_camera_matrix, mesh_package_path, devi
 def build_object_finder(params, native_camera_matrix, mesh_package_path, device_id=0, sensor=None):
     """The object finder that stands in for the controller's FindObject service
     (R:source/dbot_ros/tracker/object_tracker_controller_service_node.cpp:143-167): the object model and camera data
-    assembled as build_particle_tracker does, its parameters from the optional `object_finder:` mapping (its `foreground:` sub-mapping switches step 1b on).  sensor: a
+    assembled as build_particle_tracker does, its parameters from the optional `object_finder:` mapping (its `foreground:` sub-mapping switches step 1b on, its `refinement:` sub-mapping step 6b).  sensor: a
     sensor to search with (a tracker's own); None builds one from the tree.  Returns (finder, object_model,
     camera_data); close the finder, then a sensor built here (finder.sensor)."""
     from .finder import ObjectFinder
@@ -99,8 +99,9 @@ def build_object_finder(params, native_camera_matrix, mesh_package_path, device_
         params_obsrv = RbSensorBuilder.Parameters.from_rosparam(params)
         params_obsrv.sample_count = 1
         sensor = RbSensorBuilder(object_model, camera_data, params_obsrv, device_id=device_id).build()
-    finder_params = ObjectFinder.Parameters.from_rosparam(params)   # object_finder/foreground: step 1b's setting, passed through
-    return ObjectFinder(sensor, object_model, finder_params, foreground=finder_params.foreground), object_model, camera_data
+    finder_params = ObjectFinder.Parameters.from_rosparam(params)   # object_finder/foreground, /refinement: steps 1b and 6b, passed through
+    return (ObjectFinder(sensor, object_model, finder_params, foreground=finder_params.foreground, refinement=finder_params.refinement),
+            object_model, camera_data)
 
 
 def to_eigen_vector(native_image, downsampling_factor):

@@ -37,6 +37,11 @@ public:
         Foreground() { rbs_find_default_foreground(this); }
     };
 
+    /// rbs_find_refinement with the library's defaults, enabled (step 6b: every survivor's search covariance adapts to its best children).
+    struct Refinement : rbs_find_refinement {
+        Refinement() { rbs_find_default_refinement(this); }
+    };
+
     /// The last find's dominant plane, 1 / z = a u + b v + c over the coarse pixels (rbs_find_get_plane).
     struct Plane {
         bool accepted = false;
@@ -89,6 +94,26 @@ public:
     {
         if (rbs_find_set_foreground(f_, g) != RBS_OK)
             throw std::runtime_error(std::string("ObjectFinder::set_foreground: ") + rbs_find_last_error(f_));
+    }
+
+    /// Step 6b for the finds from the next one on; nullptr (or enabled == 0): off, step 6's fixed schedule.  Bad values throw,
+    /// the previous setting stays.
+    void set_refinement(const rbs_find_refinement* g)
+    {
+        if (rbs_find_set_refinement(f_, g) != RBS_OK)
+            throw std::runtime_error(std::string("ObjectFinder::set_refinement: ") + rbs_find_last_error(f_));
+    }
+
+    /// The last find's covariances entering `round` (round == rounds: the final ones), [survivors][36] row-major; step 6b only.
+    std::vector<Real> covariance(int round)
+    {
+        int64_t n = 0;
+        if (rbs_find_get_covariance(f_, round, nullptr, &n) != RBS_OK)
+            throw std::runtime_error(std::string("ObjectFinder::covariance: ") + rbs_find_last_error(f_));
+        std::vector<Real> out(36 * static_cast<size_t>(n));
+        if (rbs_find_get_covariance(f_, round, out.data(), &n) != RBS_OK)
+            throw std::runtime_error(std::string("ObjectFinder::covariance: ") + rbs_find_last_error(f_));
+        return out;
     }
 
     Plane plane()

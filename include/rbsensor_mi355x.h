@@ -691,6 +691,21 @@ int32_t rbs_gauss_result(rbs_gauss* g, double* out_state, double* out_cov);
  *                   are then sorted in step 5's order (by survivor index on ties); none is dropped here: those with a
  *                   NaN score come last, in survivor order, so poses [i] may carry scores [i] = NaN at the end, and
  *                   found is 0 when even the best score is NaN.
+ *   6b adaptive     opt-in (rbs_find_set_refinement; off by default), in place of step 6's fixed schedule.  Everything is
+ *      refinement   binary64 in the order written; apart from step 6's normals and R(v) the only operations are + - * / and
+ *                   sqrt.  Survivor k carries a symmetric 6 x 6 covariance C_k over (rotation vector (3), translation (3)),
+ *                   at the start diag(sa^2, sa^2, sa^2, st^2, st^2, st^2), sa = sigma_angle, st = sigma_translation; `decay`
+ *                   is not read.  Round r: L_k is the lower Cholesky factor of C_k by rows -- for i = 0..5, j = 0..i:
+ *                   s = C_ij, then s = s - L_ik L_jk for k = 0..j-1 ascending; L_ii = sqrt(s), L_ij = s / L_jj -- and when a
+ *                   pivot s is not > 0 or not finite, L_k := diag(sqrt(max(C_ii, jitter))), max(x, y) = x > y ? x : y.
+ *                   Child 0 is the survivor; child j > 0 has d = L_k n, d_a = L_a0 n_0 + L_a1 n_1 + ... + L_aa n_a summed in
+ *                   that order, n step 6's six normals from the same Philox counters, and R = R(d_0..2) R_k,
+ *                   t = t_k + d_3..5.  Scoring and keeping the best child are exactly step 6's: a survivor's score never
+ *                   goes down.  Then the update: the elite is the `elite` best children of the round in step 5's order
+ *                   (score descending, j ascending, NaN never); fewer children with a number: those m; m = 0: C_k stays.
+ *                   M_ab = (sum of d_a d_b over the elite, in elite order, from 0; child 0 has d = 0) / m, and
+ *                   C_ab <- shrink ((1 - mix) C_ab + mix M_ab), + jitter where a = b.  Steps 5 and 7 and the final sort are
+ *                   unchanged.  The covariances never leave the device between rounds.
  *   7 output        the k <= n_survivors best poses [k][12] (R row-major | t, the sensor's mesh frame) and their
  *                   scores; found = (best score >= min_score).  A frame without a valid seed: RBS_OK, found = 0,
  *                   *n_out = 0.
@@ -754,7 +769,7 @@ enum { RBS_FIND_SEEDS = 0, RBS_FIND_COARSE = 1, RBS_FIND_CANDIDATES = 2, RBS_FIN
 int32_t rbs_find_get_stage(rbs_find* f, int32_t stage, int32_t round, double* poses, double* scores, int64_t* indices,
                            int64_t* n, double* info);
 /* Device time of the last find's stages in ms (HIP events): [0] frame + seeds (step 1b included), [1] coarse scoring, [2] selection
- * (top-k + suppression), [3] refinement, [4] the whole find. */
+ * (top-k + suppression), [3] refinement (step 6 or 6b), [4] the whole find. */
 int32_t rbs_find_stage_ms(rbs_find* f, float* out5);
 /* Step 1b, the foreground.  Memory: one coarse frame and plane_trials records of 36 bytes, allocated when the stage is
  * first switched on. */
@@ -775,6 +790,27 @@ int32_t rbs_find_set_foreground(rbs_find* f, const rbs_find_foreground* g);
 int32_t rbs_find_get_plane(rbs_find* f, double* out8);
 /* The last find's seeding frame (the stage off: the coarse frame): *n := coarse rows * cols; out (may be NULL) [*n]. */
 int32_t rbs_find_get_seed_frame(rbs_find* f, float* out, int64_t* n);
+/* Step 6b, the adaptive refinement.  Memory, allocated when the stage is first switched on: per survivor 36 doubles for
+ * each of the rounds + 1 covariances kept for rbs_find_get_covariance and 36 for the current factor, and 6 doubles per child
+ * and round for the perturbations d. */
+typedef struct rbs_find_refinement {
+    int32_t enabled;               /* 0: the stage is off (a new finder)                                            */
+    int32_t elite;                 /* 8 (1 .. 64, <= children)                                                      */
+    double mix;                    /* 0.5, in [0, 1]: the weight of the elite's second moment                       */
+    double shrink;                 /* 1, in (0, 1]                                                                  */
+    double jitter;                 /* 1e-10 (>= 0, finite): added to the diagonal after every update                */
+} rbs_find_refinement;
+/* The defaults above with enabled = 1, stated once. */
+void rbs_find_default_refinement(rbs_find_refinement* g);
+/* The setting of the finds from the next rbs_find_run on.  NULL or enabled == 0: the stage is off, and a find is bit for
+ * bit that of a finder never configured.  Bad values: RBS_ERR_INVALID_ARGUMENT, and the previous setting stays. */
+int32_t rbs_find_set_refinement(rbs_find* f, const rbs_find_refinement* g);
+/* The last find's covariances entering round `round` (0 .. rounds; round == rounds: the final ones): *n := survivors,
+ * cov (may be NULL) [*n][36] row-major.  The last find ran without the stage: RBS_ERR_INVALID_ARGUMENT. */
+int32_t rbs_find_get_covariance(rbs_find* f, int32_t round, double* cov, int64_t* n);
+/* The perturbations d of round `round`'s children (0 .. rounds - 1), for the tests: *n := survivors * children,
+ * d (may be NULL) [*n][6], in RBS_FIND_CHILDREN's order. */
+int32_t rbs_find_get_perturbations(rbs_find* f, int32_t round, double* d, int64_t* n);
 /* Message of the last error on this finder. Never NULL. */
 const char* rbs_find_last_error(const rbs_find* f);
 

@@ -5,6 +5,7 @@ scoring.  Prints ONE JSON line:
       "stage_ms": {"frame_seeds", "coarse", "selection", "refinement"}, "hypotheses_per_s", "oracle_s",
       "found": {"dt_mm", "iou", "score", "truth_score"}, "nearest_candidate": {"dt_mm", "deg"},
       "nearest_survivor": {"dt_mm", "deg"}, "scene_seed", "seed_stride", "foreground", "plane": {...} | null,
+      "refinement", "rounds", "sigma_angle_deg", "sigma_translation",
       "seeds_by_label": {"plane", "object", "occluder"}, "meets_bar"}, ...]}
 
 Cases: M1, M2, M3 at 640x480 and M4 at 1280x960, the header's default parameters; one synth.make_frame frame per case
@@ -18,9 +19,11 @@ then rotation angle of that pose) -- whether the search had the object in hand b
 scenes' seeds (the accuracy bar's six scenes: --cases m1,m2,m3 --scene-seeds 101,102).  plane: the dominant plane the find
 took away (rbs_find_get_plane); seeds_by_label: the find's seeds on the background plane, the object and the occluder (labels
 from the noise-free scene); meets_bar: translation < 1 cm, IoU >= 0.85, score >= 0.98 x the truth's.  --oracle-poses 0 skips
-the oracle's timing.
+the oracle's timing.  --refinement switches step 6b on (the library's default setting); --sigma-angle (degrees),
+--sigma-translation (metres) and --rounds set the search's start and length for either refinement.
 Usage: python tools/find_object_timing.py [--finds N] [--oracle-poses P] [--cases m1,m2,m3,m4] [--foreground] [--seed-stride S]
-                                          [--scene-seeds 101,102]
+                                          [--scene-seeds 101,102] [--refinement] [--sigma-angle DEG] [--sigma-translation M]
+                                          [--rounds R]
 """
 import os
 
@@ -90,7 +93,8 @@ def oracle_s_per_pose(om, K, rows, cols, P, frame, poses):
     return s
 
 
-def run_case(name, finds, oracle_poses, seed=101, foreground=False, seed_stride=None):
+def run_case(name, finds, oracle_poses, seed=101, foreground=False, seed_stride=None, refinement=False, sigma_angle=None,
+             sigma_translation=None, rounds=None):
     mesh, cols, rows = CASES[name]
     om, cam, P = sc.make_scene((mesh,), cols, rows, max_particles=1)
     with RbSensor(om, cam, P, max_particles=1) as sensor:
@@ -98,7 +102,14 @@ def run_case(name, finds, oracle_poses, seed=101, foreground=False, seed_stride=
         p = ObjectFinder.Parameters()
         if seed_stride:
             p.seed_stride = seed_stride
-        with ObjectFinder(sensor, om, p, foreground=ObjectFinder.Foreground() if foreground else None) as fnd:
+        if sigma_angle is not None:
+            p.sigma_angle = math.radians(sigma_angle)
+        if sigma_translation is not None:
+            p.sigma_translation = sigma_translation
+        if rounds is not None:
+            p.rounds = rounds
+        with ObjectFinder(sensor, om, p, foreground=ObjectFinder.Foreground() if foreground else None,
+                          refinement=ObjectFinder.Refinement() if refinement else None) as fnd:
             fnd.find(frame)                                       # warm-up
             t0 = time.perf_counter()
             for _ in range(finds):
@@ -141,6 +152,8 @@ def run_case(name, finds, oracle_poses, seed=101, foreground=False, seed_stride=
             "oracle_s": round(per_coarse * hyp + per_full * children, 1),
             "found": found, "nearest_candidate": nearest(cp, truth), "nearest_survivor": nearest(sp, truth),
             "scene_seed": seed, "seed_stride": p.seed_stride, "foreground": bool(foreground), "plane": plane,
+            "refinement": bool(refinement), "rounds": p.rounds, "sigma_angle_deg": round(math.degrees(p.sigma_angle), 3),
+            "sigma_translation": p.sigma_translation,
             "seeds_by_label": dict(zip(("plane", "object", "occluder"), (int((seed_labels == k).sum()) for k in range(3)))),
             "meets_bar": meets}
 
@@ -153,8 +166,13 @@ def main():
     ap.add_argument("--foreground", action="store_true")
     ap.add_argument("--seed-stride", type=int, default=0)
     ap.add_argument("--scene-seeds", default="101")
+    ap.add_argument("--refinement", action="store_true")
+    ap.add_argument("--sigma-angle", type=float, default=None, help="degrees")
+    ap.add_argument("--sigma-translation", type=float, default=None, help="metres")
+    ap.add_argument("--rounds", type=int, default=None)
     a = ap.parse_args()
-    cases = [run_case(c, a.finds, a.oracle_poses, int(s), a.foreground, a.seed_stride) for c in a.cases.split(",")
+    cases = [run_case(c, a.finds, a.oracle_poses, int(s), a.foreground, a.seed_stride, a.refinement, a.sigma_angle, a.sigma_translation,
+                      a.rounds) for c in a.cases.split(",")
              for s in a.scene_seeds.split(",")]
     print(json.dumps({"tool": "find_object_timing", "cases": cases}))
 
