@@ -94,22 +94,20 @@ struct rbs_handle {
     int area_n = 0;
     bool wide = false;
     double area_frac = 0.0;     // last sampled stored-window area / frame area
-    double mid_enter = 0.15;    // above it: two raster blocks per CU, so the windowed copy runs beside them
+    static constexpr double mid_enter = 0.15;    // above it: two raster blocks per CU, so the windowed copy runs beside them
     // Raster / copy balance: the windowed copy kernel runs beside the persistent raster blocks and
     // a call ends when the later of the two does.  When the copy kernel outlasts the raster kernel
     // (several bodies far apart: one window spans them and the copy fills the gaps) the next calls
     // run a few raster blocks fewer, and take them back when the raster kernel is the later one
     // again.  Decided from the kernel timers of the last timed call; the results do not depend on
-    // the number of blocks.  RBS_BALANCE=0 pins the grid.
-    bool balance = true;
+    // the number of blocks.
     int balance_blocks = 0;     // current grid of the raster kernel (0: raster_blocks)
     long balance_seen = 0;      // timed_calls the rule has looked at
     double wide_enter = 0.50, wide_leave = 0.35;   // measured: the streaming copy wins from about half the frame
     int cu_count = 256;
     int smalln_target = 768;    // few particles: aim at about this many work items per call
-    int rect_align = 4;         // windowed planes: rectangles move in float4 columns
-    int win_chunks = 8;         // row chunks (blocks) per particle of the windowed copy kernel (several bodies: it walks the whole window)
-    int win_chunks_single = 2;  // ... one body: it enumerates only the cells outside the rectangle, a tenth of the window
+    static constexpr int win_chunks = 8;         // row chunks (blocks) per particle of the windowed copy kernel (several bodies: it walks the whole window)
+    static constexpr int win_chunks_single = 2;  // ... one body: it enumerates only the cells outside the rectangle, a tenth of the window
     int upload_chunks = 2;      // pieces a caller's host frame is staged and sent in (RBS_UPLOAD_CHUNKS) ...
     bool quiet = false;         // ... while nothing long of this handle's is running on the device (set by the entry points that
                                 // wait for results, cleared by every launch): behind a running raster kernel the second piece's
@@ -168,7 +166,6 @@ struct rbs_handle {
     int precision = RBS_PRECISION_F64;
     // Stamped planes (rbs_config.occlusion_mode = RBS_OCC_REFERENCE; DevParams::exact): a slot is plane_px floats + plane_px
     // 16-bit ages, plane_stride floats in all.
-    bool one_body_kernel = true;    // single-body models take rbs_raster_kernel_one_f64 (RBS_ONE_BODY=0, tooling: the general kernel)
     bool fused_copy = true;         // windowed copy inside the raster kernel where it applies (RBS_FUSED_COPY=0, tooling / A-B: the side-stream kernel)
     bool exact = false;
     int age_max = 0;            // ages beyond it are background
@@ -189,7 +186,7 @@ struct rbs_handle {
     hipEvent_t ev_out = nullptr;
     float* h_frames[2] = {nullptr, nullptr};   // pinned frame staging, alternating
     float* h_frames_dev[2] = {nullptr, nullptr};   // ... as the device addresses them
-    size_t frame_pull_bytes = 128 * 1024;      // frames up to this size are read from the staging buffer by a kernel (RBS_FRAME_PULL_BYTES)
+    static constexpr size_t frame_pull_bytes = 128 * 1024;   // frames up to this size are read from the staging buffer by a kernel
     hipEvent_t ev_frame[2] = {nullptr, nullptr};   // the upload out of h_frames[k] into d_fin[k] has finished
     // Host frames travel on their own stream into one of two device staging buffers, and the launch
     // stream only waits for the upload where it ingests the frame: a frame handed over while the
@@ -220,11 +217,8 @@ struct rbs_handle {
     hipStream_t stream = nullptr;
     hipStream_t copy_stream = nullptr;   // the copy kernel runs here, beside the raster kernel
     hipEvent_t ev_fork = nullptr;
-    int copy_blocks = 1 << 30;  // cap on the copy grid (one block per (particle, band) below it)
+    static constexpr int copy_blocks = 1 << 30;  // cap on the copy grid (one block per (particle, band) below it)
     int raster_blocks = 768;    // persistent raster grid: 3 per CU
-    int copy_rows = 2;          // rows per block of rbs_copy_rows_kernel (0: banded kernel)
-    int copy_tpb = 64;          // threads per copy block: one wave = 1 KB of a row (0: a block spans a row)
-    const char* tile_override = nullptr;  // RBS_TILE env (tuning)
     // timing ring: HIP events around the whole call (on the launch stream) and around the copy
     // kernel (on the copy stream) for the last kRing loglikes calls
     static constexpr int kRing = 256;
@@ -563,7 +557,7 @@ int32_t upload_frame(rbs_handle* h, const float* src, const float* pageable = nu
     // job costs ~11 us before it moves a byte and ~9 more until a kernel behind it starts.  The kernel that computes
     // the frame's model terms reads it where the host staged it (this handle's pinned buffer, over PCIe) and leaves
     // the observation in d_fin[k] as it goes (precision F32: that copy is all it does).
-    const bool pull = h->frame_pull_bytes > 0 && n * sizeof(float) <= h->frame_pull_bytes && h->h_frames_dev[k] &&
+    const bool pull = n * sizeof(float) <= h->frame_pull_bytes && h->h_frames_dev[k] &&
                       (pageable || pageable_f64 || src == h->h_frames[k]);
     if (pageable || pageable_f64) {
         float* stage = h->h_frames[k];
@@ -773,7 +767,7 @@ void frame_abandon(rbs_handle* h)
 // whole planes or slabs, and the same eight again for object models with a body of many clusters.
 void launch_raster(const rbs_handle* h, bool update, dim3 grid, dim3 block, size_t smem, hipStream_t s, const DevParams& P)
 {
-    if (h->exact && h->one_body_kernel && !h->many_clusters && h->n_bodies == 1 && !P.groups) {   // stamped planes, one body
+    if (h->exact && !h->many_clusters && h->n_bodies == 1 && !P.groups) {   // stamped planes, one body
 #define RBS_X(U, S, T) hipLaunchKernelGGL((rbs::rbs_raster_kernel_exact_one_f64<U, S, T>), grid, block, smem, s, P); break
         switch ((update ? 4 : 0) | (h->slab_px ? 2 : 0) | (P.bgp_src ? 1 : 0)) {
             case 0: RBS_X(false, false, false);  case 1: RBS_X(false, false, true);
@@ -823,7 +817,7 @@ void launch_raster(const rbs_handle* h, bool update, dim3 grid, dim3 block, size
         }
         return;
     }
-    if (h->one_body_kernel && !h->many_clusters && h->precision == RBS_PRECISION_F64 && h->n_bodies == 1 && !P.groups) {
+    if (!h->many_clusters && h->precision == RBS_PRECISION_F64 && h->n_bodies == 1 && !P.groups) {
         switch ((update ? 2 : 0) | (h->slab_px ? 1 : 0)) {
             case 0: hipLaunchKernelGGL((rbs::rbs_raster_kernel_one_f64<false, false>), grid, block, smem, s, P); break;
             case 1: hipLaunchKernelGGL((rbs::rbs_raster_kernel_one_f64<false, true>), grid, block, smem, s, P); break;
@@ -914,7 +908,7 @@ int32_t enqueue_loglikes(rbs_handle* h, const double* d_poses, const int* d_indi
         P.bg_old = P.bg_new;
     }
     P.windowed = h->windowed ? 1 : 0;
-    P.rect_align = h->windowed ? h->rect_align : rbs::kRectAlign;
+    P.rect_align = h->windowed ? rbs::kRectAlignWindowed : rbs::kRectAlign;
     P.win_src = h->d_win[h->cur];
     P.win_dst = h->d_win[1 - h->cur];
     P.win_used = h->d_win_used;
@@ -1045,7 +1039,6 @@ int32_t enqueue_loglikes(rbs_handle* h, const double* d_poses, const int* d_indi
     if (split && !h->exact && !(!h->windowed && h->raster_blocks <= 2 * h->cu_count)) P.tile_px = rbs::kDepthTilePx;   // (= kTilePxF64 already; stamped planes: their own, smaller)
     P.tile_w = 256;
     P.tile_h = std::max(4, P.tile_px / 256 / std::max(1, h->smalln_target / std::max(1, n)));
-    if (const char* m = h->tile_override) { P.tile_w = std::max(16, std::atoi(m) / 16 * 16); P.tile_h = std::max(1, std::atoi(m)); }
     const size_t tiles_max = tiles_upper_bound(h->cols, h->rows, P.tile_w, std::min(P.tile_w * P.tile_h, P.tile_px));
     const size_t need = (size_t)n * tiles_max * (h->d_groups[0] ? rbs::kMaxGroups : 1);
     if (need > h->partial_cap) {
@@ -1158,8 +1151,7 @@ int32_t enqueue_loglikes(rbs_handle* h, const double* d_poses, const int* d_indi
     // the windowed copy done by the raster kernel's own blocks (rbs_raster_kernel_wcopy_*: one body, one rectangle, scalar
     // background, whole planes, one device): the call is then prep + raster on this stream -- no fork, no second queue, no join
     const bool fused = h->fused_copy && update && h->windowed && !wide && !mid && !split && !h->exact && !h->slab_px && !P.bgp_src &&
-                       !P.groups && h->n_bodies == 1 && !h->many_clusters && !h->group && h->peer_world <= 1 && !h->ipc_exported &&
-                       (h->precision == RBS_PRECISION_F32 || h->one_body_kernel);
+                       !P.groups && h->n_bodies == 1 && !h->many_clusters && !h->group && h->peer_world <= 1 && !h->ipc_exported;
     if (timed && fused) h->ring_update[tslot] = false;   // (no copy kernel to time: timing_summary's copy_kernel_ms is 0)
     if (const float* df = take_device_frame(h, s)) {   // a device frame pending on this stream rides on the rectangles kernel
         launch_prep(P, d_rects, update ? 1 : 0, false, df, h->d_aux, h->d_pbg, df == h->d_frame ? (float*)nullptr : h->d_frame, s);
@@ -1190,7 +1182,7 @@ int32_t enqueue_loglikes(rbs_handle* h, const double* d_poses, const int* d_indi
         RBS_HIP(h, hipStreamWaitEvent(s, h->ev_join[h->join_pending], 0));
         h->join_pending = -1;
     }
-    if (h->balance && h->windowed && update && !wide && !mid && !fused && h->timed_calls > h->balance_seen && h->raster_blocks == 3 * h->cu_count) {
+    if (h->windowed && update && !wide && !mid && !fused && h->timed_calls > h->balance_seen && h->raster_blocks == 3 * h->cu_count) {
         const int last = (int)((h->timed_calls - 1) % rbs_handle::kRing);
         if (h->ring_update[last] && hipEventQuery(h->ev_raster_stop[last]) == hipSuccess && hipEventQuery(h->ev_copy_stop[last]) == hipSuccess) {
             float r_ms = 0.f, c_ms = 0.f;
@@ -1207,7 +1199,7 @@ int32_t enqueue_loglikes(rbs_handle* h, const double* d_poses, const int* d_indi
             h->balance_seen = h->timed_calls;
         }
     }
-    const int full_grid = h->balance && h->balance_blocks && h->windowed && update && !fused ? h->balance_blocks : h->raster_blocks;
+    const int full_grid = h->balance_blocks && h->windowed && update && !fused ? h->balance_blocks : h->raster_blocks;
     const dim3 rgrid((unsigned)(wide || mid ? std::min(h->raster_blocks, 2 * h->cu_count) : full_grid));
     // a host frame that is read where it was uploaded: only now does the stream wait for the upload
     // (split launch: the geometry kernel needs no frame -- the wait sits between the two kernels, and a host frame
@@ -1222,8 +1214,8 @@ int32_t enqueue_loglikes(rbs_handle* h, const double* d_poses, const int* d_indi
         if (timed) RBS_HIP(h, hipEventRecord(h->ev_copy_start[tslot], h->copy_stream));
         const int ny = std::min(n, 32768);
         // one body: only the cells outside its rectangle are enumerated (1); several bodies: the strip list the rectangles kernel
-        // made (2: round 6); RBS_COPY_STRIPS=0 builds / RBS_COPY_WALK=1: the walk over the whole region (0)
-        const int strips = !RBS_COPY_STRIPS ? 0 : !P.groups ? 1 : (P.strips ? 2 : 0);
+        // made (2: round 6); RBS_COPY_WALK=1: the walk over the whole region (0)
+        const int strips = !P.groups ? 1 : (P.strips ? 2 : 0);
         const dim3 wg((unsigned)(strips == 1 ? h->win_chunks_single : h->win_chunks), (unsigned)ny, (unsigned)((n + ny - 1) / ny));
 #define RBS_X3(S, B, E)                                                                                                             \
         do {                                                                                                                        \
@@ -1253,8 +1245,7 @@ int32_t enqueue_loglikes(rbs_handle* h, const double* d_poses, const int* d_indi
         if (h->many_clusters) hipLaunchKernelGGL((rbs::rbs_depth_kernel<true>), dgrid, block, dsm, s, P);
         else hipLaunchKernelGGL((rbs::rbs_depth_kernel<false>), dgrid, block, dsm, s, P);
         RBS_HIP(h, hipGetLastError());
-        static const bool copy_first = [] { const char* e = std::getenv("RBS_SPLIT_COPY_FIRST"); return e ? std::atoi(e) != 0 : true; }();
-        if (copy_first && have_borrowed && update && h->windowed && !wide)
+        if (have_borrowed && update && h->windowed && !wide)
             if (int32_t rc = launch_window_copy()) return rc;
         if (have_borrowed) {   // the host converts and sends the caller's frame while the depth tiles are rasterized
             if (int32_t rc = stage_borrowed(h)) {
@@ -1301,7 +1292,6 @@ int32_t enqueue_loglikes(rbs_handle* h, const double* d_poses, const int* d_indi
         else if (!split) launch_raster(h, true, rgrid, block, rsm, s, P);
         RBS_HIP(h, hipGetLastError());
         if (timed) RBS_HIP(h, hipEventRecord(h->ev_raster_stop[tslot], s));
-        const dim3 cgrid((unsigned)std::min<long>((long)h->copy_blocks, (long)n * P.bands));
         if (timed && (!h->windowed || wide)) RBS_HIP(h, hipEventRecord(h->ev_copy_start[tslot], h->copy_stream));
         if (fused) {
             // (done: the raster kernel wrote the particles' cells outside their rectangles)
@@ -1318,24 +1308,16 @@ int32_t enqueue_loglikes(rbs_handle* h, const double* d_poses, const int* d_indi
             P.wide_flags = h->d_wide_flags;
             hipLaunchKernelGGL((rbs::rbs_copy_rows_kernel<2, true>), rg, dim3(64), 0, h->copy_stream, P, nseg);
             hipLaunchKernelGGL(rbs::rbs_wide_window_kernel, dim3((unsigned)n), dim3(64), 0, h->copy_stream, P, nseg, nblk);
-        } else if ((P.cols & 3) == 0 && h->copy_rows > 0) {
+        } else if ((P.cols & 3) == 0) {   // two rows per one-wave block: a wave moves 1 KB of a row
             const int W4 = P.cols >> 2;
-            const int tpb = h->copy_tpb > 0 ? h->copy_tpb : std::min(1024, (W4 + 63) / 64 * 64);
-            const int nseg = (W4 + tpb - 1) / tpb;
-            const dim3 rblock((unsigned)tpb);
+            const int nseg = (W4 + 63) / 64;
             const int ny = std::min(n, 32768);
-            const dim3 rg((unsigned)(((P.rows + h->copy_rows - 1) / h->copy_rows) * nseg), (unsigned)ny,
-                          (unsigned)((n + ny - 1) / ny));
-            switch (h->copy_rows) {
-                case 1: hipLaunchKernelGGL((rbs::rbs_copy_rows_kernel<1, false>), rg, rblock, 0, h->copy_stream, P, nseg); break;
-                case 2: hipLaunchKernelGGL((rbs::rbs_copy_rows_kernel<2, false>), rg, rblock, 0, h->copy_stream, P, nseg); break;
-                case 4: hipLaunchKernelGGL((rbs::rbs_copy_rows_kernel<4, false>), rg, rblock, 0, h->copy_stream, P, nseg); break;
-                default: hipLaunchKernelGGL((rbs::rbs_copy_rows_kernel<8, false>), rg, rblock, 0, h->copy_stream, P, nseg); break;
-            }
-        } else if ((P.cols & 3) == 0)
-            hipLaunchKernelGGL((rbs::rbs_copy_kernel<4>), cgrid, block, 0, h->copy_stream, P);
-        else
+            const dim3 rg((unsigned)(((P.rows + 1) / 2) * nseg), (unsigned)ny, (unsigned)((n + ny - 1) / ny));
+            hipLaunchKernelGGL((rbs::rbs_copy_rows_kernel<2, false>), rg, dim3(64), 0, h->copy_stream, P, nseg);
+        } else {
+            const dim3 cgrid((unsigned)std::min<long>((long)h->copy_blocks, (long)n * P.bands));
             hipLaunchKernelGGL((rbs::rbs_copy_kernel<1>), cgrid, block, 0, h->copy_stream, P);
+        }
         RBS_HIP(h, hipGetLastError());
         if (!h->windowed || wide) {
             if (timed) RBS_HIP(h, hipEventRecord(h->ev_copy_stop[tslot], h->copy_stream));
@@ -1801,9 +1783,8 @@ int32_t create_impl(const rbs_config* cfg, rbs_handle* h)
     rbs::PreparedMesh mesh;
     {
         const rbs::MeshInput in = {cfg->n_objects, cfg->vertices, cfg->vertex_counts, cfg->triangles, cfg->triangle_counts};
-        const bool allow_cull = !(std::getenv("RBS_NO_CULL") && std::atoi(std::getenv("RBS_NO_CULL")));
         std::string why;
-        if (const int rc = rbs::prepare_mesh(in, allow_cull, &mesh, &why)) return fail(h, rc, why);
+        if (const int rc = rbs::prepare_mesh(in, /*allow_cull=*/true, &mesh, &why)) return fail(h, rc, why);
         std::copy(std::begin(mesh.tri_begin), std::end(mesh.tri_begin), B.tri_begin);
         std::copy(std::begin(mesh.tri_end), std::end(mesh.tri_end), B.tri_end);
         std::copy(std::begin(mesh.vtx_begin), std::end(mesh.vtx_begin), B.vtx_begin);
@@ -1852,36 +1833,24 @@ int32_t create_impl(const rbs_config* cfg, rbs_handle* h)
         // tuning overrides (defaults are the measured best on MI355X)
         if (const char* m = std::getenv("RBS_RASTER_BLOCKS")) h->raster_blocks = std::max(1, std::atoi(m));
         if (const char* m = std::getenv("RBS_SHARED_TRAIL")) h->stp_allowed = std::atoi(m) != 0;
-        if (const char* m = std::getenv("RBS_ONE_BODY")) h->one_body_kernel = std::atoi(m) != 0;
         if (const char* m = std::getenv("RBS_FUSED_COPY")) h->fused_copy = std::atoi(m) != 0;
         if (const char* m = std::getenv("RBS_TRACKER_SPLIT_MAX")) h->tracker_split_max = std::atoi(m);
         if (const char* m = std::getenv("RBS_STP_ENTER")) h->stp_enter = std::atof(m);
         if (const char* m = std::getenv("RBS_STP_EVERY")) h->stp_every = std::max(1, std::atoi(m));
-        h->split = RBS_SPLIT_DEFAULT != 0;
         if (const char* m = std::getenv("RBS_SPLIT")) h->split = std::atoi(m) != 0;
         h->depth_blocks = RBS_DEPTH_MINWAVES * h->cu_count;
         h->eval_blocks = RBS_EVAL_MINWAVES * h->cu_count;
-        if (const char* m = std::getenv("RBS_DEPTH_BLOCKS")) h->depth_blocks = std::max(1, std::atoi(m));
-        if (const char* m = std::getenv("RBS_EVAL_BLOCKS")) h->eval_blocks = std::max(1, std::atoi(m));
-        h->tile_override = std::getenv("RBS_TILE");
-        if (const char* m = std::getenv("RBS_COPY_ROWS")) h->copy_rows = std::atoi(m);
-        if (const char* m = std::getenv("RBS_COPY_TPB")) h->copy_tpb = std::max(64, std::atoi(m) / 64 * 64);
         // the layout is the caller's choice (rbs_config.state_layout); the environment is consulted
         // only when the caller leaves it open (tools comparing both layouts of an unchanged caller)
         if (cfg->state_layout == RBS_STATE_DENSE) h->windowed = false;
         else if (cfg->state_layout == RBS_STATE_DEFAULT)
             if (const char* m = std::getenv("RBS_STATE")) h->windowed = std::strcmp(m, "dense") != 0;
         h->smalln_target = 2 * std::max(1, prop.multiProcessorCount);   // measured best at 64..500 particles
-        if (const char* m = std::getenv("RBS_SMALLN_TARGET")) h->smalln_target = std::max(1, std::atoi(m));
-        if (const char* m = std::getenv("RBS_MID_ENTER")) h->mid_enter = std::atof(m);
-        if (const char* m = std::getenv("RBS_BALANCE")) h->balance = std::atoi(m) != 0;
         if (const char* m = std::getenv("RBS_WIDE_ENTER")) { h->wide_enter = std::atof(m); h->wide_leave = h->wide_enter * 0.67; }
-        if (const char* m = std::getenv("RBS_RECT_ALIGN")) h->rect_align = std::atoi(m) >= 16 ? 16 : (std::atoi(m) >= 8 ? 8 : 4);
         if (const char* m = std::getenv("RBS_TIMING_EVERY")) h->timing_every = std::max(1, std::atoi(m));
-        if (const char* m = std::getenv("RBS_WIN_CHUNKS")) h->win_chunks = h->win_chunks_single = std::min(1024, std::max(1, std::atoi(m)));
         if (const char* m = std::getenv("RBS_UPLOAD_CHUNKS")) h->upload_chunks = std::min(16, std::max(1, std::atoi(m)));
         if (h->cols & 3) h->windowed = false;   // windows move whole float4s
-        h->base.rect_align = h->windowed ? h->rect_align : rbs::kRectAlign;
+        h->base.rect_align = h->windowed ? rbs::kRectAlignWindowed : rbs::kRectAlign;
         // whole planes: the big copy kernel must run BESIDE the raster kernel, and three raster
         // blocks per CU hold 504 of a SIMD's 512 VGPRs -- two leave room for the copy waves
         if (!h->windowed && !std::getenv("RBS_RASTER_BLOCKS")) h->raster_blocks = 2 * std::max(1, prop.multiProcessorCount);
@@ -1963,7 +1932,7 @@ int32_t create_impl(const rbs_config* cfg, rbs_handle* h)
     RBS_HIP(h, hipMalloc(&h->d_indices, sizeof(int) * (size_t)h->max_particles));
     RBS_HIP(h, hipMalloc(&h->d_rects[0], sizeof(int) * 4 * (size_t)h->max_particles));
     RBS_HIP(h, hipMalloc(&h->d_rects[1], sizeof(int) * 4 * (size_t)h->max_particles));
-    if (h->n_bodies > 1 && !(std::getenv("RBS_NO_GROUPS") && std::atoi(std::getenv("RBS_NO_GROUPS")))) {
+    if (h->n_bodies > 1) {
         RBS_HIP(h, hipMalloc(&h->d_groups[0], sizeof(rbs::Groups) * (size_t)h->max_particles));
         RBS_HIP(h, hipMalloc(&h->d_groups[1], sizeof(rbs::Groups) * (size_t)h->max_particles));
         if (const char* e = std::getenv("RBS_COPY_WALK")) h->copy_walk = std::atoi(e) != 0;
@@ -1996,7 +1965,6 @@ int32_t create_impl(const rbs_config* cfg, rbs_handle* h)
     B.tri_plane = reinterpret_cast<const rbs::floatx4*>(h->d_tri_plane);
     if (int32_t rc = upload(h, &h->d_vtx, mesh.vtx, 4)) return rc;   // float32 copy of the vertices, per body (screen rectangles)
     B.vtx = reinterpret_cast<const rbs::floatx4*>(h->d_vtx);
-    if (const char* e = std::getenv("RBS_FRAME_PULL_BYTES")) h->frame_pull_bytes = (size_t)std::max(0L, std::atol(e));
     RBS_HIP(h, hipStreamCreateWithFlags(&h->up_stream, hipStreamNonBlocking));
     for (int k = 0; k < 2; ++k) {
         RBS_HIP(h, hipHostMalloc(&h->h_frames[k], plane, hipHostMallocPortable));   // (every device of a group uploads from shard 0's)
@@ -2995,7 +2963,7 @@ int32_t rbs_loglikes_device(rbs_handle* h, const double* d_poses, const int32_t*
         P.poses = d_poses; P.indices = d_indices; P.n = n;
         P.slots = h->max_particles; P.n_dev = 1; P.shard_cap = h->max_particles;
         P.win_src = h->d_win[h->cur];
-        P.rect_align = h->windowed ? h->rect_align : rbs::kRectAlign;
+        P.rect_align = h->windowed ? rbs::kRectAlignWindowed : rbs::kRectAlign;
         if (int32_t rc = drain(h, false)) return rc;
         int* d_max = h->d_err + 1;   // (the sticky maximum the rectangles kernel keeps: the probe only raises it early)
         hipLaunchKernelGGL(rbs::rbs_region_probe_kernel, dim3((unsigned)((n + rbs::kPrepPerBlock - 1) / rbs::kPrepPerBlock)),
@@ -3344,7 +3312,6 @@ int32_t rbs_ipc_attach(rbs_handle* h, int32_t rank, int32_t world, const void* b
 #endif
     if ((long)world * h->max_particles > 0x7fffffffL) return fail(h, RBS_ERR_INVALID_ARGUMENT, "ipc_attach: too many global slots");
     RBS_HIP(h, hipSetDevice(h->device));
-    if (std::getenv("RBS_DEBUG_IPC")) std::fprintf(stderr, "[rbs ipc] rank %d attach: draining\n", rank);
     if (int32_t rc = drain(h, true)) return rc;
     const unsigned char* raw = static_cast<const unsigned char*>(blobs);
     for (int k = 0; k < world; ++k) {
@@ -3373,9 +3340,7 @@ int32_t rbs_ipc_attach(rbs_handle* h, int32_t rank, int32_t world, const void* b
         for (int m = 0; m < 6; ++m) {
             if (m >= 4 && !h->slab_px) break;
             void* p = nullptr;
-            if (std::getenv("RBS_DEBUG_IPC")) std::fprintf(stderr, "[rbs ipc] rank %d opens rank %d buffer %d\n", rank, k, m);
             const hipError_t e = hipIpcOpenMemHandle(&p, b.mem[m], hipIpcMemLazyEnablePeerAccess);
-            if (std::getenv("RBS_DEBUG_IPC")) std::fprintf(stderr, "[rbs ipc] rank %d opened rank %d buffer %d -> %p (%d)\n", rank, k, m, p, (int)e);
             if (e != hipSuccess) {
                 (void)hipGetLastError();
                 return fail(h, RBS_ERR_HIP, fmt("hipIpcOpenMemHandle(rank %d, buffer %d): %s", k, m, hipGetErrorString(e)));
@@ -4215,9 +4180,8 @@ int32_t rbs_tracker_result(rbs_tracker* t, double* out_state, int32_t* out_resam
         // the frame's number behind it with a system-scope release: spin on that number -- the signalling
         // of the kernel's completion and the wake-up behind it cost several microseconds more.  The
         // event is the fall-back (and the only way with slabs, whose error word arrives by a copy).
-        static const bool spin = [] { const char* e = std::getenv("RBS_TRACKER_SPIN"); return !(e && std::atoi(e) == 0); }();
         bool seen = false;
-        if (spin && !t->s->slab_px && t->res_seq[slot] > 0) {
+        if (!t->s->slab_px && t->res_seq[slot] > 0) {
             volatile int* seq = t->h_flags[slot] + 2;
             for (long it = 0; it < 4000000 && !seen; ++it) {
                 seen = __atomic_load_n(seq, __ATOMIC_ACQUIRE) == t->res_seq[slot];

@@ -57,26 +57,8 @@ namespace rbs {
 #ifndef RBS_COPY_UNROLL
 #define RBS_COPY_UNROLL 8
 #endif
-#ifndef RBS_NT
-#define RBS_NT 1
-#endif
 #ifndef RBS_BIG_THRESH
 #define RBS_BIG_THRESH 96
-#endif
-// float32 filter of the coverage test in the per-lane sample loops (tri_filter): bit-exact by
-// construction and green on every depth test, but MEASURED SLOWER on C1 (raster kernel F32 0.146 ->
-// 0.154 ms, F64 0.184 -> 0.187): the loop's instruction count barely moves (36 -> 29 per sample, +25
-// per triangle for the filter's coefficients), and its binary64 edge functions were filling the
-// bubbles of the division's dependent chain for free.  Two samples per trip (two divisions in
-// flight) measured no better either (0.146 -> 0.149).  Off by default; kept as the documented experiment.
-#ifndef RBS_EDGE_FILTER
-#define RBS_EDGE_FILTER 0
-#endif
-#ifndef RBS_PIN_EDGES
-#define RBS_PIN_EDGES 1        // raster_lane_samples: the edge components stay in registers across the sample loops
-#endif
-#ifndef RBS_SHARE_VERTICES
-#define RBS_SHARE_VERTICES 1   // raster_shared_cluster (0: every triangle transforms its own three vertices)
 #endif
 
 #ifndef RBS_BLOCK
@@ -87,10 +69,7 @@ constexpr int kTilePx = RBS_TILE_PX;       // LDS depth tile (u32 per pixel) of 
 constexpr int kTilePxBig = 16384;          // ... of a launch with 2 blocks per CU (whole planes / wide windows)
 // Precision F64 keeps the erfc and log tables of rbs_math.h in LDS (per-lane table reads: 5.9 KB
 // per block), taken from the depth tile so that the same number of blocks stays resident.
-#ifndef RBS_MATH_LDS
-#define RBS_MATH_LDS 1
-#endif
-constexpr int kMathTabDoubles = RBS_MATH_LDS ? rbsm::kErfcIntervals * rbsm::kErfcCoefs + rbsm::kLogIntervals * 2 : 0;
+constexpr int kMathTabDoubles = rbsm::kErfcIntervals * rbsm::kErfcCoefs + rbsm::kLogIntervals * 2;
 constexpr int kMathTabPx = (kMathTabDoubles * 8 + 63) / 64 * 16;   // the tables' size in tile pixels, a multiple of 16
 constexpr int kTilePxF64 = kTilePx - kMathTabPx, kTilePxBigF64 = kTilePxBig - kMathTabPx;
 #ifndef RBS_BIG_CAP
@@ -125,6 +104,7 @@ constexpr int kCullSteps = 28;              // steps of 64 clusters culled betwe
                                             // left below the next 1 280-byte step (three blocks per CU, RBS_TILE_PX)
 constexpr int kQPlanes = kQPlanes_;                 // ints per queued pixel: index, depth, prior, observation (F32 precision)
 constexpr int kRectAlign = 16;              // whole planes: rectangle x-alignment in pixels (64 B)
+constexpr int kRectAlignWindowed = 4;       // windowed planes: rectangles move in float4 columns
 constexpr float kSnapTau = 0x1p-18f;         // background snap of the occlusion process (oracle ORC_SNAP_TAU)
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 constexpr unsigned kInfBits = 0x7f800000u;
@@ -469,21 +449,13 @@ __device__ inline Rect particle_rect(const DevParams& P, const double* __restric
 // or beyond 2^1000) the result may be inf / NaN / off where IEEE gives a finite huge or tiny
 // number: every use below rejects those values on both sides (a depth must be a positive finite
 // float, a bounding box must not be empty or NaN), so outcomes stay identical to the oracle's.
-// RBS_IEEE_DIV=1 restores the plain operator (A/B builds).
-#ifndef RBS_IEEE_DIV
-#define RBS_IEEE_DIV 0
-#endif
 __device__ inline double div_f64(double a, double b)
 {
-#if RBS_IEEE_DIV
-    return a / b;
-#else
     double r = __builtin_amdgcn_rcp(b);
     r = __builtin_fma(r, __builtin_fma(-b, r, 1.0), r);
     r = __builtin_fma(r, __builtin_fma(-b, r, 1.0), r);
     const double q = a * r;
     return __builtin_fma(__builtin_fma(-b, q, a), r, q);
-#endif
 }
 
 // ------------------------------------------------------------------ triangle setup
@@ -492,40 +464,7 @@ struct Tri {
     double e01u, e01v, e12u, e12v, e20u, e20v;
     double pa, pb, pc, nv0;
     int xlo, xhi, ylo, yhi;
-    // float32 FILTER of the three edge functions over the bounding box (tri_filter): sample (i, j)
-    // of the box has E_k ~ fB[k] i + fA[k] j + fC[k] with |error| < thr
-    float fA[3], fB[3], fC[3], thr;
 };
-
-// The coverage rule is a sign test on three binary64 edge functions, 21 binary64 instructions per
-// sample -- and a binary64 instruction holds the VALU 1.65x as long as a float32 one on this chip
-// (profiles/r03_valu_issue_microbench.txt).  An exact floating-point FILTER decides almost every
-// sample in float32 instead: the edge functions are evaluated in box-local coordinates (vertex
-// minus the box's corner, rounded to float: magnitudes of a few pixels, not hundreds) with a
-// rigorous bound `thr` on their distance from the oracle's binary64 values; all three clearly
-// positive or all clearly negative -> covered, one clearly positive and one clearly negative ->
-// not covered, anything else (a sample within `thr` of an edge: about one in 1e4, or a non-finite
-// intermediate) -> the oracle's own binary64 expression decides (tri_inside_exact).  Coverage is
-// therefore bit-exact by construction.
-// Bound: with L = max(box width, box height) + 1 every local coordinate, edge component and sample
-// offset is <= 2L in magnitude; the local vertices carry a relative rounding u = 2^-24, the edges
-// 2 more, each product and sum one more: |E_float - E_exact| <= 32 u L^2 (generous), and the
-// oracle's binary64 value is within 1e-13 L^2 of E_exact.  thr = 64 u L^2.
-__device__ inline void tri_filter(Tri& T, double xlo_d, double ylo_d)
-{
-    const float lu0 = (float)(T.u0 - xlo_d), lv0 = (float)(T.v0 - ylo_d);
-    const float lu1 = (float)(T.u1 - xlo_d), lv1 = (float)(T.v1 - ylo_d);
-    const float lu2 = (float)(T.u2 - xlo_d), lv2 = (float)(T.v2 - ylo_d);
-    // E_k(i, j) = eu_k (j - lv_k) - ev_k (i - lu_k)
-    const float eu0 = lu1 - lu0, ev0 = lv1 - lv0;
-    const float eu1 = lu2 - lu1, ev1 = lv2 - lv1;
-    const float eu2 = lu0 - lu2, ev2 = lv0 - lv2;
-    T.fA[0] = eu0; T.fB[0] = -ev0; T.fC[0] = fmaf(ev0, lu0, -(eu0 * lv0));
-    T.fA[1] = eu1; T.fB[1] = -ev1; T.fC[1] = fmaf(ev1, lu1, -(eu1 * lv1));
-    T.fA[2] = eu2; T.fB[2] = -ev2; T.fC[2] = fmaf(ev2, lu2, -(eu2 * lv2));
-    const float L = (float)(max(T.xhi - T.xlo, T.yhi - T.ylo) + 2);
-    T.thr = (64.0f * 0x1p-24f) * L * L;
-}
 
 // Same operations, same order as oracle/rbsensor_oracle.c raster_triangle().  The clip window
 // [wx0,wx1) x [wy0,wy1) is a sub-rectangle of the image, so clipping to it instead of to the
@@ -565,9 +504,6 @@ __device__ inline bool tri_finish(const DevParams& P, const double* X, const dou
     T.pb = div_f64(ny, P.fy);
     T.pc = (nz - T.pa * P.cx) - T.pb * P.cy;
     T.xlo = (int)xlo_d; T.xhi = (int)xhi_d; T.ylo = (int)ylo_d; T.yhi = (int)yhi_d;
-#if RBS_EDGE_FILTER
-    tri_filter(T, xlo_d, ylo_d);
-#endif
     return true;
 }
 
@@ -627,14 +563,6 @@ __device__ inline bool tri_inside_exact(const Tri& T, double px, double py)
     // all three >= 0 or all three <= 0, as min / max (E is finite: the setup rejected anything else):
     // four instructions and one branch instead of two compare chains with a branch between them.
     return ((int)(mn >= 0.0) | (int)(mx <= 0.0)) != 0;
-}
-// Depth of a covered sample; z-min into the LDS tile at `at`.
-__device__ inline void tri_depth(const Tri& T, double px, double py, unsigned* at)
-{
-    const double den = (T.pa * px + T.pb * py) + T.pc;
-    const float zf = (float)div_f64(T.nv0, den);
-    // a depth must be a positive finite float (zf > 0 && zf < inf): one class test, +denormal | +normal
-    if (__builtin_amdgcn_classf(zf, 0x180)) atomicMin(at, __float_as_uint(zf));
 }
 // Coverage test + depth for one integer pixel (px, py: its coordinates as doubles); z-min into the
 // LDS tile at `at`.
@@ -761,32 +689,6 @@ __device__ inline void raster_lane_samples(const Tri& T, int t, int wx0, int wy0
         if (slot < kBigCap) { big[slot] = t; return; }
     }
     // (one flat loop over the box's samples instead of rows x columns: fewer trips, 3 % slower)
-#if RBS_EDGE_FILTER
-    const float thr = T.thr, nthr = -T.thr;
-    float fj = 0.0f;
-    for (int row = T.ylo; row <= T.yhi; ++row, fj += 1.0f) {
-        const float r0 = fmaf(T.fA[0], fj, T.fC[0]), r1 = fmaf(T.fA[1], fj, T.fC[1]), r2 = fmaf(T.fA[2], fj, T.fC[2]);
-        unsigned* trow = tile + (row - wy0) * tw - wx0;
-        float fi = 0.0f;
-        for (int col = T.xlo; col <= T.xhi; ++col, fi += 1.0f) {
-            const float e0 = fmaf(T.fB[0], fi, r0), e1 = fmaf(T.fB[1], fi, r1), e2 = fmaf(T.fB[2], fi, r2);
-            const float mn = __builtin_fminf(__builtin_fminf(e0, e1), e2), mx = __builtin_fmaxf(__builtin_fmaxf(e0, e1), e2);
-            bool in = mn > thr || mx < nthr;                          // clearly inside (either winding)
-            const bool out = mn < nthr && mx > thr;                   // clearly outside
-            if (__builtin_expect(__ballot(!in && !out) != 0, 0)) {    // within thr of an edge (or not finite): the oracle's expression
-                if (!in && !out) {
-                    // (opaque to the optimiser: the row-invariant half of the binary64 expression must not be
-                    // hoisted into the row loop -- it is needed about once in 1e4 samples)
-                    double px = (double)col, py = (double)row;
-                    asm volatile("" : "+v"(px), "+v"(py));
-                    in = tri_inside_exact(T, px, py);
-                }
-            }
-            if (in) tri_depth(T, (double)col, (double)row, trow + col);
-        }
-    }
-#else
-#if RBS_PIN_EDGES
     // (the six edge components opaque to the optimiser, so that none of them is re-derived from the vertices inside the
     // loop: left alone the compiler re-materialises one of them per trip -- a binary64 subtraction it deems cheaper than two
     // registers; C2 / C4 +0.5-0.7 %, C1 +0.2 %, same bits)
@@ -795,12 +697,6 @@ __device__ inline void raster_lane_samples(const Tri& T, int t, int wx0, int wy0
     for (int row = U.ylo; row <= U.yhi; ++row)
         for (int col = U.xlo; col <= U.xhi; ++col)
             tri_pixel(U, col, row, tile, tw, wx0, wy0);
-#else
-    for (int row = T.ylo; row <= T.yhi; ++row)
-        for (int col = T.xlo; col <= T.xhi; ++col)
-            tri_pixel(T, col, row, tile, tw, wx0, wy0);
-#endif
-#endif
 }
 
 // One lane's triangle: setup, then its sample points.
@@ -952,9 +848,6 @@ __device__ inline void raster_window(const DevParams& P, const double* __restric
             const int ci = base + lane;
             int facing;
             bool hit;
-#ifndef RBS_NV_EARLY
-#define RBS_NV_EARLY 1   // the cluster_nv read issued with the sphere and cone reads, not behind the cull (C1 +0.4 %)
-#endif
             int nvc_early = 0;
             if (MANY) {
                 const int it = (base - cbase) >> 6;
@@ -965,9 +858,7 @@ __device__ inline void raster_window(const DevParams& P, const double* __restric
                 if (ci < c1) {
                     sph = reinterpret_cast<const floatx4*>(P.cluster_sphere)[ci];
                     cone = reinterpret_cast<const floatx4*>(P.cluster_cone)[ci];
-#if RBS_NV_EARLY
-                    nvc_early = P.cluster_nv[ci];
-#endif
+                    nvc_early = P.cluster_nv[ci];   // issued with the sphere and cone reads, not behind the cull (C1 +0.4 %)
                 }
                 facing = cullsign != 0 && ci < c1 ? cluster_facing(Rt, sph, cone) : 0;
                 hit = ci < c1 && (!cull || cluster_may_touch(P, Rt, sph, wx0, wy0, wx1, wy1)) && facing <= 0;
@@ -980,13 +871,12 @@ __device__ inline void raster_window(const DevParams& P, const double* __restric
             unsigned long long mine = __ballot(hit && (rank % (kBlock / 64)) == wave);
             taken += __popcll(mask);
             if (MANY && mine == 0) continue;   // (nine clusters in ten of a large body are culled: most steps leave this wave nothing)
-#if RBS_SHARE_VERTICES
             // Clusters all of whose triangles go to the setup -- every cluster of a body that is not
             // culled, and the clusters whose normal cone faces the camera (4/5 of a closed body's
             // surviving triangles) -- are set up with their vertices shared, straight from the
             // cluster (no pre-test, no ring); the others (silhouette clusters, clusters with more
             // than 64 unique vertices) take the per-triangle route below.
-            const int nvc = RBS_NV_EARLY && !MANY ? nvc_early : ci < c1 ? P.cluster_nv[ci] : 0;
+            const int nvc = !MANY ? nvc_early : ci < c1 ? P.cluster_nv[ci] : 0;
             unsigned long long whole = mine & __ballot(hit && nvc > 0 && (cullsign == 0 || facing < 0));
             mine &= ~whole;
             while (whole) {
@@ -997,7 +887,6 @@ __device__ inline void raster_window(const DevParams& P, const double* __restric
                                       tile, tw, big, nbig RBS_TICK_ARG);
                 __builtin_amdgcn_wave_barrier(); RBS_TICK(12); RBS_COUNT(18, 1); RBS_COUNT(19, 1);
             }
-#endif
             if (cullsign == 0) {   // nothing to pre-test: the clusters' lanes go straight to the setup
                 while (mine) {
                     const int bit = __builtin_ctzll(mine);
@@ -1134,15 +1023,10 @@ struct MathTabs { const double* erfc; const double* logt; const double* ages; };
 #endif
 constexpr int kLdsAges = RBS_EXACT_LDS_AGES;
 
-#ifdef RBS_NOINLINE_EVAL
-#define RBS_EVAL_INLINE __attribute__((noinline))
-#else
-#define RBS_EVAL_INLINE inline
-#endif
 // EXACT (stamped planes): `prior` is the pixel's stored VALUE and `age` the frames since its update -- the table entry of that
 // age is requested WITH the frame terms, and the prior is formed once both have arrived (exact_prior's operations).
 template <bool EXACT = false>
-__device__ RBS_EVAL_INLINE double pixel_loglik(const DevParams& P, const MathTabs& M, int gi, float r, float prior, float& posterior, int age = 0)
+__device__ inline double pixel_loglik(const DevParams& P, const MathTabs& M, int gi, float r, float prior, float& posterior, int age = 0)
 {
     // the per-frame terms of this pixel, observation included: one 32-byte entry, one memory round trip
     typedef double doublex2 __attribute__((ext_vector_type(2)));
@@ -1188,21 +1072,11 @@ __device__ RBS_EVAL_INLINE double pixel_loglik(const DevParams& P, const MathTab
 // 3.0e-6 max, bias +3e-8, posterior 6.6e-7 max (tests/pixel_f32_twin.py, the numpy float32 twin of these functions, over 4e5 pixels; the device
 // is held to twice the twin's worst and mean pixel by pixel: tests/test_gpu_pixel_math.py); the particle's sum is accumulated
 // in binary64.  tests/: <= 1e-5 relative against the reference-semantics (LAZY) oracle, the north_star tolerance.
-#ifndef RBS_F32_EXP
-#define RBS_F32_EXP 0
-#endif
-#ifndef RBS_F32_LOG
-#define RBS_F32_LOG 0
-#endif
-#ifndef RBS_F32_DIV
-#define RBS_F32_DIV 0
-#endif
-__device__ inline float fast_exp(float x) { return RBS_F32_EXP ? expf(x) : __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
-__device__ inline float fast_log(float x) { return RBS_F32_LOG ? logf(x) : 0.6931471805599453f * __builtin_amdgcn_logf(x); }
+__device__ inline float fast_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
+__device__ inline float fast_log(float x) { return 0.6931471805599453f * __builtin_amdgcn_logf(x); }
 // hardware reciprocal (1 ulp) + one Newton step: half an ulp for operands in the normal range
 __device__ inline float fast_rcp(float x)
 {
-    if (RBS_F32_DIV) return 1.0f / x;
     const float r = __builtin_amdgcn_rcpf(x);
     return fmaf(r, fmaf(-x, r, 1.0f), r);
 }
@@ -1334,8 +1208,7 @@ __device__ inline double raster_eval_tile(const DevParams& P, int particle, Rect
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     int* q = m.evalq + wave * kQPlanes * kEvalQueue;   // planes: pixel index, depth bits, prior, observation
     int* aq = EXACT ? m.ageq + wave * kEvalQueue : nullptr;   // stamped planes: plane 2 holds the stored VALUE, this ring its age
-    const MathTabs mt = RBS_MATH_LDS ? MathTabs{m.mtab, m.mtab + rbsm::kErfcIntervals * rbsm::kErfcCoefs, m.agetab}
-                                     : MathTabs{rbsm::kErfcTab, rbsm::kLogTab, m.agetab};
+    const MathTabs mt = {m.mtab, m.mtab + rbsm::kErfcIntervals * rbsm::kErfcCoefs, m.agetab};
     int qh = 0, qn = 0;                                // ring: head, count (wave-uniform)
     // evaluate the 64 (or, at the end, `cnt_`) oldest queued pixels
 #define RBS_EVAL_BATCH(cnt_)                                                                            \
@@ -1588,11 +1461,7 @@ __device__ inline void copy_band(const DevParams& P, int particle, int band, Rec
                 const int idx = base + k * kBlock;
                 const int col = c4 << 2;
                 ok[k] = idx < n4 && !raster_writes(P, particle, make_int4(r.x0, r.y0, r.x1, r.y1), row, col);
-#if RBS_NT
                 if (ok[k]) v[k] = __builtin_nontemporal_load(&s4[idx]);
-#else
-                if (ok[k]) v[k] = s4[idx];
-#endif
                 c4 += rstep; row += qstep;
                 if (c4 >= W4) { c4 -= W4; ++row; }
             }
@@ -1604,11 +1473,7 @@ __device__ inline void copy_band(const DevParams& P, int particle, int band, Rec
                 w.y = occ_step(alpha, beta, v[k].y, bg_new);
                 w.z = occ_step(alpha, beta, v[k].z, bg_new);
                 w.w = occ_step(alpha, beta, v[k].w, bg_new);
-#if RBS_NT
                 __builtin_nontemporal_store(w, &d4[base + k * kBlock]);
-#else
-                d4[base + k * kBlock] = w;
-#endif
             }
         }
     } else {
@@ -2007,15 +1872,15 @@ __device__ __forceinline__ void raster_kernel_body(const DevParams& P)
 {
     static_assert(!FCOPY || (UPDATE && !SLAB && !MANY && !STP && !EXACT), "the fused copy serves windowed whole planes, scalar background");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    Smem m = carve(smem, P.tile_px, PREC == 0 && RBS_MATH_LDS);
+    Smem m = carve(smem, P.tile_px, PREC == 0);
     if (EXACT) {
-        m.ageq = reinterpret_cast<int*>(smem + smem_bytes(P.tile_px, PREC == 0 && RBS_MATH_LDS, MANY));
+        m.ageq = reinterpret_cast<int*>(smem + smem_bytes(P.tile_px, PREC == 0, MANY));
         m.agetab = reinterpret_cast<double*>(m.ageq + (kBlock / 64) * kEvalQueue);
         for (int i = threadIdx.x; i < 2 * min(kLdsAges, P.age_max + 1); i += kBlock) m.agetab[i] = P.ptab[i];
     }
     const int total = P.ctr_this[0];
     if (blockIdx.x == 0 && threadIdx.x == 0) { P.ctr_next[0] = 0; P.ctr_next[1] = 0; }
-    if (PREC == 0 && RBS_MATH_LDS) {   // once per persistent block (the first item's tile clear ends in a barrier)
+    if (PREC == 0) {   // once per persistent block (the first item's tile clear ends in a barrier)
         constexpr int ne = rbsm::kErfcIntervals * rbsm::kErfcCoefs, nl = rbsm::kLogIntervals * 2;
         for (int i = threadIdx.x; i < ne; i += kBlock) m.mtab[i] = rbsm::kErfcTab[i];
         for (int i = threadIdx.x; i < nl; i += kBlock) m.mtab[ne + i] = rbsm::kLogTab[i];
@@ -2123,22 +1988,18 @@ void rbs_raster_kernel_f32(const DevParams P)
 }
 // The same budget for the binary64 likelihood: on rbs_math.h's functions it fits 160 registers
 // (a few kernel-lifetime dwords in scratch at most), so the windowed copy kernel runs beside it as well (C1 9.27 -> 9.72 M/s, C2 3.24
-// -> 3.45; ocml's exp / erf / log needed 168 + 72 spilled).  RBS_RASTER_VGPRS_F64=0: no budget.
+// -> 3.45; ocml's exp / erf / log needed 168 + 72 spilled).
 #ifndef RBS_RASTER_VGPRS_F64
 #define RBS_RASTER_VGPRS_F64 80
 #endif
-#if RBS_RASTER_VGPRS_F64
 #define RBS_F64_BUDGET __attribute__((amdgpu_num_vgpr(RBS_RASTER_VGPRS_F64)))
-#else
-#define RBS_F64_BUDGET
-#endif
 template <bool UPDATE, bool SLAB>
 __global__ __launch_bounds__(kBlock, RBS_RASTER_MINWAVES_F64) RBS_F64_BUDGET void rbs_raster_kernel_f64(const DevParams P)
 {
     raster_kernel_body<UPDATE, 0, SLAB>(P);
 }
 // ... an object model of ONE body (round 6, VERDICT r5 #7: the bounded experiment -- body loop, body masks, groups and the per-body
-// tables' run-time indexing gone from the kernel).  Measured on C1 (tools/dbg/ab_one_body.sh, same box, two rounds each): spilled
+// tables' run-time indexing gone from the kernel).  Measured on C1 (same box, two rounds each): spilled
 // scalar registers 59 -> 48, kernel 0.1662 -> 0.1654 ms; with the registers that frees spent on the pixel pass' loads in flight
 // (RBS_SCAN_UNROLL_ONE): three quads 0.1640 (44 spilled SGPRs, nothing in scratch), four 0.1647.  The target was 0.158: the kernel's
 // waiting is not the scalar spills'.  Kept at three quads for its 1.3 % (parity suite green on it); the C1 kernel is finished here.
@@ -2207,9 +2068,6 @@ __global__ __launch_bounds__(kBlock, RBS_RASTER_MINWAVES_F64) RBS_F64_BUDGET voi
 //                      occlusion process, compaction of covered + observed pixels, the binary64 likelihood 64 pixels
 //                      at a time, block reduce, plane write.  15 KB of LDS and a small register budget: 5-6 waves per
 //                      SIMD hide the 32-byte gather and the exp / erfc / log chains that three waves do not.
-#ifndef RBS_SPLIT_DEFAULT
-#define RBS_SPLIT_DEFAULT 0         // what a handle does when RBS_SPLIT is not in the environment
-#endif
 // Measured (round 5, profiles/r05_split_*): four geometry blocks per CU need a 7 680-px tile and a 120-register budget that
 // spills 55 registers -- 126 us; three blocks per CU at the one-kernel launch's own tile and budget: 105 us.  The tile of the
 // one-kernel launch also makes the two launches interchangeable call by call: the same work items, the same summation order,
@@ -2505,9 +2363,6 @@ __global__ __launch_bounds__(64) void rbs_wide_window_kernel(const DevParams P, 
 // could not: C2 3.33 -> 3.61 M/s, C3 slice 12.0 -> 12.8 M/s, C1 step 0.2055 -> 0.2015 ms).
 #ifndef RBS_WIN_UNROLL
 #define RBS_WIN_UNROLL 2
-#endif
-#ifndef RBS_COPY_STRIPS
-#define RBS_COPY_STRIPS 1      // (0: one body takes the walk-everything form as well -- A/B)
 #endif
 constexpr int kWinUnroll = RBS_WIN_UNROLL;
 // STRIPS: one rectangle per particle (P.groups == nullptr) -- only the cells outside it are enumerated; otherwise the

@@ -31,7 +31,7 @@ namespace probe {
 
 constexpr int64_t kProbeMax = int64_t(1) << 26;   // elements per call (the largest buffer, [n][4] doubles, is then 2 GB)
 constexpr int kProbeTabErfc = rbsm::kErfcIntervals * rbsm::kErfcCoefs, kProbeTabLog = rbsm::kLogIntervals * 2;
-static_assert(!RBS_MATH_LDS || kMathTabDoubles == kProbeTabErfc + kProbeTabLog, "the probes' LDS copy is the raster kernel's");
+static_assert(kMathTabDoubles == kProbeTabErfc + kProbeTabLog, "the probes' LDS copy is the raster kernel's");
 
 __device__ inline size_t probe_index() { return (size_t)blockIdx.x * blockDim.x + threadIdx.x; }
 
@@ -91,7 +91,7 @@ __global__ void __launch_bounds__(kBlock) pixel_f64_kernel(const DevParams P, co
                                                            double* __restrict__ term, float* __restrict__ post, size_t n)
 {
     __shared__ alignas(16) double tab[kProbeTabErfc + kProbeTabLog];
-    const MathTabs M = probe_tabs<RBS_MATH_LDS != 0>(tab);
+    const MathTabs M = probe_tabs<true>(tab);
     const size_t i = probe_index();
     if (i < n) {
         float q;
