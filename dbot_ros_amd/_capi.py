@@ -51,7 +51,9 @@ EXPORTS = (
     "rbs_find_stage_ms", "rbs_find_last_error",
     "rbs_find_default_foreground", "rbs_find_set_foreground", "rbs_find_get_plane", "rbs_find_get_seed_frame",
     "rbs_find_default_refinement", "rbs_find_set_refinement", "rbs_find_get_covariance", "rbs_find_get_perturbations",
+    "rbs_assess_default_params", "rbs_assess_poses", "rbs_assess_verdict", "rbs_assess_get_plane", "rbs_assess_kernel_ms",
 )
+RBS_ASSESS_OUT_OF_VIEW, RBS_ASSESS_OCCLUDED, RBS_ASSESS_SUPPORTED, RBS_ASSESS_LOST = range(4)
 RBS_FIND_SEEDS, RBS_FIND_COARSE, RBS_FIND_CANDIDATES, RBS_FIND_SURVIVORS, RBS_FIND_CHILDREN, RBS_FIND_RESULT = range(6)
 
 
@@ -121,6 +123,28 @@ class RbsFindRefinement(C.Structure):
         ("mix", C.c_double),
         ("shrink", C.c_double),
         ("jitter", C.c_double),
+    ]
+
+
+class RbsAssessParams(C.Structure):
+    _fields_ = [
+        ("sigmas", C.c_double),
+        ("min_support_fraction", C.c_double),
+        ("min_visible_fraction", C.c_double),
+        ("min_pixels", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
+class RbsAssessBody(C.Structure):
+    _fields_ = [
+        ("rendered", C.c_int32),
+        ("valid", C.c_int32),
+        ("support", C.c_int32),
+        ("in_front", C.c_int32),
+        ("behind", C.c_int32),
+        ("verdict", C.c_int32),
+        ("reserved", C.c_int32 * 2),
     ]
 
 
@@ -348,5 +372,15 @@ def load():
     lib.rbs_find_get_perturbations.argtypes = [H, C.c_int32, dp, lp]
     lib.rbs_find_last_error.restype = C.c_char_p
     lib.rbs_find_last_error.argtypes = [H]
+    lib.rbs_assess_default_params.restype = None
+    lib.rbs_assess_default_params.argtypes = [C.POINTER(RbsAssessParams)]
+    lib.rbs_assess_poses.restype = C.c_int32
+    lib.rbs_assess_poses.argtypes = [H, C.POINTER(RbsAssessParams), fp, dp, C.c_int32, C.POINTER(RbsAssessBody)]
+    lib.rbs_assess_verdict.restype = C.c_int32
+    lib.rbs_assess_verdict.argtypes = [C.POINTER(RbsAssessParams), C.POINTER(RbsAssessBody), ip]
+    lib.rbs_assess_get_plane.restype = C.c_int32
+    lib.rbs_assess_get_plane.argtypes = [H, C.c_int32, C.c_int32, fp]
+    lib.rbs_assess_kernel_ms.restype = C.c_int32
+    lib.rbs_assess_kernel_ms.argtypes = [H, fp]
     _lib = lib
     return lib

@@ -1,0 +1,332 @@
+// rbsensor_assess.hip -- poses judged against one depth frame (rbs_assess_*, include/rbsensor_mi355x.h; the rule:
+// DESIGN.md Appendix J).  Included at the end of rbsensor_capi.hip: it uses the handle, its observation and the
+// rasterizer of rbsensor_kernels.hip.
+//
+// Per call, on the sensor's stream:
+//   rbs_assess_render_kernel  one block row per (pose, body): the body's own screen rectangle cut into 64 x 64 tiles
+//                             dealt to the row's blocks; every tile goes through raster_window with the body's bit as
+//                             the body mask, culled as rbs_render_kernel's (the minimum over the bodies is bit-identical
+//                             to rbs_render_depth).  Plane (k, b) is valid inside rect (k, b) only.
+//   rbs_assess_count_kernel   a fixed grid per pose over the union of its bodies' rectangles: owner and class per pixel,
+//                             integer counts in LDS, one integer global add per block and counter.
+// Integer sums do not depend on their order: the same inputs give the same counts, run after run.  The verdict is
+// taken on the host from the counts (assess::verdict_of, also rbs_assess_verdict).
+namespace rbs {
+
+constexpr int kAssessMaxPlanes = 64;      // n x n_objects of one call
+constexpr int kAssessRenderSplit = 32;    // blocks per (pose, body) (tiles beyond it: strided)
+constexpr int kAssessCountBlocks = 32;    // blocks per pose of the count kernel
+constexpr int kAssessTileW = 64, kAssessTilePx = 4096;
+constexpr int kAssessFields = 8;          // int32 per record (rbs_assess_body)
+
+__global__ __launch_bounds__(kBlock) void rbs_assess_render_kernel(const DevParams P, float* __restrict__ planes, int4* __restrict__ rects)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const Smem m = carve(smem, P.tile_px, false);
+    const int kb = blockIdx.x;                // (pose, body)
+    const int k = kb / P.n_bodies, b = kb - k * P.n_bodies;
+    const double* pose = P.poses + (size_t)k * 12 * P.n_bodies;
+    const Rect r = bodies_rect(P, pose, b, b + 1);
+    if (blockIdx.y == 0 && threadIdx.x == 0) rects[kb] = make_int4(r.x0, r.y0, r.x1, r.y1);
+    if (r.x1 <= r.x0) return;
+    const TileGrid tg = tile_grid(r.x1 - r.x0, r.y1 - r.y0, P.tile_w, min(P.tile_w * P.tile_h, P.tile_px));
+    const int nx = (r.x1 - r.x0 + tg.tw - 1) / tg.tw, ny = (r.y1 - r.y0 + tg.th - 1) / tg.th;
+    float* out = planes + (size_t)kb * P.npx;
+    for (int t = blockIdx.y; t < nx * ny; t += gridDim.y) {
+        const int ty = t / nx;
+        const int wx0 = r.x0 + (t - ty * nx) * tg.tw, wy0 = r.y0 + ty * tg.th;
+        const int wx1 = min(r.x1, wx0 + tg.tw), wy1 = min(r.y1, wy0 + tg.th);
+        const int tw = wx1 - wx0, npx = tw * (wy1 - wy0);
+        raster_window(P, pose, wx0, wy0, wx1, wy1, true, m.tile, m.big, m.nbig,
+                      m.evalq + (threadIdx.x >> 6) * kQPlanes * kEvalQueue, 1u << b);
+        for (int p = threadIdx.x; p < npx; p += kBlock) {
+            const int lr = p / tw;
+            out[(size_t)(wy0 + lr) * P.cols + wx0 + (p - lr * tw)] = __uint_as_float(m.tile[p]);
+        }
+        __syncthreads();
+    }
+}
+
+struct AssessArgs {
+    const float* planes;      // [n x B][npx], plane (k, b) valid inside rects[k B + b]
+    const int4* rects;        // [n x B]
+    const float* frame;
+    int cols, npx, B;
+    double sigmas, ms, sf;    // tau = sigmas (ms + sf d d)
+    int* rec;                 // [n x B][kAssessFields], zeroed: rendered, valid, support, in_front, behind
+};
+
+// Owner and class of every pixel of pose blockIdx.y's rectangle (the union of its bodies').
+__global__ __launch_bounds__(256) void rbs_assess_count_kernel(const AssessArgs A)
+{
+    __shared__ int s_cnt[kMaxBodies * 5];
+    __shared__ int4 s_rect[kMaxBodies];
+    const int tid = threadIdx.x, k = blockIdx.y, B = A.B;
+    for (int e = tid; e < B * 5; e += 256) s_cnt[e] = 0;
+    if (tid < B) s_rect[tid] = A.rects[k * B + tid];
+    __syncthreads();
+    int x0 = A.cols, y0 = A.npx, x1 = 0, y1 = 0;
+    for (int b = 0; b < B; ++b) {
+        const int4 r = s_rect[b];
+        if (r.z <= r.x) continue;
+        x0 = min(x0, r.x); y0 = min(y0, r.y); x1 = max(x1, r.z); y1 = max(y1, r.w);
+    }
+    if (x1 > x0) {
+        const int w = x1 - x0, total = w * (y1 - y0);
+        const float* planes = A.planes + (size_t)k * B * A.npx;
+        for (int p = blockIdx.x * 256 + tid; p < total; p += gridDim.x * 256) {
+            const int ly = p / w, x = x0 + (p - ly * w), y = y0 + ly;
+            const int i = y * A.cols + x;
+            float best = INFINITY;
+            int owner = -1;
+            for (int b = 0; b < B; ++b) {       // ascending: a tie stays with the lowest body
+                const int4 r = s_rect[b];
+                if (x < r.x || x >= r.z || y < r.y || y >= r.w) continue;
+                const float d = planes[(size_t)b * A.npx + i];
+                if (d < best) { best = d; owner = b; }
+            }
+            if (owner < 0) continue;
+            const float yv = A.frame[i];
+            int* c = s_cnt + owner * 5;
+            atomicAdd(c + 0, 1);
+            if (!(fabsf(yv) < INFINITY)) continue;   // no reading (NaN fails the comparison too)
+            const double d = (double)best;
+            const double r = (double)yv - d;
+            const double tau = A.sigmas * (A.ms + A.sf * (d * d));
+            atomicAdd(c + 1, 1);
+            atomicAdd(c + (r < -tau ? 3 : r > tau ? 4 : 2), 1);
+        }
+    }
+    __syncthreads();
+    for (int e = tid; e < B * 5; e += 256) {
+        const int v = s_cnt[e];
+        if (v) atomicAdd(A.rec + (size_t)(k * B + e / 5) * kAssessFields + e % 5, v);
+    }
+}
+
+}  // namespace rbs
+
+static_assert(sizeof(rbs_assess_body) == 32 && sizeof(rbs_assess_body) == sizeof(int32_t) * rbs::kAssessFields &&
+                  offsetof(rbs_assess_body, verdict) == 20,
+              "rbs_assess_body layout is mirrored by dbot_ros_amd/_capi.py, the count kernel and tests/test_assess_cpu.py");
+static_assert(sizeof(rbs_assess_params) == 32, "rbs_assess_params layout is mirrored by dbot_ros_amd/_capi.py");
+
+// What a sensor owns once it has assessed: allocated at first use, grow-only, freed by rbs_destroy.
+struct rbs_assess_state {
+    int cap = 0;                    // planes the buffers hold
+    float* d_planes = nullptr;      // [cap][npx]
+    int4* d_rects = nullptr;        // [cap]
+    int* d_rec = nullptr;           // [cap][8]
+    double* d_poses = nullptr;      // [cap][12]
+    float* d_frame = nullptr;       // [npx] a caller's frame
+    unsigned char* h_pin = nullptr; // pinned: frame [npx] floats | poses [kAssessMaxPlanes][12] | records [kAssessMaxPlanes]
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    float ms[2] = {0.f, 0.f};
+    int n = 0;                      // poses of the last call (0: none yet)
+};
+
+namespace {
+namespace assess {
+
+const char* check_params(const rbs_assess_params* p)
+{
+    if (!(p->sigmas > 0.0) || !std::isfinite(p->sigmas)) return "assess: sigmas must be finite and > 0";
+    if (!(p->min_support_fraction >= 0.0 && p->min_support_fraction <= 1.0)) return "assess: min_support_fraction must lie in [0, 1]";
+    if (!(p->min_visible_fraction >= 0.0 && p->min_visible_fraction <= 1.0)) return "assess: min_visible_fraction must lie in [0, 1]";
+    if (p->min_pixels < 1) return "assess: min_pixels must be >= 1";
+    return nullptr;
+}
+
+int32_t verdict_of(const rbs_assess_params& p, const rbs_assess_body& c)
+{
+    const int32_t u = c.support + c.behind;
+    if (c.rendered < p.min_pixels) return RBS_ASSESS_OUT_OF_VIEW;
+    if ((double)u < p.min_visible_fraction * (double)c.rendered) return RBS_ASSESS_OCCLUDED;
+    if ((double)c.support >= p.min_support_fraction * (double)u) return RBS_ASSESS_SUPPORTED;
+    return RBS_ASSESS_LOST;
+}
+
+size_t pin_poses_off(const rbs_handle* h) { return (sizeof(float) * (size_t)h->npx + 15) & ~(size_t)15; }
+size_t pin_rec_off(const rbs_handle* h) { return pin_poses_off(h) + sizeof(double) * 12 * rbs::kAssessMaxPlanes; }
+
+int32_t ensure(rbs_handle* h, int planes)
+{
+    if (!h->assess) {
+        h->assess = new (std::nothrow) rbs_assess_state;
+        if (!h->assess) return fail(h, RBS_ERR_OUT_OF_MEMORY, "assess: out of host memory");
+    }
+    rbs_assess_state* a = h->assess;
+    if (!a->h_pin) {
+        RBS_HIP(h, hipHostMalloc(&a->h_pin, pin_rec_off(h) + sizeof(rbs_assess_body) * rbs::kAssessMaxPlanes, hipHostMallocDefault));
+        RBS_HIP(h, hipMalloc(&a->d_frame, sizeof(float) * (size_t)h->npx));
+        for (hipEvent_t& e : a->ev) RBS_HIP(h, hipEventCreate(&e));
+    }
+    if (planes > a->cap) {   // (grow-only; the stream is idle of this state's readers: every call ends synchronised)
+        RBS_HIP(h, hipStreamSynchronize(h->stream));
+        (void)hipFree(a->d_planes); (void)hipFree(a->d_rects); (void)hipFree(a->d_rec); (void)hipFree(a->d_poses);
+        a->d_planes = nullptr; a->d_rects = nullptr; a->d_rec = nullptr; a->d_poses = nullptr;
+        a->cap = 0;
+        a->n = 0;
+        RBS_HIP(h, hipMalloc(&a->d_planes, sizeof(float) * (size_t)planes * h->npx));
+        RBS_HIP(h, hipMalloc(&a->d_rects, sizeof(int4) * (size_t)planes));
+        RBS_HIP(h, hipMalloc(&a->d_rec, sizeof(int) * rbs::kAssessFields * (size_t)planes));
+        RBS_HIP(h, hipMalloc(&a->d_poses, sizeof(double) * 12 * (size_t)planes));
+        a->cap = planes;
+    }
+    return RBS_OK;
+}
+
+}  // namespace assess
+
+// rbs_create: the render kernel's dynamic LDS, beside rbs_render_kernel's.
+int32_t assess_configure(rbs_handle* h)
+{
+    RBS_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&rbs::rbs_assess_render_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)rbs::smem_bytes(rbs::kAssessTilePx, false)));
+    return RBS_OK;
+}
+
+// rbs_destroy (the handle's device is current and its streams are idle).
+void assess_release(rbs_handle* h)
+{
+    rbs_assess_state* a = h->assess;
+    if (!a) return;
+    (void)hipFree(a->d_planes);
+    (void)hipFree(a->d_rects);
+    (void)hipFree(a->d_rec);
+    (void)hipFree(a->d_poses);
+    (void)hipFree(a->d_frame);
+    if (a->h_pin) (void)hipHostFree(a->h_pin);
+    for (hipEvent_t e : a->ev)
+        if (e) (void)hipEventDestroy(e);
+    delete a;
+    h->assess = nullptr;
+}
+
+}  // namespace
+
+extern "C" {
+
+void rbs_assess_default_params(rbs_assess_params* p)
+{
+    if (!p) return;
+    p->sigmas = 3.0;
+    p->min_support_fraction = 0.5;
+    p->min_visible_fraction = 0.25;
+    p->min_pixels = 16;
+    p->reserved = 0;
+}
+
+int32_t rbs_assess_verdict(const rbs_assess_params* params, const rbs_assess_body* body, int32_t* verdict)
+{
+    if (!body || !verdict) return RBS_ERR_INVALID_ARGUMENT;
+    rbs_assess_params p;
+    if (params) p = *params; else rbs_assess_default_params(&p);
+    if (assess::check_params(&p)) return RBS_ERR_INVALID_ARGUMENT;
+    *verdict = assess::verdict_of(p, *body);
+    return RBS_OK;
+}
+
+int32_t rbs_assess_poses(rbs_handle* h, const rbs_assess_params* params, const float* frame, const double* poses, int32_t n,
+                         rbs_assess_body* out)
+{
+    if (!h) return RBS_ERR_INVALID_ARGUMENT;
+    if (!poses || !out) return fail(h, RBS_ERR_INVALID_ARGUMENT, "assess_poses: null pointer");
+    if (n < 1) return fail(h, RBS_ERR_INVALID_ARGUMENT, "assess_poses: n < 1");
+    rbs_assess_params p;
+    if (params) p = *params; else rbs_assess_default_params(&p);
+    if (const char* bad = assess::check_params(&p)) return fail(h, RBS_ERR_INVALID_ARGUMENT, bad);
+    if (!h->shards.empty() || h->group || h->peer_world > 1)
+        return fail(h, RBS_ERR_UNSUPPORTED, "assess_poses: single-device handles only");
+    const int B = h->n_bodies;
+    if ((long)n * B > rbs::kAssessMaxPlanes)
+        return fail(h, RBS_ERR_INVALID_ARGUMENT, fmt("assess_poses: n x n_objects = %ld exceeds %d", (long)n * B, rbs::kAssessMaxPlanes));
+    const int planes = n * B;
+    for (size_t i = 0; i < (size_t)planes * 12; ++i)
+        if (!std::isfinite(poses[i])) return fail(h, RBS_ERR_INVALID_ARGUMENT, fmt("assess_poses: pose entry %zu is not finite", i));
+    RBS_REFUSE_POISONED(h);
+    RBS_HIP(h, hipSetDevice(h->device));
+    if (int32_t rc = assess::ensure(h, planes)) return rc;
+    rbs_assess_state* a = h->assess;
+    hipStream_t s = h->stream;
+    const size_t npx = (size_t)h->npx;
+    const float* d_frame;
+    if (frame) {
+        std::memcpy(a->h_pin, frame, sizeof(float) * npx);
+        RBS_HIP(h, hipMemcpyAsync(a->d_frame, a->h_pin, sizeof(float) * npx, hipMemcpyHostToDevice, s));
+        d_frame = a->d_frame;
+    } else {   // the sensor's current observation, as rbs_get_observation reads it (the kernels below run behind the sensor's queued work)
+        if (int32_t rc = make_current(h, s)) return rc;
+        d_frame = obs_frame(h);
+    }
+    double* h_poses = reinterpret_cast<double*>(a->h_pin + assess::pin_poses_off(h));
+    rbs_assess_body* h_rec = reinterpret_cast<rbs_assess_body*>(a->h_pin + assess::pin_rec_off(h));
+    std::memcpy(h_poses, poses, sizeof(double) * 12 * (size_t)planes);
+    RBS_HIP(h, hipMemcpyAsync(a->d_poses, h_poses, sizeof(double) * 12 * (size_t)planes, hipMemcpyHostToDevice, s));
+    RBS_HIP(h, hipMemsetAsync(a->d_rec, 0, sizeof(int) * rbs::kAssessFields * (size_t)planes, s));
+    DevParams P = h->base;
+    P.poses = a->d_poses;
+    P.n = n;
+    P.tile_w = rbs::kAssessTileW;
+    P.tile_px = rbs::kAssessTilePx;
+    P.tile_h = rbs::kAssessTilePx / rbs::kAssessTileW;
+    a->n = 0;
+    RBS_HIP(h, hipEventRecord(a->ev[0], s));
+    hipLaunchKernelGGL(rbs::rbs_assess_render_kernel, dim3((unsigned)planes, rbs::kAssessRenderSplit), dim3(rbs::kBlock),
+                       rbs::smem_bytes(rbs::kAssessTilePx, false), s, P, a->d_planes, a->d_rects);
+    RBS_HIP(h, hipGetLastError());
+    RBS_HIP(h, hipEventRecord(a->ev[1], s));
+    rbs::AssessArgs A{};
+    A.planes = a->d_planes;
+    A.rects = a->d_rects;
+    A.frame = d_frame;
+    A.cols = h->cols;
+    A.npx = h->npx;
+    A.B = B;
+    A.sigmas = p.sigmas;
+    A.ms = h->base.ms;
+    A.sf = h->base.sf;
+    A.rec = a->d_rec;
+    hipLaunchKernelGGL(rbs::rbs_assess_count_kernel, dim3(rbs::kAssessCountBlocks, (unsigned)n), dim3(256), 0, s, A);
+    RBS_HIP(h, hipGetLastError());
+    RBS_HIP(h, hipEventRecord(a->ev[2], s));
+    RBS_HIP(h, hipMemcpyAsync(h_rec, a->d_rec, sizeof(rbs_assess_body) * (size_t)planes, hipMemcpyDeviceToHost, s));
+    RBS_HIP(h, hipStreamSynchronize(s));
+    for (int k = 0; k < 2; ++k) RBS_HIP(h, hipEventElapsedTime(&a->ms[k], a->ev[k], a->ev[k + 1]));
+    for (int i = 0; i < planes; ++i) {
+        out[i] = h_rec[i];
+        out[i].verdict = assess::verdict_of(p, out[i]);
+        out[i].reserved[0] = out[i].reserved[1] = 0;
+    }
+    a->n = n;
+    return RBS_OK;
+}
+
+int32_t rbs_assess_get_plane(rbs_handle* h, int32_t k, int32_t b, float* out)
+{
+    if (!h) return RBS_ERR_INVALID_ARGUMENT;
+    const rbs_assess_state* a = h->assess;
+    if (!out || !a || a->n < 1 || k < 0 || k >= a->n || b < 0 || b >= h->n_bodies)
+        return fail(h, RBS_ERR_INVALID_ARGUMENT, "assess_get_plane: no poses assessed yet, a bad index or a null pointer");
+    RBS_HIP(h, hipSetDevice(h->device));
+    RBS_HIP(h, hipStreamSynchronize(h->stream));
+    const size_t kb = (size_t)k * h->n_bodies + b;
+    int4 r;
+    RBS_HIP(h, hipMemcpy(&r, a->d_rects + kb, sizeof(int4), hipMemcpyDeviceToHost));
+    RBS_HIP(h, hipMemcpy(out, a->d_planes + kb * h->npx, sizeof(float) * h->npx, hipMemcpyDeviceToHost));
+    for (int row = 0; row < h->rows; ++row)   // the plane is valid inside its rectangle only
+        for (int col = 0; col < h->cols; ++col)
+            if (!(col >= r.x && col < r.z && row >= r.y && row < r.w)) out[(size_t)row * h->cols + col] = INFINITY;
+    return RBS_OK;
+}
+
+int32_t rbs_assess_kernel_ms(rbs_handle* h, float* out2)
+{
+    if (!h) return RBS_ERR_INVALID_ARGUMENT;
+    if (!out2 || !h->assess || h->assess->n < 1) return fail(h, RBS_ERR_INVALID_ARGUMENT, "assess_kernel_ms: no poses assessed yet or a null pointer");
+    out2[0] = h->assess->ms[0];
+    out2[1] = h->assess->ms[1];
+    return RBS_OK;
+}
+
+}  // extern "C"

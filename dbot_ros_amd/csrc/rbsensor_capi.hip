@@ -270,6 +270,8 @@ struct rbs_handle {
     std::vector<int32_t> cfg_vertex_counts, cfg_triangles, cfg_triangle_counts;
     int occ_slots = 0;          // occlusion slots allocated: 0 = max_particles; a finder's scoring handle keeps slot 0 only
                                 // (it is only ever called with update = 0 and every index 0)
+    // ---- the pose assessor (rbsensor_assess.hip): its planes, records and staging, allocated by the first rbs_assess_poses
+    struct rbs_assess_state* assess = nullptr;
 };
 
 // RCCL, bound at run time (dlopen): a single-device handle never needs it, and a process that
@@ -316,6 +318,10 @@ int32_t fail(rbs_handle* h, int32_t code, const std::string& msg)
     h->err = msg;
     return code;
 }
+
+// rbsensor_assess.hip: its render kernel's launch attribute (create_impl), its buffers (release)
+int32_t assess_configure(rbs_handle* h);
+void assess_release(rbs_handle* h);
 
 // One host array to a new device allocation of at least min_count elements.
 template <class T>
@@ -1662,6 +1668,7 @@ void release(rbs_handle* h)
     (void)hipFree(h->d_tri_plane);
     (void)hipFree(h->d_vtx);
     (void)hipFree(h->d_render);
+    assess_release(h);
     if (h->up_stream) (void)hipStreamSynchronize(h->up_stream);
     for (int k = 0; k < 2; ++k) {
         if (h->h_frames[k]) (void)hipHostFree(h->h_frames[k]);
@@ -2013,6 +2020,7 @@ int32_t create_impl(const rbs_config* cfg, rbs_handle* h)
     }
     RBS_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&rbs::rbs_render_kernel),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)rbs::smem_bytes(rbs::kTilePxBig, false)));
+    if (int32_t rc = assess_configure(h)) return rc;
 
     {   // per-item partial sums: sized for the default tiling so no call ever allocates
         const size_t gmul = h->d_groups[0] ? rbs::kMaxGroups : 1;   // every group of bodies tiles its own rectangle
@@ -4272,6 +4280,8 @@ int32_t rbs_tracker_get(rbs_tracker* t, double* particles, double* log_weights, 
 
 // The robust Gaussian tracker (rbs_gauss_*): its kernels and host side.
 #include "rbsensor_gauss.hip"
+// The pose assessor (rbs_assess_*): its kernels and host side.
+#include "rbsensor_assess.hip"
 #include "rbsensor_find.hip"
 
 #ifdef RBS_TEST_HOOKS   // (librbsensor_mi355x_hooks.so only) rbs_test_*: the per-pixel likelihood's inline functions, value by value (tests/test_gpu_pixel_math.py)

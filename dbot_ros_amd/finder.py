@@ -25,6 +25,8 @@ class FindResult:
     states: np.ndarray    # [K, 12] tracker states (position, rotation vector, zero velocities), caller's mesh frame
     poses: np.ndarray     # [K, 12] R row-major | t of the sensor's (centred) mesh frame
     scores: np.ndarray    # [K] log-likelihoods at the sensor's resolution
+    assessment: Optional[object] = None   # find(assess=PoseAssessor): the assess.Assessment of the K poses against the frame
+    confirmed: Optional[int] = None       # ... and the first pose whose verdict is SUPPORTED (-1: none)
 
 
 # the dominant plane of the last find (step 1b): 1 / z = a u + b v + c over the coarse pixels (u, v)
@@ -186,9 +188,11 @@ class ObjectFinder:
         if rc != 0:
             raise RbSensorError(rc, self._lib.rbs_find_last_error(self._f).decode())
 
-    def find(self, frame=None, k=None):
+    def find(self, frame=None, k=None, assess=None):
         """frame: rows*cols depth (metres, NaN = no reading) at the sensor's resolution, or None for
-        the sensor's current observation.  Returns up to k (default n_survivors) poses, best first."""
+        the sensor's current observation.  Returns up to k (default n_survivors) poses, best first.
+        assess: a PoseAssessor over the same sensor -- the returned poses are judged against the same frame
+        (FindResult.assessment) and `confirmed` names the first one that is SUPPORTED; `found` is unchanged."""
         k = int(self.params.n_survivors if k is None else k)
         poses = np.zeros((max(k, 1), 12))
         scores = np.zeros(max(k, 1))
@@ -209,7 +213,15 @@ class ObjectFinder:
             R = poses[i, :9].reshape(3, 3)
             states[i, 0:3] = poses[i, 9:12] - R @ c
             states[i, 3:6] = matrix_to_rotvec(R)
-        return FindResult(bool(found.value), states, poses, scores)
+        res = FindResult(bool(found.value), states, poses, scores)
+        if assess is not None:
+            from .assess import SUPPORTED
+            res.confirmed = -1
+            if K > 0:
+                res.assessment = assess.assess(poses[:min(K, 64)], img)
+                hits = np.nonzero(res.assessment.verdicts[:, 0] == SUPPORTED)[0]
+                res.confirmed = int(hits[0]) if hits.size else -1
+        return res
 
     def stage(self, stage, round=0):
         """One stage's exact outputs of the last find: (poses, scores, indices, info); see rbs_find_get_stage."""

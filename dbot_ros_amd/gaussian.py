@@ -114,6 +114,9 @@ class GaussianTracker:
     # -- State <-> model coordinates: ParticleTracker's rule (it reads parts, centers, params.center_object_frame)
     _to_model = ParticleTracker._to_model
     _from_model = ParticleTracker._from_model
+    # -- the last estimate judged against its frame: ParticleTracker's method (it reads moving_average, sensor, _in_flight)
+    assess = ParticleTracker.assess
+    _in_flight = 0
 
     # -- Tracker interface -------------------------------------------------------------------
     def initialize(self, initial_states, cov0=None):
@@ -129,6 +132,7 @@ class GaussianTracker:
         self.sensor._check(self._lib.rbs_gauss_initialize(self._g, d.ctypes.data_as(dp), None if c is None else c.ctypes.data_as(dp)))
         self._cov = None if c is None else c.copy()
         self.moving_average = None
+        self._in_flight = 0   # (rbs_gauss_initialize drops frames still in flight)
 
     def track(self, image):
         """One depth frame (float32 or float64, rows*cols metres, NaN = no reading) -> State.  image=None: the frame
@@ -163,6 +167,7 @@ class GaussianTracker:
             img = np.ascontiguousarray(image, dtype=np.float32).ravel()
             rc = self._lib.rbs_gauss_submit(self._g, img.ctypes.data_as(C.POINTER(C.c_float)))
         self.sensor._check(rc)   # (the library has staged the frame: the buffer is the caller's again)
+        self._in_flight += 1
 
     def result(self):
         """The moving-average estimate of the oldest submitted frame (rbs_gauss_result); covariance is updated here."""
@@ -171,6 +176,7 @@ class GaussianTracker:
         cov = np.empty((self.D, self.D))
         dp = C.POINTER(C.c_double)
         self.sensor._check(self._lib.rbs_gauss_result(self._g, out.ctypes.data_as(dp), cov.ctypes.data_as(dp)))
+        self._in_flight = max(0, self._in_flight - 1)
         return self._finish(out, cov)
 
     def _finish(self, out, cov):

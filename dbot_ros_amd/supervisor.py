@@ -1,0 +1,80 @@
+"""Track supervisor: the loop the reference leaves to a person.  Its controller shows a found pose in rviz and waits
+for a click before it starts the tracker (R:source/dbot_ros/tracker/object_tracker_controller_service_node.cpp:180-195),
+and nothing tells a running tracker that its object is gone.  TrackSupervisor judges every estimate against its frame
+(dbot_ros_amd/assess.py), counts the frames that read LOST, and -- given a finder -- re-initialises the tracker from a
+found pose that the assessor confirms.  Host logic only: the tracker, the assessor and the finder do the device work.
+"""
+import numpy as np
+
+from .assess import LOST, OCCLUDED, SUPPORTED
+
+
+class TrackSupervisor:
+    """TrackSupervisor(tracker, assessor, find=None, lost_frames=3, occluded_frames=0).step(frame) ->
+    (estimate, verdicts [parts], event).
+
+    tracker   .track(frame) -> State, .initialize([state]), .parts; driven frame by frame only.
+    assessor  .assess_state(tracker, state, frame) -> Assessment of one pose (a PoseAssessor).
+    find      None, or find(frame) -> a State (parts*12) or None; one object only.
+    A frame counts as lost when any body reads LOST, and -- with occluded_frames > 0 -- when any body has read OCCLUDED
+    for more than occluded_frames consecutive frames.  The lost_frames-th such frame in a row has the event "lost".
+    Without a finder the event repeats every further lost_frames such frames.  With a finder the next frame that still
+    counts as lost is searched: the found state is assessed against that frame, a SUPPORTED one re-initialises the
+    tracker ("reacquired", and the returned estimate is the found state); no state or any other verdict is
+    "find_failed", and the next attempt comes after another lost_frames such frames.  A frame that does not count as
+    lost ends the run.  Other frames: event None."""
+
+    def __init__(self, tracker, assessor, find=None, lost_frames=3, occluded_frames=0, look_ahead=False):
+        if look_ahead:
+            raise ValueError("TrackSupervisor drives the tracker frame by frame: a verdict decides what the next frame starts from")
+        if int(lost_frames) < 1 or int(occluded_frames) < 0:
+            raise ValueError("TrackSupervisor: lost_frames >= 1 and occluded_frames >= 0")
+        self.tracker, self.assessor, self.find = tracker, assessor, find
+        self.parts = int(tracker.parts)
+        if find is not None and self.parts != 1:
+            raise ValueError("TrackSupervisor: a finder searches for one object; this tracker has %d" % self.parts)
+        self.lost_frames, self.occluded_frames = int(lost_frames), int(occluded_frames)
+        self.lost_run = 0                                   # consecutive frames that count as lost
+        self.occluded_run = np.zeros(self.parts, dtype=int)  # consecutive OCCLUDED frames per body
+        self.next_attempt = None                            # finder: the lost_run at which the next search comes (None: not lost)
+        self.last = None                                    # the last frame's Assessment
+
+    def reset(self):
+        self.lost_run = 0
+        self.occluded_run[:] = 0
+        self.next_attempt = None
+
+    def step(self, frame):
+        if getattr(self.tracker, "_in_flight", 0) > 0:
+            raise ValueError("TrackSupervisor.step: the tracker has frames in flight (submit / result); collect them first")
+        est = self.tracker.track(frame)
+        self.last = self.assessor.assess_state(self.tracker, est, frame)
+        verdicts = np.asarray(self.last.verdicts).reshape(-1)[:self.parts].copy()
+        self.occluded_run = np.where(verdicts == OCCLUDED, self.occluded_run + 1, 0)
+        lost = bool((verdicts == LOST).any())
+        if self.occluded_frames > 0 and bool((self.occluded_run > self.occluded_frames).any()):
+            lost = True
+        if not lost:
+            self.lost_run, self.next_attempt = 0, None
+            return est, verdicts, None
+        self.lost_run += 1
+        if self.find is None:
+            return est, verdicts, "lost" if self.lost_run % self.lost_frames == 0 else None
+        if self.next_attempt is None:
+            if self.lost_run < self.lost_frames:
+                return est, verdicts, None
+            self.next_attempt = self.lost_run + 1
+            return est, verdicts, "lost"
+        if self.lost_run < self.next_attempt:
+            return est, verdicts, None
+        self.next_attempt = self.lost_run + self.lost_frames
+        state = self.find(frame)
+        if state is None:
+            return est, verdicts, "find_failed"
+        state = np.asarray(state, dtype=np.float64).reshape(-1)
+        found = self.assessor.assess_state(self.tracker, state, frame)
+        if not bool((np.asarray(found.verdicts).reshape(-1) == SUPPORTED).all()):
+            return est, verdicts, "find_failed"
+        self.tracker.initialize([state])
+        self.reset()
+        return state.copy(), verdicts, "reacquired"

@@ -199,6 +199,20 @@ class ParticleTracker:
         self.moving_average = est if self.moving_average is None else rate * est + (1 - rate) * self.moving_average
         return self.moving_average.copy()
 
+    # -- the last estimate judged against its frame (dbot_ros_amd/assess.py) -------------------
+    _in_flight = 0   # frames submitted and not yet collected (the device trackers' submit / result)
+
+    def assess(self, frame=None, assessor=None):
+        """The last estimate judged against `frame` (None: the sensor's current observation) -> assess.Assessment of one
+        pose.  assessor: a PoseAssessor over the same sensor (None: one with the default parameters, kept).  With frames
+        in flight (submit / result) the frame must be given: ValueError otherwise."""
+        from . import assess as _assess
+        if assessor is None:
+            assessor = getattr(self, "_assessor", None)
+            if assessor is None:
+                assessor = self._assessor = _assess.PoseAssessor(self.sensor)
+        return _assess.assess_last_estimate(self, assessor, frame, self._in_flight > 0)
+
 
 def _rotvecs(R):
     """Vectorised matrix -> rotation vector (atan2 form; particle deltas are far from pi)."""
@@ -257,6 +271,7 @@ class DeviceParticleTracker(ParticleTracker):
         self.sensor._check(self._lib.rbs_tracker_initialize(self._t, d.ctypes.data_as(self._C.POINTER(self._C.c_double))))
         self.moving_average = None
         self.n_resamplings = 0
+        self._in_flight = 0   # (rbs_tracker_initialize drops frames still in flight)
 
     def _frame_args(self, image, normals, uniforms):
         C = self._C
@@ -298,6 +313,7 @@ class DeviceParticleTracker(ParticleTracker):
         flight.  result() hands out the estimates in submission order."""
         _keep, args = self._frame_args(image, normals, uniforms)
         self.sensor._check((self._lib.rbs_tracker_submit_f64 if self._f64 else self._lib.rbs_tracker_submit)(self._t, *args))
+        self._in_flight += 1
 
     def result(self):
         """The moving-average estimate of the oldest submitted frame (rbs_tracker_result)."""
@@ -305,6 +321,7 @@ class DeviceParticleTracker(ParticleTracker):
         out = np.empty(self.parts * BODY)
         nres = C.c_int32()
         self.sensor._check(self._lib.rbs_tracker_result(self._t, out.ctypes.data_as(C.POINTER(C.c_double)), C.byref(nres)))
+        self._in_flight = max(0, self._in_flight - 1)
         return self._estimate(out, nres)
 
     def get_state(self):

@@ -814,6 +814,73 @@ int32_t rbs_find_get_perturbations(rbs_find* f, int32_t round, double* d, int64_
 /* Message of the last error on this finder. Never NULL. */
 const char* rbs_find_last_error(const rbs_find* f);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Poses judged against one depth frame (rbsensor_assess.hip).
+ *
+ * The reference leaves this judgement to a person: its controller shows the found pose in rviz and waits for a click
+ * between FindObject and RunObjectTracker (object_tracker_controller_service_node.cpp:180-195), and nothing tells a
+ * tracker that it has lost its object.  rbs_assess_poses counts, per pose and body, the pixels where the frame agrees
+ * with the rendered body, and names a verdict.  Everything below is binary64 with + - x and comparisons and integer
+ * counts: the same inputs give the same records on every run, and a numpy restatement takes every decision bit for bit.
+ *
+ * A call takes n absolute poses [n][n_objects][12] (R row-major | t, as for rbs_render_depth) and one frame.  For each pose:
+ *   planes    d_b(i) is the depth of body b rendered alone (the rasterizer of rbs_render_depth with that body only,
+ *             culled alike); uncovered pixels are +inf.  min over b of d_b equals rbs_render_depth of the pose bit for bit.
+ *   owner     body b owns pixel i when d_b(i) is finite, d_b(i) < d_c(i) for every c < b and d_b(i) <= d_c(i) for every
+ *             c > b: the nearest body, ties to the lowest.
+ *   class     of an owned pixel, with y the frame's float, d = d_b(i), r = (double)y - (double)d and
+ *             tau = sigmas x (model_sigma + sigma_factor x (d x d)) from the sensor's rbs_config (the finder's step 1b
+ *             sigma(z)):  y not finite: no reading;  r < -tau: in_front;  r > tau: behind (the sensor sees through the
+ *             place where the body should be);  otherwise: support.
+ *   record    per (pose, body): rendered = owned pixels, valid = those with a finite y, support, in_front, behind.
+ *   verdict   with u = support + behind:
+ *               1. rendered < min_pixels                                     RBS_ASSESS_OUT_OF_VIEW
+ *               2. (double)u < min_visible_fraction x (double)rendered        RBS_ASSESS_OCCLUDED (undecided)
+ *               3. (double)support >= min_support_fraction x (double)u        RBS_ASSESS_SUPPORTED
+ *               4. otherwise                                                  RBS_ASSESS_LOST
+ *
+ * The blind spot: something that stands NEARER than the pose says looks the same whether it is an occluder or the object
+ * itself.  A pose pushed 2 cm back from the truth reads in_front on most pixels and hence OCCLUDED, not LOST; `behind` is
+ * the decisive evidence, and only a pose that leaves the sensor looking through the body is called LOST.
+ *
+ * A call does not touch the sensor's state: poses staged by other calls, rbs_render_depth's image, the observation, the
+ * clock, the occlusion planes and their windows are left as they were.  It runs on the sensor's stream into buffers of
+ * its own (n x n_objects planes of rows x cols floats, allocated by the first call, grown when a later call needs more,
+ * freed by rbs_destroy) and ends with one copy of n x n_objects records and one synchronisation.  With frame == NULL it
+ * reads the sensor's current observation as rbs_get_observation does: it WAITS for the work queued on the sensor.  With
+ * a frame given it reads nothing of the sensor.  Limits: n >= 1, n x n_objects <= 64, every pose entry finite
+ * (checked on the host before any launch), single-device handles (RBS_ERR_UNSUPPORTED otherwise). */
+enum { RBS_ASSESS_OUT_OF_VIEW = 0, RBS_ASSESS_OCCLUDED = 1, RBS_ASSESS_SUPPORTED = 2, RBS_ASSESS_LOST = 3 };
+
+typedef struct rbs_assess_params {
+    double sigmas;                 /* 3: a correct pixel lies within 3 sigma(z) of the sensor's own noise model with
+                                      probability 0.997; finite, > 0                                                */
+    double min_support_fraction;   /* 0.5 of u, in [0, 1] (policy: DESIGN.md Appendix J)                            */
+    double min_visible_fraction;   /* 0.25 of rendered, in [0, 1] (policy)                                          */
+    int32_t min_pixels;            /* 16 (>= 1) (policy)                                                            */
+    int32_t reserved;              /* 0                                                                             */
+} rbs_assess_params;
+
+typedef struct rbs_assess_body {   /* 32 bytes */
+    int32_t rendered, valid, support, in_front, behind;
+    int32_t verdict;               /* RBS_ASSESS_*                                                                  */
+    int32_t reserved[2];           /* 0                                                                             */
+} rbs_assess_body;
+
+/* The defaults above, stated once. */
+void rbs_assess_default_params(rbs_assess_params* p);
+/* controller:180-195 -- n poses judged against one frame.  params: NULL = the defaults; frame: rows*cols floats (NULL:
+ * the sensor's current observation); poses [n][n_objects][12]; out [n][n_objects]. */
+int32_t rbs_assess_poses(rbs_handle* h, const rbs_assess_params* params, const float* frame, const double* poses, int32_t n,
+                         rbs_assess_body* out);
+/* The verdict of one record's counts (rule above): host only, no device.  params: NULL = the defaults. */
+int32_t rbs_assess_verdict(const rbs_assess_params* params, const rbs_assess_body* body, int32_t* verdict);
+/* Inspection, for the tests: d_b of pose k of the last call, rows*cols floats, +inf outside the body's rectangle.  Before
+ * the first call or for a bad k or b: RBS_ERR_INVALID_ARGUMENT. */
+int32_t rbs_assess_get_plane(rbs_handle* h, int32_t k, int32_t b, float* out);
+/* Device time of the last call's kernels in ms (HIP events): [0] render, [1] count. */
+int32_t rbs_assess_kernel_ms(rbs_handle* h, float* out2);
+
 #ifdef __cplusplus
 }
 #endif
