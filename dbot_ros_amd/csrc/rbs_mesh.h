@@ -20,9 +20,9 @@
 
 namespace rbs {
 
-constexpr int kMeshMaxBodies = 16;          // == kMaxBodies of the kernels (asserted in rbsensor_capi.hip)
+constexpr int kMeshMaxBodies = 16;          // == kMaxBodies of the kernels (asserted in rbs_handle.h)
 constexpr int kMeshOk = 0;
-constexpr int kMeshInvalidArgument = -1;    // == RBS_ERR_INVALID_ARGUMENT (asserted in rbsensor_capi.hip)
+constexpr int kMeshInvalidArgument = -1;    // == RBS_ERR_INVALID_ARGUMENT (asserted in rbs_handle.h)
 
 struct MeshInput {                  // as in rbs_config
     int n_bodies;

@@ -1,6 +1,6 @@
 // rbsensor_assess.hip -- poses judged against one depth frame (rbs_assess_*, include/rbsensor_mi355x.h; the rule:
-// DESIGN.md Appendix J).  Included at the end of rbsensor_capi.hip: it uses the handle, its observation and the
-// rasterizer of rbsensor_kernels.hip.
+// DESIGN.md Appendix J).  Included by rbsensor_capi.hip ahead of create_impl: it uses the handle, its observation and the
+// rasterizer of rbsensor_kernels.hip, and sensor creation and release call assess_configure / assess_release.
 //
 // Per call, on the sensor's stream:
 //   rbs_assess_render_kernel  one block row per (pose, body): the body's own screen rectangle cut into 64 x 64 tiles
