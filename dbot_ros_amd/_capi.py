@@ -52,8 +52,10 @@ EXPORTS = (
     "rbs_find_default_foreground", "rbs_find_set_foreground", "rbs_find_get_plane", "rbs_find_get_seed_frame",
     "rbs_find_default_refinement", "rbs_find_set_refinement", "rbs_find_get_covariance", "rbs_find_get_perturbations",
     "rbs_assess_default_params", "rbs_assess_poses", "rbs_assess_verdict", "rbs_assess_get_plane", "rbs_assess_kernel_ms",
+    "rbs_contour_default_params", "rbs_contour_poses", "rbs_contour_verdict", "rbs_contour_kernel_ms",
 )
 RBS_ASSESS_OUT_OF_VIEW, RBS_ASSESS_OCCLUDED, RBS_ASSESS_SUPPORTED, RBS_ASSESS_LOST = range(4)
+RBS_CONTOUR_NO_RIM, RBS_CONTOUR_UNDECIDED, RBS_CONTOUR_PRESENT, RBS_CONTOUR_ABSENT = range(4)
 RBS_FIND_SEEDS, RBS_FIND_COARSE, RBS_FIND_CANDIDATES, RBS_FIND_SURVIVORS, RBS_FIND_CHILDREN, RBS_FIND_RESULT = range(6)
 
 
@@ -143,6 +145,28 @@ class RbsAssessBody(C.Structure):
         ("support", C.c_int32),
         ("in_front", C.c_int32),
         ("behind", C.c_int32),
+        ("verdict", C.c_int32),
+        ("reserved", C.c_int32 * 2),
+    ]
+
+
+class RbsContourParams(C.Structure):
+    _fields_ = [
+        ("radius", C.c_int32),
+        ("min_rim_pixels", C.c_int32),
+        ("min_valid_fraction", C.c_double),
+        ("min_contour_fraction", C.c_double),
+        ("min_flush_fraction", C.c_double),
+    ]
+
+
+class RbsContourBody(C.Structure):
+    _fields_ = [
+        ("rim", C.c_int32),
+        ("valid", C.c_int32),
+        ("flush", C.c_int32),
+        ("in_front", C.c_int32),
+        ("beyond", C.c_int32),
         ("verdict", C.c_int32),
         ("reserved", C.c_int32 * 2),
     ]
@@ -382,5 +406,14 @@ def load():
     lib.rbs_assess_get_plane.argtypes = [H, C.c_int32, C.c_int32, fp]
     lib.rbs_assess_kernel_ms.restype = C.c_int32
     lib.rbs_assess_kernel_ms.argtypes = [H, fp]
+    lib.rbs_contour_default_params.restype = None
+    lib.rbs_contour_default_params.argtypes = [C.POINTER(RbsContourParams)]
+    lib.rbs_contour_poses.restype = C.c_int32
+    lib.rbs_contour_poses.argtypes = [H, C.POINTER(RbsAssessParams), C.POINTER(RbsContourParams), fp, dp, C.c_int32,
+                                      C.POINTER(RbsAssessBody), C.POINTER(RbsContourBody)]
+    lib.rbs_contour_verdict.restype = C.c_int32
+    lib.rbs_contour_verdict.argtypes = [C.POINTER(RbsContourParams), C.POINTER(RbsContourBody), ip]
+    lib.rbs_contour_kernel_ms.restype = C.c_int32
+    lib.rbs_contour_kernel_ms.argtypes = [H, fp]
     _lib = lib
     return lib

@@ -11,6 +11,8 @@
 //                             integer counts in LDS, one integer global add per block and counter.
 // Integer sums do not depend on their order: the same inputs give the same counts, run after run.  The verdict is
 // taken on the host from the counts (assess::verdict_of, also rbs_assess_verdict).
+// rbs_contour_poses (rbsensor_contour.hip) is the same call with one more kernel behind the count kernel, on the same
+// planes: assess::run below serves both entry points.
 namespace rbs {
 
 constexpr int kAssessMaxPlanes = 64;      // n x n_objects of one call
@@ -117,15 +119,21 @@ struct rbs_assess_state {
     float* d_planes = nullptr;      // [cap][npx]
     int4* d_rects = nullptr;        // [cap]
     int* d_rec = nullptr;           // [cap][8]
+    int* d_crec = nullptr;          // [cap][8] the contour rule's records (rbsensor_contour.hip)
     double* d_poses = nullptr;      // [cap][12]
     float* d_frame = nullptr;       // [npx] a caller's frame
-    unsigned char* h_pin = nullptr; // pinned: frame [npx] floats | poses [kAssessMaxPlanes][12] | records [kAssessMaxPlanes]
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    float ms[2] = {0.f, 0.f};
+    unsigned char* h_pin = nullptr; // pinned: frame [npx] floats | poses [kAssessMaxPlanes][12] | records [kAssessMaxPlanes] | contour records [kAssessMaxPlanes]
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    float ms[3] = {0.f, 0.f, 0.f};   // render, count, contour
     int n = 0;                      // poses of the last call (0: none yet)
+    bool contour = false;           // the last call was an rbs_contour_poses
 };
 
 namespace {
+
+// rbsensor_contour.hip: the rim kernel behind the count kernel, on the planes and rectangles of A, into rec (zeroed).
+int32_t contour_enqueue(rbs_handle* h, const rbs::AssessArgs& A, int n, int radius, int* rec);
+
 namespace assess {
 
 const char* check_params(const rbs_assess_params* p)
@@ -148,6 +156,7 @@ int32_t verdict_of(const rbs_assess_params& p, const rbs_assess_body& c)
 
 size_t pin_poses_off(const rbs_handle* h) { return (sizeof(float) * (size_t)h->npx + 15) & ~(size_t)15; }
 size_t pin_rec_off(const rbs_handle* h) { return pin_poses_off(h) + sizeof(double) * 12 * rbs::kAssessMaxPlanes; }
+size_t pin_crec_off(const rbs_handle* h) { return pin_rec_off(h) + sizeof(rbs_assess_body) * rbs::kAssessMaxPlanes; }
 
 int32_t ensure(rbs_handle* h, int planes)
 {
@@ -157,22 +166,110 @@ int32_t ensure(rbs_handle* h, int planes)
     }
     rbs_assess_state* a = h->assess;
     if (!a->h_pin) {
-        RBS_HIP(h, hipHostMalloc(&a->h_pin, pin_rec_off(h) + sizeof(rbs_assess_body) * rbs::kAssessMaxPlanes, hipHostMallocDefault));
+        RBS_HIP(h, hipHostMalloc(&a->h_pin, pin_crec_off(h) + sizeof(rbs_contour_body) * rbs::kAssessMaxPlanes, hipHostMallocDefault));
         RBS_HIP(h, hipMalloc(&a->d_frame, sizeof(float) * (size_t)h->npx));
         for (hipEvent_t& e : a->ev) RBS_HIP(h, hipEventCreate(&e));
     }
     if (planes > a->cap) {   // (grow-only; the stream is idle of this state's readers: every call ends synchronised)
         RBS_HIP(h, hipStreamSynchronize(h->stream));
-        (void)hipFree(a->d_planes); (void)hipFree(a->d_rects); (void)hipFree(a->d_rec); (void)hipFree(a->d_poses);
-        a->d_planes = nullptr; a->d_rects = nullptr; a->d_rec = nullptr; a->d_poses = nullptr;
+        (void)hipFree(a->d_planes); (void)hipFree(a->d_rects); (void)hipFree(a->d_rec); (void)hipFree(a->d_crec); (void)hipFree(a->d_poses);
+        a->d_planes = nullptr; a->d_rects = nullptr; a->d_rec = nullptr; a->d_crec = nullptr; a->d_poses = nullptr;
         a->cap = 0;
         a->n = 0;
         RBS_HIP(h, hipMalloc(&a->d_planes, sizeof(float) * (size_t)planes * h->npx));
         RBS_HIP(h, hipMalloc(&a->d_rects, sizeof(int4) * (size_t)planes));
         RBS_HIP(h, hipMalloc(&a->d_rec, sizeof(int) * rbs::kAssessFields * (size_t)planes));
+        RBS_HIP(h, hipMalloc(&a->d_crec, sizeof(int) * rbs::kAssessFields * (size_t)planes));
         RBS_HIP(h, hipMalloc(&a->d_poses, sizeof(double) * 12 * (size_t)planes));
         a->cap = planes;
     }
+    return RBS_OK;
+}
+
+// rbs_assess_poses (contour == nullptr: its two kernels and nothing else) and rbs_contour_poses (contour: checked by the
+// caller; one more kernel and one more copy; out_contour gets the counts, its caller takes the verdicts).  `who` names
+// the entry point in the messages.  out may be NULL.
+int32_t run(rbs_handle* h, const char* who, const rbs_assess_params* params, const rbs_contour_params* contour, const float* frame,
+            const double* poses, int32_t n, rbs_assess_body* out, rbs_contour_body* out_contour)
+{
+    if (!poses) return fail(h, RBS_ERR_INVALID_ARGUMENT, fmt("%s: null pointer", who));
+    if (n < 1) return fail(h, RBS_ERR_INVALID_ARGUMENT, fmt("%s: n < 1", who));
+    rbs_assess_params p;
+    if (params) p = *params; else rbs_assess_default_params(&p);
+    if (const char* bad = check_params(&p)) return fail(h, RBS_ERR_INVALID_ARGUMENT, bad);
+    if (!h->shards.empty() || h->group || h->peer_world > 1)
+        return fail(h, RBS_ERR_UNSUPPORTED, fmt("%s: single-device handles only", who));
+    const int B = h->n_bodies;
+    if ((long)n * B > rbs::kAssessMaxPlanes)
+        return fail(h, RBS_ERR_INVALID_ARGUMENT, fmt("%s: n x n_objects = %ld exceeds %d", who, (long)n * B, rbs::kAssessMaxPlanes));
+    const int planes = n * B;
+    for (size_t i = 0; i < (size_t)planes * 12; ++i)
+        if (!std::isfinite(poses[i])) return fail(h, RBS_ERR_INVALID_ARGUMENT, fmt("%s: pose entry %zu is not finite", who, i));
+    RBS_REFUSE_POISONED(h);
+    RBS_HIP(h, hipSetDevice(h->device));
+    if (int32_t rc = ensure(h, planes)) return rc;
+    rbs_assess_state* a = h->assess;
+    hipStream_t s = h->stream;
+    const size_t npx = (size_t)h->npx;
+    const float* d_frame;
+    if (frame) {
+        std::memcpy(a->h_pin, frame, sizeof(float) * npx);
+        RBS_HIP(h, hipMemcpyAsync(a->d_frame, a->h_pin, sizeof(float) * npx, hipMemcpyHostToDevice, s));
+        d_frame = a->d_frame;
+    } else {   // the sensor's current observation, as rbs_get_observation reads it (the kernels below run behind the sensor's queued work)
+        if (int32_t rc = make_current(h, s)) return rc;
+        d_frame = obs_frame(h);
+    }
+    double* h_poses = reinterpret_cast<double*>(a->h_pin + pin_poses_off(h));
+    rbs_assess_body* h_rec = reinterpret_cast<rbs_assess_body*>(a->h_pin + pin_rec_off(h));
+    rbs_contour_body* h_crec = reinterpret_cast<rbs_contour_body*>(a->h_pin + pin_crec_off(h));
+    std::memcpy(h_poses, poses, sizeof(double) * 12 * (size_t)planes);
+    RBS_HIP(h, hipMemcpyAsync(a->d_poses, h_poses, sizeof(double) * 12 * (size_t)planes, hipMemcpyHostToDevice, s));
+    RBS_HIP(h, hipMemsetAsync(a->d_rec, 0, sizeof(int) * rbs::kAssessFields * (size_t)planes, s));
+    if (contour) RBS_HIP(h, hipMemsetAsync(a->d_crec, 0, sizeof(int) * rbs::kAssessFields * (size_t)planes, s));
+    DevParams P = h->base;
+    P.poses = a->d_poses;
+    P.n = n;
+    P.tile_w = rbs::kAssessTileW;
+    P.tile_px = rbs::kAssessTilePx;
+    P.tile_h = rbs::kAssessTilePx / rbs::kAssessTileW;
+    a->n = 0;
+    a->contour = false;
+    RBS_HIP(h, hipEventRecord(a->ev[0], s));
+    hipLaunchKernelGGL(rbs::rbs_assess_render_kernel, dim3((unsigned)planes, rbs::kAssessRenderSplit), dim3(rbs::kBlock),
+                       rbs::smem_bytes(rbs::kAssessTilePx, false), s, P, a->d_planes, a->d_rects);
+    RBS_HIP(h, hipGetLastError());
+    RBS_HIP(h, hipEventRecord(a->ev[1], s));
+    rbs::AssessArgs A{};
+    A.planes = a->d_planes;
+    A.rects = a->d_rects;
+    A.frame = d_frame;
+    A.cols = h->cols;
+    A.npx = h->npx;
+    A.B = B;
+    A.sigmas = p.sigmas;
+    A.ms = h->base.ms;
+    A.sf = h->base.sf;
+    A.rec = a->d_rec;
+    hipLaunchKernelGGL(rbs::rbs_assess_count_kernel, dim3(rbs::kAssessCountBlocks, (unsigned)n), dim3(256), 0, s, A);
+    RBS_HIP(h, hipGetLastError());
+    RBS_HIP(h, hipEventRecord(a->ev[2], s));
+    if (contour) {
+        if (int32_t rc = contour_enqueue(h, A, n, contour->radius, a->d_crec)) return rc;
+        RBS_HIP(h, hipEventRecord(a->ev[3], s));
+        RBS_HIP(h, hipMemcpyAsync(h_crec, a->d_crec, sizeof(rbs_contour_body) * (size_t)planes, hipMemcpyDeviceToHost, s));
+    }
+    RBS_HIP(h, hipMemcpyAsync(h_rec, a->d_rec, sizeof(rbs_assess_body) * (size_t)planes, hipMemcpyDeviceToHost, s));
+    RBS_HIP(h, hipStreamSynchronize(s));
+    for (int k = 0; k < (contour ? 3 : 2); ++k) RBS_HIP(h, hipEventElapsedTime(&a->ms[k], a->ev[k], a->ev[k + 1]));
+    for (int i = 0; out && i < planes; ++i) {
+        out[i] = h_rec[i];
+        out[i].verdict = verdict_of(p, out[i]);
+        out[i].reserved[0] = out[i].reserved[1] = 0;
+    }
+    for (int i = 0; out_contour && i < planes; ++i) out_contour[i] = h_crec[i];
+    a->n = n;
+    a->contour = contour != nullptr;
     return RBS_OK;
 }
 
@@ -194,6 +291,7 @@ void assess_release(rbs_handle* h)
     (void)hipFree(a->d_planes);
     (void)hipFree(a->d_rects);
     (void)hipFree(a->d_rec);
+    (void)hipFree(a->d_crec);
     (void)hipFree(a->d_poses);
     (void)hipFree(a->d_frame);
     if (a->h_pin) (void)hipHostFree(a->h_pin);
@@ -231,75 +329,8 @@ int32_t rbs_assess_poses(rbs_handle* h, const rbs_assess_params* params, const f
                          rbs_assess_body* out)
 {
     if (!h) return RBS_ERR_INVALID_ARGUMENT;
-    if (!poses || !out) return fail(h, RBS_ERR_INVALID_ARGUMENT, "assess_poses: null pointer");
-    if (n < 1) return fail(h, RBS_ERR_INVALID_ARGUMENT, "assess_poses: n < 1");
-    rbs_assess_params p;
-    if (params) p = *params; else rbs_assess_default_params(&p);
-    if (const char* bad = assess::check_params(&p)) return fail(h, RBS_ERR_INVALID_ARGUMENT, bad);
-    if (!h->shards.empty() || h->group || h->peer_world > 1)
-        return fail(h, RBS_ERR_UNSUPPORTED, "assess_poses: single-device handles only");
-    const int B = h->n_bodies;
-    if ((long)n * B > rbs::kAssessMaxPlanes)
-        return fail(h, RBS_ERR_INVALID_ARGUMENT, fmt("assess_poses: n x n_objects = %ld exceeds %d", (long)n * B, rbs::kAssessMaxPlanes));
-    const int planes = n * B;
-    for (size_t i = 0; i < (size_t)planes * 12; ++i)
-        if (!std::isfinite(poses[i])) return fail(h, RBS_ERR_INVALID_ARGUMENT, fmt("assess_poses: pose entry %zu is not finite", i));
-    RBS_REFUSE_POISONED(h);
-    RBS_HIP(h, hipSetDevice(h->device));
-    if (int32_t rc = assess::ensure(h, planes)) return rc;
-    rbs_assess_state* a = h->assess;
-    hipStream_t s = h->stream;
-    const size_t npx = (size_t)h->npx;
-    const float* d_frame;
-    if (frame) {
-        std::memcpy(a->h_pin, frame, sizeof(float) * npx);
-        RBS_HIP(h, hipMemcpyAsync(a->d_frame, a->h_pin, sizeof(float) * npx, hipMemcpyHostToDevice, s));
-        d_frame = a->d_frame;
-    } else {   // the sensor's current observation, as rbs_get_observation reads it (the kernels below run behind the sensor's queued work)
-        if (int32_t rc = make_current(h, s)) return rc;
-        d_frame = obs_frame(h);
-    }
-    double* h_poses = reinterpret_cast<double*>(a->h_pin + assess::pin_poses_off(h));
-    rbs_assess_body* h_rec = reinterpret_cast<rbs_assess_body*>(a->h_pin + assess::pin_rec_off(h));
-    std::memcpy(h_poses, poses, sizeof(double) * 12 * (size_t)planes);
-    RBS_HIP(h, hipMemcpyAsync(a->d_poses, h_poses, sizeof(double) * 12 * (size_t)planes, hipMemcpyHostToDevice, s));
-    RBS_HIP(h, hipMemsetAsync(a->d_rec, 0, sizeof(int) * rbs::kAssessFields * (size_t)planes, s));
-    DevParams P = h->base;
-    P.poses = a->d_poses;
-    P.n = n;
-    P.tile_w = rbs::kAssessTileW;
-    P.tile_px = rbs::kAssessTilePx;
-    P.tile_h = rbs::kAssessTilePx / rbs::kAssessTileW;
-    a->n = 0;
-    RBS_HIP(h, hipEventRecord(a->ev[0], s));
-    hipLaunchKernelGGL(rbs::rbs_assess_render_kernel, dim3((unsigned)planes, rbs::kAssessRenderSplit), dim3(rbs::kBlock),
-                       rbs::smem_bytes(rbs::kAssessTilePx, false), s, P, a->d_planes, a->d_rects);
-    RBS_HIP(h, hipGetLastError());
-    RBS_HIP(h, hipEventRecord(a->ev[1], s));
-    rbs::AssessArgs A{};
-    A.planes = a->d_planes;
-    A.rects = a->d_rects;
-    A.frame = d_frame;
-    A.cols = h->cols;
-    A.npx = h->npx;
-    A.B = B;
-    A.sigmas = p.sigmas;
-    A.ms = h->base.ms;
-    A.sf = h->base.sf;
-    A.rec = a->d_rec;
-    hipLaunchKernelGGL(rbs::rbs_assess_count_kernel, dim3(rbs::kAssessCountBlocks, (unsigned)n), dim3(256), 0, s, A);
-    RBS_HIP(h, hipGetLastError());
-    RBS_HIP(h, hipEventRecord(a->ev[2], s));
-    RBS_HIP(h, hipMemcpyAsync(h_rec, a->d_rec, sizeof(rbs_assess_body) * (size_t)planes, hipMemcpyDeviceToHost, s));
-    RBS_HIP(h, hipStreamSynchronize(s));
-    for (int k = 0; k < 2; ++k) RBS_HIP(h, hipEventElapsedTime(&a->ms[k], a->ev[k], a->ev[k + 1]));
-    for (int i = 0; i < planes; ++i) {
-        out[i] = h_rec[i];
-        out[i].verdict = assess::verdict_of(p, out[i]);
-        out[i].reserved[0] = out[i].reserved[1] = 0;
-    }
-    a->n = n;
-    return RBS_OK;
+    if (!out) return fail(h, RBS_ERR_INVALID_ARGUMENT, "assess_poses: null pointer");
+    return assess::run(h, "assess_poses", params, nullptr, frame, poses, n, out, nullptr);
 }
 
 int32_t rbs_assess_get_plane(rbs_handle* h, int32_t k, int32_t b, float* out)

@@ -13,7 +13,7 @@
 //   rbs_handle.h   struct rbs_handle, Rccl, fmt / fail / upload, RBS_HIP, RBS_REFUSE_POISONED, with_flags
 //   rbs_call.h     the likelihood call: occlusion_coeffs, launch_prep, launch_raster, launch_bgp_step, stp_decide, enqueue_loglikes
 //   rbs_ipc.h      IpcBlob, rbs_ipc_export, rbs_ipc_attach, rbs_stage_windows, rbs_peer_resample
-// This file, in order: frame ingest, (rbs_call.h), plane housekeeping, (rbsensor_assess.hip), release / create_impl, several
+// This file, in order: frame ingest, (rbs_call.h), plane housekeeping, (rbsensor_assess.hip, rbsensor_contour.hip), release / create_impl, several
 // devices, the extern "C" sensor entry points (rbs_ipc.h among them), the device tracker's API.
 #include "rbsensor_kernels.hip"
 #include "rbsensor_tracker.hip"
@@ -657,6 +657,8 @@ int32_t drain(rbs_handle* h, bool host_sync)
 
 // The pose assessor (rbs_assess_*): its kernels and host side (release and create_impl call into it).
 #include "rbsensor_assess.hip"
+// The contour rule beside it (rbs_contour_*): one more kernel on the assessor's planes.
+#include "rbsensor_contour.hip"
 
 namespace {
 

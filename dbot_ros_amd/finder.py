@@ -192,7 +192,8 @@ class ObjectFinder:
         """frame: rows*cols depth (metres, NaN = no reading) at the sensor's resolution, or None for
         the sensor's current observation.  Returns up to k (default n_survivors) poses, best first.
         assess: a PoseAssessor over the same sensor -- the returned poses are judged against the same frame
-        (FindResult.assessment) and `confirmed` names the first one that is SUPPORTED; `found` is unchanged."""
+        (FindResult.assessment) and `confirmed` names the first one that is SUPPORTED (with the assessor's contour rule
+        on: the first of Assessment.confirmed_mask()); `found` is unchanged."""
         k = int(self.params.n_survivors if k is None else k)
         poses = np.zeros((max(k, 1), 12))
         scores = np.zeros(max(k, 1))
@@ -220,6 +221,8 @@ class ObjectFinder:
             if K > 0:
                 res.assessment = assess.assess(poses[:min(K, 64)], img)
                 hits = np.nonzero(res.assessment.verdicts[:, 0] == SUPPORTED)[0]
+                if res.assessment.contour_verdicts is not None:   # the assessor's contour rule is on: the silhouette must be PRESENT too
+                    hits = np.nonzero(res.assessment.confirmed_mask())[0]
                 res.confirmed = int(hits[0]) if hits.size else -1
         return res
 

@@ -169,7 +169,9 @@ def replay_dataset_supervised(params, dataset, mesh_package_path, initial_states
     its frame (dbot_ros_amd/assess.py) and a TrackSupervisor (dbot_ros_amd/supervisor.py) re-finds an object the tracker
     has lost.  Frame by frame only (look_ahead: ValueError) -- a verdict decides what the next frame starts from.
     The optional `supervisor:` mapping of the tree: lost_frames (3), occluded_frames (0), assess: (PoseAssessor.Parameters'
-    fields).  initial_states=None: the object is found on frame 0 and the find must be CONFIRMED -- the first returned pose
+    fields), contour: (PoseAssessor.ContourParameters' fields; its presence, even empty, switches the contour rule on: a
+    find is then confirmed only when its silhouette reads PRESENT too), contour_lost: (false; with contour: a body whose
+    contour verdict is ABSENT makes the frame count as lost).  initial_states=None: the object is found on frame 0 and the find must be CONFIRMED -- the first returned pose
     that reads SUPPORTED starts the tracker; none: RuntimeError.  With initial states and several objects there is no finder:
     the supervisor only reports.  Returns (estimates [frames, parts*12], verdicts [frames, parts], events [frames] of
     None / "lost" / "reacquired" / "find_failed")."""
@@ -178,10 +180,11 @@ def replay_dataset_supervised(params, dataset, mesh_package_path, initial_states
     if look_ahead:
         raise ValueError("replay_dataset_supervised runs frame by frame: look_ahead is not supported")
     m = dict((params or {}).get("supervisor") or {})
-    unknown = sorted(set(m) - {"lost_frames", "occluded_frames", "assess"})
+    unknown = sorted(set(m) - {"lost_frames", "occluded_frames", "assess", "contour", "contour_lost"})
     if unknown:
-        raise ValueError(f"supervisor/{unknown[0]}: unknown key (one of ['assess', 'lost_frames', 'occluded_frames'])")
+        raise ValueError(f"supervisor/{unknown[0]}: unknown key (one of ['assess', 'contour', 'contour_lost', 'lost_frames', 'occluded_frames'])")
     assess_params = PoseAssessor.Parameters.from_mapping(m.get("assess"))
+    contour_params = PoseAssessor.ContourParameters.from_mapping(m["contour"]) if "contour" in m else None
     tracker, object_model, camera_data, _ = build_particle_tracker(params, dataset.get_camera_matrix(0),
                                                                    mesh_package_path, device_id=device_id, seed=seed)
     f = int(params["downsampling_factor"])
@@ -189,7 +192,7 @@ def replay_dataset_supervised(params, dataset, mesh_package_path, initial_states
     try:
         n = dataset.size() if max_frames is None else min(max_frames, dataset.size())
         frames = [dataset.frame_vector(i, f) for i in range(n)]
-        assessor = PoseAssessor(tracker.sensor, assess_params)
+        assessor = PoseAssessor(tracker.sensor, assess_params, contour_params)
         find = None
         if tracker.parts == 1:
             finder, _, _ = build_object_finder(params, dataset.get_camera_matrix(0), mesh_package_path, device_id=device_id,
@@ -207,7 +210,7 @@ def replay_dataset_supervised(params, dataset, mesh_package_path, initial_states
             initial_states = [state]
         tracker.initialize(initial_states)
         sup = TrackSupervisor(tracker, assessor, find=find, lost_frames=int(m.get("lost_frames", 3)),
-                              occluded_frames=int(m.get("occluded_frames", 0)))
+                              occluded_frames=int(m.get("occluded_frames", 0)), contour_lost=bool(m.get("contour_lost", False)))
         ests, verdicts, events = [], [], []
         for fr in frames:
             e, v, ev = sup.step(fr)

@@ -6,7 +6,7 @@ found pose that the assessor confirms.  Host logic only: the tracker, the assess
 """
 import numpy as np
 
-from .assess import LOST, OCCLUDED, SUPPORTED
+from .assess import CONTOUR_ABSENT, LOST, OCCLUDED, SUPPORTED
 
 
 class TrackSupervisor:
@@ -22,9 +22,12 @@ class TrackSupervisor:
     counts as lost is searched: the found state is assessed against that frame, a SUPPORTED one re-initialises the
     tracker ("reacquired", and the returned estimate is the found state); no state or any other verdict is
     "find_failed", and the next attempt comes after another lost_frames such frames.  A frame that does not count as
-    lost ends the run.  Other frames: event None."""
+    lost ends the run.  Other frames: event None.
+    With the assessor's contour rule on (PoseAssessor(contour=...)) a found state must pass Assessment.confirmed_mask():
+    SUPPORTED and its silhouette PRESENT.  contour_lost=True (it needs that rule) also counts a frame as lost when a
+    body's contour verdict is ABSENT."""
 
-    def __init__(self, tracker, assessor, find=None, lost_frames=3, occluded_frames=0, look_ahead=False):
+    def __init__(self, tracker, assessor, find=None, lost_frames=3, occluded_frames=0, look_ahead=False, contour_lost=False):
         if look_ahead:
             raise ValueError("TrackSupervisor drives the tracker frame by frame: a verdict decides what the next frame starts from")
         if int(lost_frames) < 1 or int(occluded_frames) < 0:
@@ -34,6 +37,9 @@ class TrackSupervisor:
         if find is not None and self.parts != 1:
             raise ValueError("TrackSupervisor: a finder searches for one object; this tracker has %d" % self.parts)
         self.lost_frames, self.occluded_frames = int(lost_frames), int(occluded_frames)
+        self.contour_lost = bool(contour_lost)
+        if self.contour_lost and getattr(assessor, "contour", None) is None:
+            raise ValueError("TrackSupervisor: contour_lost needs an assessor with the contour rule on")
         self.lost_run = 0                                   # consecutive frames that count as lost
         self.occluded_run = np.zeros(self.parts, dtype=int)  # consecutive OCCLUDED frames per body
         self.next_attempt = None                            # finder: the lost_run at which the next search comes (None: not lost)
@@ -54,6 +60,8 @@ class TrackSupervisor:
         lost = bool((verdicts == LOST).any())
         if self.occluded_frames > 0 and bool((self.occluded_run > self.occluded_frames).any()):
             lost = True
+        if self.contour_lost and bool((np.asarray(self.last.contour_verdicts).reshape(-1)[:self.parts] == CONTOUR_ABSENT).any()):
+            lost = True
         if not lost:
             self.lost_run, self.next_attempt = 0, None
             return est, verdicts, None
@@ -73,7 +81,10 @@ class TrackSupervisor:
             return est, verdicts, "find_failed"
         state = np.asarray(state, dtype=np.float64).reshape(-1)
         found = self.assessor.assess_state(self.tracker, state, frame)
-        if not bool((np.asarray(found.verdicts).reshape(-1) == SUPPORTED).all()):
+        ok = bool((np.asarray(found.verdicts).reshape(-1) == SUPPORTED).all())
+        if getattr(found, "contour_verdicts", None) is not None:
+            ok = bool(found.confirmed_mask().all())
+        if not ok:
             return est, verdicts, "find_failed"
         self.tracker.initialize([state])
         self.reset()

@@ -881,6 +881,64 @@ int32_t rbs_assess_get_plane(rbs_handle* h, int32_t k, int32_t b, float* out);
 /* Device time of the last call's kernels in ms (HIP events): [0] render, [1] count. */
 int32_t rbs_assess_kernel_ms(rbs_handle* h, float* out2);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * The silhouette of a pose judged against the frame (rbsensor_contour.hip; DESIGN.md Appendix J, "The contour rule").
+ *
+ * The assess rule above sees depth agreement INSIDE the rendered body and nothing else: a pose whose visible face lies in
+ * a surface of the scene (a wall, a table) reads RBS_ASSESS_SUPPORTED.  The contour rule is an opt-in second rule beside
+ * it.  It looks at the pixels just OUTSIDE the rendered body: around an object the scene falls away behind the
+ * silhouette; around a pose that lies in a wall the wall goes on.  Inputs per pose are the planes d_b of the assess rule
+ * and the frame y; owner(i) and depth(i) = d_owner(i)(i) are those of the assess rule; a pixel is covered when it has an
+ * owner.  Everything is binary64 + - x, comparisons, a float maximum and integer counts, as above.
+ *   rim       an uncovered pixel i inside the image (no body of the pose owns it) is a rim pixel of body b when some
+ *             pixel j owned by b lies in the Chebyshev window |x_i - x_j| <= radius, |y_i - y_j| <= radius, clipped to
+ *             the image.  A pixel may be a rim pixel of several bodies and counts in each one's record.
+ *   anchor    a_b(i) = the maximum of depth(j) over those j, as a float: the farthest point of the body's surface beside
+ *             the pixel (the conservative choice; a maximum does not depend on order).
+ *   class     of a rim pixel with a finite y, with g = (double)y - (double)a and
+ *             tau = sigmas x (model_sigma + sigma_factor x (a x a)), sigmas the assess parameter:
+ *             g < -tau: in_front (an occluder, or nothing to learn);  g > tau: beyond (the scene falls away behind the
+ *             silhouette);  otherwise: flush (the surface the pose lies in continues past its silhouette).
+ *   record    per (pose, body): rim, valid (finite y), flush, in_front, beyond; valid = flush + in_front + beyond.
+ *   verdict   on the host from the counts, in this order:
+ *               1. rim < min_rim_pixels                                                      RBS_CONTOUR_NO_RIM
+ *               2. valid == 0 or (double)valid < min_valid_fraction x (double)rim            RBS_CONTOUR_UNDECIDED
+ *               3. (double)beyond >= min_contour_fraction x (double)valid                    RBS_CONTOUR_PRESENT
+ *               4. (double)flush >= min_flush_fraction x (double)valid                       RBS_CONTOUR_ABSENT
+ *               5. otherwise                                                                 RBS_CONTOUR_UNDECIDED
+ *
+ * rbs_contour_poses is rbs_assess_poses plus one more kernel on the same planes: one call, one frame upload, one
+ * synchronisation.  out_assess (may be NULL) equals rbs_assess_poses' output for the same arguments field for field;
+ * limits, frame == NULL and "touches nothing of the sensor" are rbs_assess_poses'; rbs_assess_get_plane works after it. */
+enum { RBS_CONTOUR_NO_RIM = 0, RBS_CONTOUR_UNDECIDED = 1, RBS_CONTOUR_PRESENT = 2, RBS_CONTOUR_ABSENT = 3 };
+
+typedef struct rbs_contour_params {   /* 32 bytes */
+    int32_t radius;                /* 2 pixels (1 .. 8): half the window's side                                     */
+    int32_t min_rim_pixels;        /* 16 (>= 1) (policy: DESIGN.md Appendix J)                                      */
+    double min_valid_fraction;     /* 0.5 of rim, in [0, 1] (policy)                                                */
+    double min_contour_fraction;   /* 0.3 of valid, in [0, 1] (policy)                                              */
+    double min_flush_fraction;     /* 0.5 of valid, in [0, 1] (policy)                                              */
+} rbs_contour_params;
+
+typedef struct rbs_contour_body {   /* 32 bytes */
+    int32_t rim, valid, flush, in_front, beyond;
+    int32_t verdict;               /* RBS_CONTOUR_*                                                                 */
+    int32_t reserved[2];           /* 0                                                                             */
+} rbs_contour_body;
+
+/* The defaults above, stated once. */
+void rbs_contour_default_params(rbs_contour_params* p);
+/* n poses judged by both rules against one frame.  params, contour: NULL = the defaults; frame, poses, n: as for
+ * rbs_assess_poses; out_assess [n][n_objects] or NULL; out_contour [n][n_objects].  Bad parameters are refused before
+ * any launch. */
+int32_t rbs_contour_poses(rbs_handle* h, const rbs_assess_params* params, const rbs_contour_params* contour, const float* frame,
+                          const double* poses, int32_t n, rbs_assess_body* out_assess, rbs_contour_body* out_contour);
+/* The verdict of one record's counts (rule above): host only, no device.  params: NULL = the defaults. */
+int32_t rbs_contour_verdict(const rbs_contour_params* params, const rbs_contour_body* body, int32_t* verdict);
+/* Device time of the last rbs_contour_poses' kernels in ms (HIP events): [0] render, [1] count, [2] contour.  When the
+ * handle's last assessment was not an rbs_contour_poses: RBS_ERR_INVALID_ARGUMENT. */
+int32_t rbs_contour_kernel_ms(rbs_handle* h, float* out3);
+
 #ifdef __cplusplus
 }
 #endif

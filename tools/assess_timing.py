@@ -16,7 +16,11 @@ finds: the object finder's default search on tools/find_object_timing.py's scene
 of DESIGN.md Appendix F are m1,m2,m3 x 101,102), the truth pose and the best found pose assessed against the frame with
 the assessor's default parameters; fraction = support / u, u = support + behind; confirmed: FindResult.confirmed.
 --no-finds skips that part.
+--contour: the assessor with the contour rule on at its defaults (rbs_contour_poses): "assess" rows gain "contour_ms" (the
+third kernel), every record of "finds" gains "contour": {"rim", "valid", "flush", "in_front", "beyond", "verdict"}, "found"
+rows gain "supported_by_plain_rule" and "confirmed" is Assessment.confirmed_mask()'s first pose.
 Usage: python tools/assess_timing.py [--calls N] [--frames F] [--particles P] [--cases m1,m2,m3] [--scene-seeds 101,102] [--no-finds]
+                                     [--contour]
 """
 import argparse
 import json
@@ -31,13 +35,13 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")]
 
 import scenarios as sc  # noqa: E402
 from dbot_ros_amd import RbSensor, RbSensorBuilder, synth  # noqa: E402
-from dbot_ros_amd.assess import VERDICTS, PoseAssessor  # noqa: E402
+from dbot_ros_amd.assess import CONTOUR_COUNTS, CONTOUR_VERDICTS, SUPPORTED, VERDICTS, PoseAssessor  # noqa: E402
 from dbot_ros_amd.finder import ObjectFinder  # noqa: E402
 from dbot_ros_amd.pose import matrix_to_rotvec  # noqa: E402
 from dbot_ros_amd.tracker import DeviceParticleTracker, ObjectTransitionBuilder, ParticleTrackerBuilder  # noqa: E402
 
 
-def timing(calls, frames, particles):
+def timing(calls, frames, particles, contour=None):
     cols, rows = 640, 480
     om, cam, _ = sc.make_scene(("m1",), cols, rows, max_particles=particles)
     P = RbSensorBuilder.Parameters(sample_count=particles)
@@ -47,7 +51,7 @@ def timing(calls, frames, particles):
     with RbSensor(om, cam, P, max_particles=particles) as sensor:
         seq = [synth.make_frame(np.where(np.isfinite(d), d, np.inf), rows, cols, rng)
                for d in (sensor.render_depth(t) for t in truths)]
-        a = PoseAssessor(sensor)
+        a = PoseAssessor(sensor, contour=contour)
         for n in (1, 32):
             poses = np.concatenate([truths[0][None], synth.particle_poses(truths[0], n - 1, rng, scale=2.0)]) if n > 1 else truths[0][None]
             a.assess(poses, seq[0])                               # warm-up (and the buffers' allocation)
@@ -57,6 +61,8 @@ def timing(calls, frames, particles):
             host = (time.perf_counter() - t0) / calls * 1e3
             ms = a.kernel_ms()
             out["assess"].append({"n": n, "host_ms": round(host, 3), "render_ms": round(ms[0], 3), "count_ms": round(ms[1], 3)})
+            if contour is not None:
+                out["assess"][-1]["contour_ms"] = round(ms[2], 3)
         tr = DeviceParticleTracker(ObjectTransitionBuilder(ObjectTransitionBuilder.Parameters()).build(), sensor, om,
                                    ParticleTrackerBuilder.Parameters(evaluation_count=particles), device_rng=True, seed=1)
         s0 = np.zeros(12)
@@ -72,13 +78,20 @@ def timing(calls, frames, particles):
     return out
 
 
-def record(c, v):
+def record(c, v, cc=None, cv=None):
     rendered, support, behind = int(c[0]), int(c[2]), int(c[4])
     u = support + behind
-    return {"rendered": rendered, "support": support, "u": u, "fraction": round(support / u, 3) if u else None, "verdict": VERDICTS[int(v)]}
+    out = {"rendered": rendered, "support": support, "u": u, "fraction": round(support / u, 3) if u else None, "verdict": VERDICTS[int(v)]}
+    if cc is not None:
+        out["contour"] = dict({k: int(x) for k, x in zip(CONTOUR_COUNTS, cc)}, verdict=CONTOUR_VERDICTS[int(cv)])
+    return out
 
 
-def finds(cases, seeds):
+def contour_of(a, k):
+    return (a.contour_counts[k, 0], a.contour_verdicts[k, 0]) if a.contour_counts is not None else (None, None)
+
+
+def finds(cases, seeds, contour=None):
     import find_object_timing as fot
     out = []
     for name in cases:
@@ -87,15 +100,18 @@ def finds(cases, seeds):
         for seed in seeds:
             with RbSensor(om, cam, P, max_particles=1) as sensor:
                 truth, frame, _ = fot.scene(sensor, cam, seed)
-                a = PoseAssessor(sensor)
+                a = PoseAssessor(sensor, contour=contour)
                 with ObjectFinder(sensor, om, ObjectFinder.Parameters()) as fnd:
                     r = fnd.find(frame, assess=a)
                 t = a.assess(truth, frame)
-                row = {"case": name, "scene_seed": seed, "truth": record(t.counts[0, 0], t.verdicts[0, 0]), "found": None,
+                row = {"case": name, "scene_seed": seed, "truth": record(t.counts[0, 0], t.verdicts[0, 0], *contour_of(t, 0)), "found": None,
                        "confirmed": r.confirmed}
                 if len(r.poses):
                     row["found"] = dict(dt_mm=round(float(np.linalg.norm(r.poses[0, 9:] - truth[9:])) * 1e3, 1),
-                                        **record(r.assessment.counts[0, 0], r.assessment.verdicts[0, 0]))
+                                        **record(r.assessment.counts[0, 0], r.assessment.verdicts[0, 0], *contour_of(r.assessment, 0)))
+                    if contour is not None:
+                        hits = np.nonzero(r.assessment.verdicts[:, 0] == SUPPORTED)[0]
+                        row["found"]["supported_by_plain_rule"] = int(hits[0]) if hits.size else -1
                 out.append(row)
     return out
 
@@ -108,10 +124,12 @@ def main():
     ap.add_argument("--cases", default="m1,m2,m3")
     ap.add_argument("--scene-seeds", default="101,102")
     ap.add_argument("--no-finds", action="store_true")
+    ap.add_argument("--contour", action="store_true")
     a = ap.parse_args()
-    res = {"tool": "assess_timing", "timing": timing(a.calls, a.frames, a.particles)}
+    contour = PoseAssessor.ContourParameters() if a.contour else None
+    res = {"tool": "assess_timing", "timing": timing(a.calls, a.frames, a.particles, contour)}
     if not a.no_finds:
-        res["finds"] = finds(a.cases.split(","), [int(s) for s in a.scene_seeds.split(",")])
+        res["finds"] = finds(a.cases.split(","), [int(s) for s in a.scene_seeds.split(",")], contour)
     print(json.dumps(res))
 
 
