@@ -9,12 +9,15 @@
 //   poses / indices / out   per-call staging for the host-pointer API
 // There is no CPU path in this library.
 //
-// One translation unit.  Three parts of the host side have files of their own, included below where they are needed:
-//   rbs_handle.h   struct rbs_handle, Rccl, fmt / fail / upload, RBS_HIP, RBS_REFUSE_POISONED, with_flags
-//   rbs_call.h     the likelihood call: occlusion_coeffs, launch_prep, launch_raster, launch_bgp_step, stp_decide, enqueue_loglikes
-//   rbs_ipc.h      IpcBlob, rbs_ipc_export, rbs_ipc_attach, rbs_stage_windows, rbs_peer_resample
-// This file, in order: frame ingest, (rbs_call.h), plane housekeeping, (rbsensor_assess.hip, rbsensor_contour.hip), release / create_impl, several
-// devices, the extern "C" sensor entry points (rbs_ipc.h among them), the device tracker's API.
+// One translation unit.  Most of the host side has files of its own, included below where they are needed:
+//   rbs_handle.h       struct rbs_handle, Rccl, fmt / fail / upload, RBS_HIP, RBS_REFUSE_POISONED, with_flags
+//   rbs_frames.h       frame ingest: obs_frame, convert_f64_f32*, BorrowedFrameGuard, upload_frame, hand_over_*, make_current, frame_abandon
+//   rbs_call.h         the likelihood call: occlusion_coeffs, launch_prep, launch_raster, launch_bgp_step, stp_decide, enqueue_loglikes
+//   rbs_planes.h       the occlusion planes' storage: materialize, slab_expand / exact_expand, store_plane, fit_or_grow, grow_slabs, drain
+//   rbs_planes_api.h   the slot entry points: rbs_get_occlusion .. rbs_import_window, rbs_stream_join, rbs_get_window
+//   rbs_ipc.h          IpcBlob, rbs_ipc_export, rbs_ipc_attach, rbs_stage_windows, rbs_peer_resample
+//   rbs_tracker_api.h  the device tracker's host side: struct rbs_tracker, launch_*, rbs_tracker_*
+// This file itself: release / create_impl, several devices, and the remaining extern "C" sensor entry points.
 #include "rbsensor_kernels.hip"
 #include "rbsensor_tracker.hip"
 #include "rbsensor_peers.hip"
@@ -24,9 +27,6 @@
 
 #include <dlfcn.h>
 #include <unistd.h>
-#if defined(__x86_64__)
-#include <immintrin.h>   // (the frame's double -> float staging: AVX2 / AVX-512 where the host has them; other hosts take the scalar loop)
-#endif
 
 #include <cmath>
 #include <cstdarg>
@@ -45,615 +45,13 @@
 
 #include "rbs_handle.h"
 
-namespace {
-
-// ----------------------------------------------------------------------------- the frame section (rbs_handle::fr)
-// A hand-over: frame_begin, the entry point's own checks, frame_ready, one hand_over_*.  A reader: make_current (or, in
-// enqueue_loglikes, its pieces), then obs_frame / obs_aux.
-using NextFrame = rbs_handle::NextFrame;
-
-// What the kernels read: the staging image of slot fr.cur (F64: with its model terms), or d_frame / d_aux.
-const float* obs_frame(const rbs_handle* h) { return h->fr.cur >= 0 ? h->d_fin[h->fr.cur] : h->d_frame; }
-const double* obs_aux(const rbs_handle* h) { return h->fr.cur >= 0 ? h->d_aux_slot[h->fr.cur] : h->d_aux; }
-float* staging(const rbs_handle* h) { return h->h_frames[h->fr.stage]; }
-
-// Can borrow: only a handle that stages a frame between the two kernels of the split launch takes one without copying it at
-// once (one device, binary64 likelihood, windowed planes).
-bool can_borrow(const rbs_handle* h)
-{
-    return h->shards.empty() && !h->group && h->precision == RBS_PRECISION_F64 && h->windowed;
-}
-
-// The pending device frame if its ingest is to run on stream s, taken: the caller launches that ingest (enqueue_loglikes: on
-// the rectangles kernel's launch).  nullptr otherwise.
-const float* take_device_frame(rbs_handle* h, hipStream_t s)
-{
-    if (h->fr.next.kind != NextFrame::DEVICE || h->fr.next.stream != s) return nullptr;
-    const float* f = static_cast<const float*>(h->fr.next.src);
-    h->fr.next = {};
-    return f;
-}
-
-// Launch the ingest of a device frame left pending, on the stream it was given for; `then` (if not that stream) is ordered
-// after it.
-int32_t flush_device_frame(rbs_handle* h, hipStream_t then)
-{
-    if (h->fr.next.kind != NextFrame::DEVICE) return RBS_OK;
-    const hipStream_t fs = h->fr.next.stream;
-    const float* f = take_device_frame(h, fs);
-    const size_t n = (size_t)h->npx;
-    // (precision F32 keeps no per-pixel terms: a frame already in the handle's buffer needs nothing)
-    if (h->d_aux || f != h->d_frame)
-    hipLaunchKernelGGL(rbs::frame_aux_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, fs,
-                       f, h->d_aux, h->d_pbg, h->npx, h->base.tw, h->base.ms, h->base.sf,
-                       h->base.lambda, f == h->d_frame ? (float*)nullptr : h->d_frame);
-    RBS_HIP(h, hipGetLastError());
-    if (then != fs) {
-        RBS_HIP(h, hipEventRecord(h->ev_fork, fs));
-        RBS_HIP(h, hipStreamWaitEvent(then, h->ev_fork, 0));
-    }
-    return RBS_OK;
-}
-
-// A device frame pending on a caller's stream is ingested there, into d_frame: that stream first waits for the readers
-// enqueued on the handle's stream so far.
-int32_t device_frame_after_readers(rbs_handle* h)
-{
-    if (h->fr.next.kind != NextFrame::DEVICE || h->fr.next.stream == h->stream) return RBS_OK;
-    RBS_HIP(h, hipEventRecord(h->ev_reader, h->stream));
-    RBS_HIP(h, hipStreamWaitEvent(h->fr.next.stream, h->ev_reader, 0));
-    return RBS_OK;
-}
-
-// Read done: frame N + 2's upload into the observation's staging image waits for the readers enqueued on s so far.
-int32_t frame_read_done(rbs_handle* h, hipStream_t s)
-{
-    if (h->fr.cur >= 0) RBS_HIP(h, hipEventRecord(h->ev_used[h->fr.cur], s));
-    return RBS_OK;
-}
-
-// Stream s waits for the upload of the observation's staging image (nothing to wait for on d_frame).
-int32_t wait_for_upload(rbs_handle* h, hipStream_t s)
-{
-    if (h->fr.cur >= 0) RBS_HIP(h, hipStreamWaitEvent(s, h->ev_frame[h->fr.cur], 0));
-    return RBS_OK;
-}
-
-// The staging image that served as the observation stops doing so (a new frame is coming): it may
-// be overwritten once everything launched so far has run.
-int32_t release_frame_slot(rbs_handle* h)
-{
-    if (int32_t rc = frame_read_done(h, h->stream)) return rc;
-    h->fr.cur = -1;
-    return RBS_OK;
-}
-
-// H2D of a frame staged in pinned host memory (`src`, normally staging(h)) on the upload stream into
-// the device staging buffer of the current slot, which then IS the observation; the raster kernel
-// waits for the upload (wait_for_upload).
-// `pageable`: the caller's own frame, still to be staged into `src` (= staging(h)) -- staged and sent
-// in h->upload_chunks pieces, so that the copy engine carries one piece while the host copies the next
-// (a 640x480 frame: 41 us of memcpy + 29 us of transfer one after the other, ~20 us less interleaved).
-// dbot hands the image over as a vector of DOUBLES (R:source/dbot_ros/util/ros_interface.h:152-168): double -> float while
-// staging.  The scalar loop converts 2 values per instruction on a baseline x86-64 build; AVX2 (every host this library
-// meets; checked at run time) does 4 per instruction and halves the time of a 640x480 frame.
-#if defined(__x86_64__)
-__attribute__((target("avx2"))) static void convert_f64_f32_avx2(float* __restrict__ dst, const double* __restrict__ src, size_t n)
-{
-    size_t p = 0;
-    for (; p + 8 <= n; p += 8) {
-        const __m128 a = _mm256_cvtpd_ps(_mm256_loadu_pd(src + p)), b = _mm256_cvtpd_ps(_mm256_loadu_pd(src + p + 4));
-        _mm256_storeu_ps(dst + p, _mm256_set_m128(b, a));
-    }
-    for (; p < n; ++p) dst[p] = (float)src[p];
-}
-// AVX-512 hosts: 8 values per instruction and streaming stores (the staging image is read next by the copy engine, not by
-// this core: no line of it needs to be fetched to be overwritten) -- 42 us against 50 per 640x480 frame out of L3 (EPYC 9575F,
-// tools/dbg/convert_bench.cpp); the plugin path gains ~1 %
-__attribute__((target("avx512f"))) static void convert_f64_f32_avx512(float* __restrict__ dst, const double* __restrict__ src, size_t n)
-{
-    size_t p = 0;
-    for (; p + 16 <= n; p += 16) {
-        const __m256 a = _mm512_cvtpd_ps(_mm512_loadu_pd(src + p)), b = _mm512_cvtpd_ps(_mm512_loadu_pd(src + p + 8));
-        _mm512_stream_ps(dst + p, _mm512_castpd_ps(_mm512_insertf64x4(_mm512_castpd256_pd512(_mm256_castps_pd(a)), _mm256_castps_pd(b), 1)));
-    }
-    _mm_sfence();
-    for (; p < n; ++p) dst[p] = (float)src[p];
-}
-#endif
-static void convert_f64_f32(float* __restrict__ dst, const double* __restrict__ src, size_t n)
-{
-#if defined(__x86_64__)
-    static const bool avx512 = __builtin_cpu_supports("avx512f") && !std::getenv("RBS_NO_AVX512");
-    if (avx512 && (reinterpret_cast<uintptr_t>(dst) & 63) == 0) return convert_f64_f32_avx512(dst, src, n);
-    static const bool avx2 = __builtin_cpu_supports("avx2");
-    if (avx2) return convert_f64_f32_avx2(dst, src, n);
-#endif
-    for (size_t p = 0; p < n; ++p) dst[p] = (float)src[p];
-}
-
-// Precision F64: the per-pixel model terms of the frame in d_fin[k], computed right behind its copy, on the upload stream,
-// into the slot's own table -- the launch stream does not wait for the frame until the raster kernel needs it, so a caller's
-// transition and the rectangles kernel run while the frame is still travelling (a tracker frame: 35 us of 400).
-int32_t slot_aux(rbs_handle* h, int k)
-{
-    if (!h->d_aux) return RBS_OK;
-    hipLaunchKernelGGL(rbs::frame_aux_kernel, dim3((unsigned)((h->npx + 255) / 256)), dim3(256), 0, h->up_stream,
-                       h->d_fin[k], h->d_aux_slot[k], h->d_pbg, h->npx, h->base.tw, h->base.ms, h->base.sf, h->base.lambda, (float*)nullptr);
-    RBS_HIP(h, hipGetLastError());
-    return RBS_OK;
-}
-
-int32_t upload_frame(rbs_handle* h, const float* src, const float* pageable = nullptr, const double* pageable_f64 = nullptr)
-{
-    const int k = h->fr.stage;
-    const size_t n = (size_t)h->npx;
-    h->fr.next = {};   // (a frame uploaded ahead, or borrowed and never evaluated, is abandoned; a device frame: flushed first)
-    // (the two staging images alternate, so k is never the image that serves as the observation --
-    // should it be, its readers are recorded first: the wait below must not be on a stale event)
-    if (k == h->fr.cur)
-        if (int32_t rc = release_frame_slot(h)) return rc;
-    RBS_HIP(h, hipStreamWaitEvent(h->up_stream, h->ev_used[k], 0));   // d_fin[k]: its readers were enqueued two frames ago
-    // A SMALL frame (the reference's default operating point is 80x60: 19 KB) is not worth a transfer: a copy-engine
-    // job costs ~11 us before it moves a byte and ~9 more until a kernel behind it starts.  The kernel that computes
-    // the frame's model terms reads it where the host staged it (this handle's pinned buffer, over PCIe) and leaves
-    // the observation in d_fin[k] as it goes (precision F32: that copy is all it does).
-    const bool pull = n * sizeof(float) <= h->frame_pull_bytes && h->h_frames_dev[k] &&
-                      (pageable || pageable_f64 || src == h->h_frames[k]);
-    if (pageable || pageable_f64) {
-        float* stage = h->h_frames[k];
-        // (a frame of doubles takes the host ~4x as long to stage as a frame of floats: twice the pieces)
-        const size_t want = (size_t)h->upload_chunks * (pageable_f64 && h->upload_chunks > 1 ? 2 : 1);
-        const int pieces = h->quiet ? (int)std::max<size_t>(1, std::min<size_t>(want, n / 16384)) : 1;
-        const size_t per = ((n + pieces - 1) / pieces + 1023) / 1024 * 1024;
-        for (size_t off = 0; off < n; off += per) {
-            const size_t len = std::min(per, n - off);
-            if (pageable) std::memcpy(stage + off, pageable + off, len * sizeof(float));
-            else convert_f64_f32(stage + off, pageable_f64 + off, len);   // dbot hands a vector of doubles
-            if (!pull) RBS_HIP(h, hipMemcpyAsync(h->d_fin[k] + off, stage + off, len * sizeof(float), hipMemcpyHostToDevice, h->up_stream));
-        }
-    } else if (!pull) {
-        RBS_HIP(h, hipMemcpyAsync(h->d_fin[k], src, n * sizeof(float), hipMemcpyHostToDevice, h->up_stream));
-    }
-    if (pull) {
-        hipLaunchKernelGGL(rbs::frame_aux_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->up_stream,
-                           h->h_frames_dev[k], h->d_aux ? h->d_aux_slot[k] : (double*)nullptr, h->d_pbg, h->npx, h->base.tw,
-                           h->base.ms, h->base.sf, h->base.lambda, h->d_fin[k]);
-        RBS_HIP(h, hipGetLastError());
-    } else if (int32_t rc = slot_aux(h, k)) {
-        return rc;
-    }
-    RBS_HIP(h, hipEventRecord(h->ev_frame[k], h->up_stream));
-    if (int32_t rc = release_frame_slot(h)) return rc;
-    h->fr.cur = k;   // (and, F64, its slot's table the model terms) until the next frame replaces it
-    return RBS_OK;
-}
-
-// The pinned frame buffer the next host frame is staged in: the other one of the two, once the
-// upload that last used it has finished (two frames ago: in practice never a wait).
-int32_t next_frame_staging(rbs_handle* h)
-{
-    h->fr.stage ^= 1;
-    RBS_HIP(h, hipEventSynchronize(h->ev_frame[h->fr.stage]));
-    return RBS_OK;
-}
-
-// rbs_set_observation_borrowed's frame becomes the observation now: staged (double -> float) into pinned memory and sent.
-int32_t stage_borrowed(rbs_handle* h)
-{
-    const NextFrame b = h->fr.next;
-    if (!b.borrowed()) return RBS_OK;
-    h->fr.next = {};
-    if (int32_t rc = next_frame_staging(h)) return rc;
-    if (b.kind == NextFrame::BORROWED_F64) return upload_frame(h, staging(h), nullptr, static_cast<const double*>(b.src));
-    return upload_frame(h, staging(h), static_cast<const float*>(b.src));
-}
-
-// A borrowed frame is the caller's memory until the likelihood call behind it RETURNS -- however it returns.  A call that is
-// refused or fails before its kernels staged the frame must not leave the pointer behind for a later call to read: on the way
-// out the frame is copied after all (it becomes the observation, as rbs_set_observation would have made it), or dropped where
-// the handle takes no more work.
-struct BorrowedFrameGuard {
-    rbs_handle* h;
-    ~BorrowedFrameGuard()
-    {
-        if (!h->fr.next.borrowed()) return;
-        if (h->poisoned || hipSetDevice(h->device) != hipSuccess) { h->fr.next = {}; return; }
-        const std::string keep = h->err;      // (the message of the failure that brought us here stays rbs_last_error's)
-        const int32_t rc = stage_borrowed(h);   // (whatever it returns, the frame is no longer the handle's)
-        if (rc == RBS_OK) h->err = keep;
-    }
-};
-
-// The NEXT frame, uploaded while the current one is still the observation (rbs_loglikes_prefetch: called between
-// the launch of a call's kernels and the wait for its results, so the host's staging copy and the transfer pass
-// behind the raster kernel): staged into the other pinned image, sent on the upload stream, its model terms
-// (precision F64) computed behind it -- everything upload_frame does except making it the observation.
-// What rbs_loglikes_prefetch needs, checked BEFORE the call's kernels are enqueued (a prefetch that failed
-// behind an updating call left the caller with a failed call whose planes had already flipped).
-int32_t prefetch_check(rbs_handle* h)
-{
-    if (h->fr.next.kind == NextFrame::AHEAD)
-        return fail(h, RBS_ERR_INVALID_ARGUMENT, "loglikes_prefetch: the frame uploaded ahead by the previous rbs_loglikes_prefetch has not been "
-                                                 "installed yet (rbs_set_observation_prefetched)");
-    if ((h->fr.stage ^ 1) == h->fr.cur)
-        return fail(h, RBS_ERR_INVALID_ARGUMENT, "loglikes_prefetch: the staging image the next frame would use is the current observation "
-                                                 "(the staging images did not alternate)");
-    return RBS_OK;
-}
-
-int32_t prefetch_frame(rbs_handle* h, const float* depth)
-{
-    if (int32_t rc = prefetch_check(h)) return rc;   // (before the staging image is switched: a refused call changes nothing)
-    if (int32_t rc = next_frame_staging(h)) return rc;
-    const int k = h->fr.stage;
-    const size_t n = (size_t)h->npx;
-    RBS_HIP(h, hipStreamWaitEvent(h->up_stream, h->ev_used[k], 0));   // d_fin[k]: its readers were enqueued two frames ago
-    std::memcpy(h->h_frames[k], depth, n * sizeof(float));
-    RBS_HIP(h, hipMemcpyAsync(h->d_fin[k], h->h_frames[k], n * sizeof(float), hipMemcpyHostToDevice, h->up_stream));
-    if (int32_t rc = slot_aux(h, k)) return rc;
-    RBS_HIP(h, hipEventRecord(h->ev_frame[k], h->up_stream));
-    h->fr.next = {NextFrame::AHEAD, nullptr, nullptr, k};
-    return RBS_OK;
-}
-
-
-// Make current: the observation complete in stream s's order -- a borrowed frame staged, a device frame ingested, the upload
-// of a host frame waited for.
-int32_t make_current(rbs_handle* h, hipStream_t s)
-{
-    if (int32_t rc = stage_borrowed(h)) return rc;
-    if (int32_t rc = flush_device_frame(h, s)) return rc;
-    return wait_for_upload(h, s);
-}
-
-// Begin, the prologue of every hand-over: a handle left undefined by a failed call is refused, and a buffer acquired but never
-// committed is abandoned.  Then, once the entry point has checked its frame, frame_ready: on the handle's device, a device
-// frame handed over before and never evaluated is ingested (its clock tick stays counted), ordered before stream s.
-int32_t frame_begin(rbs_handle* h)
-{
-    RBS_REFUSE_POISONED(h);
-    h->fr.acquired = false;
-    return RBS_OK;
-}
-int32_t frame_ready(rbs_handle* h, hipStream_t s)
-{
-    RBS_HIP(h, hipSetDevice(h->device));
-    return flush_device_frame(h, s);
-}
-
-// Hand over: the frame becomes the observation -- a borrowed or device frame at the next call that needs it -- whatever waited
-// in fr.next is abandoned, and the model clock advances one frame.
-// ... the caller's host frame (floats or doubles), copied now
-int32_t hand_over_host(rbs_handle* h, const float* f32, const double* f64)
-{
-    if (int32_t rc = next_frame_staging(h)) return rc;
-    if (int32_t rc = upload_frame(h, staging(h), f32, f64)) return rc;   // (staged and sent piece by piece)
-    h->pending_frames += 1;
-    return RBS_OK;
-}
-// ... a frame in pinned memory: the committed buffer (a group's: shard 0's, sent to every shard)
-int32_t hand_over_pinned(rbs_handle* h, const float* src)
-{
-    if (int32_t rc = upload_frame(h, src)) return rc;
-    h->pending_frames += 1;
-    return RBS_OK;
-}
-// ... the driver's full-resolution frame, sub-sampled by f.
-// The reference's rule (R:source/dbot_ros/util/ros_interface.h:152-168): evaluated(r, c) =
-// native(r f, c f) -- applied while the frame is staged, so that only the rows*cols values the
-// sensor evaluates are copied and sent (1/f^2 of the driver's frame: 19 KB of 1.2 MB at the
-// reference's default factor 8) and the frame then travels like any other host frame.
-int32_t hand_over_native(rbs_handle* h, const float* native, int width, int f)
-{
-    if (int32_t rc = next_frame_staging(h)) return rc;
-    for (int r = 0; r < h->rows; ++r) {
-        const float* src = native + (size_t)r * f * width;
-        float* dst = staging(h) + (size_t)r * h->cols;
-        for (int c = 0; c < h->cols; ++c) dst[c] = src[(size_t)c * f];
-    }
-    return hand_over_pinned(h, staging(h));
-}
-// ... the caller's host frame, borrowed (can_borrow): a borrowed frame nobody evaluated is simply replaced
-void hand_over_borrowed(rbs_handle* h, const float* f32, const double* f64)
-{
-    h->fr.next = f64 ? NextFrame{NextFrame::BORROWED_F64, f64} : NextFrame{NextFrame::BORROWED_F32, f32};
-    h->pending_frames += 1;
-}
-// ... a frame in device memory, ingested on stream s by whatever needs it first
-int32_t hand_over_device(rbs_handle* h, const float* d_depth, hipStream_t s)
-{
-    if (int32_t rc = release_frame_slot(h)) return rc;
-    h->fr.next = {NextFrame::DEVICE, d_depth, s};
-    h->pending_frames += 1;
-    return RBS_OK;
-}
-// ... the frame uploaded ahead (fr.next is AHEAD)
-int32_t hand_over_ahead(rbs_handle* h)
-{
-    const int k = h->fr.next.slot;
-    h->fr.next = {};
-    if (int32_t rc = release_frame_slot(h)) return rc;   // the readers of the frame it replaces are on the launch stream by now
-    h->fr.cur = k;
-    h->pending_frames += 1;
-    return RBS_OK;
-}
-
-// The pinned image the caller writes the next frame into (rbs_acquire_frame_buffer).  One image (shard 0's) feeds every device
-// of a group: it is free once every shard's upload of the frame before last has finished.
-int32_t acquire_staging(rbs_handle* h, float** buf)
-{
-    rbs_handle* const s0 = h->shards.empty() ? h : h->shards[0];
-    const int k = s0->fr.stage ^ 1;
-    for (size_t i = 0; i < std::max<size_t>(1, h->shards.size()); ++i) {
-        rbs_handle* sh = h->shards.empty() ? h : h->shards[i];
-        RBS_HIP(h, hipSetDevice(sh->device));
-        sh->fr.stage = k;
-        RBS_HIP(h, hipEventSynchronize(sh->ev_frame[k]));
-    }
-    *buf = staging(s0);
-    h->fr.acquired = true;
-    return RBS_OK;
-}
-
-// rbs_reset: an acquired buffer, a borrowed frame and a frame uploaded ahead belong to the session that ended (a device frame
-// has been ingested by the drain before).
-void frame_abandon(rbs_handle* h)
-{
-    h->fr.acquired = false;
-    h->fr.next = {};
-}
-
-}  // namespace
+// Frame ingest: obs_frame .. frame_abandon.
+#include "rbs_frames.h"
 
 #include "rbs_call.h"
 
-namespace {
-
-// Windowed planes: make slot's current plane dense in place (background outside its window) and
-// mark its window full, on stream s.  Dense planes: nothing to do.
-int32_t materialize(rbs_handle* h, int slot, hipStream_t s)
-{
-    if (!h->windowed) return RBS_OK;
-    if (h->exact) return fail(h, RBS_ERR_UNSUPPORTED, "a slot of stamped planes (occlusion_mode REFERENCE) is not a float plane: use rbs_export_plane / rbs_get_occlusion");
-    if (h->slab_px) return fail(h, RBS_ERR_UNSUPPORTED, "a slab cannot be made dense in place (state_slab_px)");
-    hipLaunchKernelGGL(rbs::rbs_materialize_kernel, dim3((unsigned)((h->npx + 255) / 256)), dim3(256), 0, s,
-                       h->d_occ[h->cur] + (size_t)slot * h->plane_stride, h->d_win[h->cur] + slot, h->rows, h->cols,
-                       h->background, h->stp ? (const float*)h->d_bgp[h->cur] : (const float*)nullptr);
-    RBS_HIP(h, hipGetLastError());
-    hipLaunchKernelGGL(rbs::rbs_set_window_kernel, dim3(1), dim3(64), 0, s, h->d_win[h->cur] + slot, 1,
-                       make_int4(0, 0, h->cols, h->rows));
-    RBS_HIP(h, hipGetLastError());
-    return RBS_OK;
-}
-
-// Slabs: a slot's plane as a whole plane in `d_full` (device, npx floats), on stream s.
-int32_t slab_expand(rbs_handle* h, int slot, float* d_full, hipStream_t s)
-{
-    hipLaunchKernelGGL(rbs::rbs_expand_kernel, dim3((unsigned)((h->npx + 255) / 256)), dim3(256), 0, s,
-                       h->d_occ[h->cur] + (size_t)slot * h->plane_stride, h->d_reg[h->cur] + slot, h->d_win[h->cur] + slot,
-                       h->rows, h->cols, h->background, d_full, h->stp ? (const float*)h->d_bgp[h->cur] : (const float*)nullptr);
-    RBS_HIP(h, hipGetLastError());
-    return RBS_OK;
-}
-
-// Slab size that holds a region of `need` px with room to move.
-// (1.5 x: a slab enlarged for `need` is at most two thirds full, below the three quarters that trigger the next
-// enlargement -- with 1.25 x the trigger stayed true after growing and every synchronising call drained the handle: ADVICE r3)
-int slab_for(const rbs_handle* h, int need) { return (int)std::min<long>(h->npx, (long)need + need / 2 + 1024); }
-
-// Slabs: store a whole plane (device, npx floats) into a slot: its stored region and window become
-// the float4-aligned bounding box of the values that differ from the background.  Synchronises
-// (the box is needed on the host to check that it fits).
-int32_t drain(rbs_handle* h, bool host_sync);
-int32_t grow_slabs(rbs_handle* h, int new_slab);
-int32_t slab_store(rbs_handle* h, int slot, const float* d_full, hipStream_t s)
-{
-    const int init[4] = {h->cols, h->rows, 0, 0};
-    RBS_HIP(h, hipMemcpyAsync(h->d_bbox, init, sizeof(init), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(rbs::rbs_bbox_kernel, dim3((unsigned)((h->npx + 255) / 256)), dim3(256), 0, s, d_full, h->rows,
-                       h->cols, h->background, h->d_bbox, h->stp ? (const float*)h->d_bgp[h->cur] : (const float*)nullptr);
-    RBS_HIP(h, hipGetLastError());
-    int box[4];
-    RBS_HIP(h, hipMemcpyAsync(box, h->d_bbox, sizeof(box), hipMemcpyDeviceToHost, s));
-    RBS_HIP(h, hipStreamSynchronize(s));
-    int4 r = make_int4(box[0], box[1], std::min(box[2], h->cols), box[3]);
-    if (r.z <= r.x || r.w <= r.y) r = make_int4(h->cols, h->rows, 0, 0);   // all background
-    const long area = r.z > r.x ? (long)(r.z - r.x) * (r.w - r.y) : 0;
-    if (area > (long)h->slab_px) {
-        // the slabs grow for a plane handed in from outside as they do for a region a call asks for -- on
-        // a handle of its own; the shards of a group and attached ranks must keep one size among them
-        if (h->group || h->peer_world > 1)
-            return fail(h, RBS_ERR_OUT_OF_MEMORY,
-                        fmt("a plane whose values differ from the background over %ld px does not fit a slab of %d px (state_slab_px)", area, h->slab_px));
-        if (int32_t rc = drain(h, true)) return rc;
-        if (int32_t rc = grow_slabs(h, slab_for(h, (int)std::min<long>(area, h->npx)))) return rc;
-        if (area > (long)h->slab_px)
-            return fail(h, RBS_ERR_OUT_OF_MEMORY, fmt("a plane of %ld px does not fit a slab of %d px (state_slab_px)", area, h->slab_px));
-    }
-    if (area > 0) {
-        hipLaunchKernelGGL(rbs::rbs_pack_kernel, dim3((unsigned)((area + 255) / 256)), dim3(256), 0, s, d_full, r, h->cols,
-                           h->d_occ[h->cur] + (size_t)slot * h->plane_stride);
-        RBS_HIP(h, hipGetLastError());
-    }
-    hipLaunchKernelGGL(rbs::rbs_set_window_kernel, dim3(1), dim3(64), 0, s, h->d_win[h->cur] + slot, 1, r);
-    hipLaunchKernelGGL(rbs::rbs_set_window_kernel, dim3(1), dim3(64), 0, s, h->d_reg[h->cur] + slot, 1, r);
-    RBS_HIP(h, hipGetLastError());
-    return RBS_OK;
-}
-
-int32_t drain(rbs_handle* h, bool host_sync);
-
-// Stamped planes (occlusion_mode REFERENCE): the hooks' two conversions.  A slot -> its plane of EFFECTIVE values as of the
-// epoch (device, npx floats); slot < 0: the shared background plane itself.
-int32_t exact_expand(rbs_handle* h, int slot, float* d_full, hipStream_t s)
-{
-    DevParams P = h->base;
-    P.ptab = h->d_ptab;
-    P.age_max = h->age_max;
-    const float* base = slot >= 0 ? h->d_occ[h->cur] + (size_t)slot * h->plane_stride : nullptr;
-    hipLaunchKernelGGL(rbs::rbs_expand_exact_kernel, dim3((unsigned)((h->npx + 255) / 256)), dim3(256), 0, s, base, h->slab_px ? h->slab_px : h->npx,
-                       slot >= 0 && h->slab_px ? (const int4*)(h->d_reg[h->cur] + slot) : (const int4*)nullptr,
-                       slot >= 0 ? (const int4*)(h->d_win[h->cur] + slot) : (const int4*)nullptr, h->rows, h->cols, h->background,
-                       h->stp ? (const float*)h->d_bgp[h->cur] : (const float*)nullptr, P, d_full);
-    RBS_HIP(h, hipGetLastError());
-    return RBS_OK;
-}
-// A plane of effective values handed in from outside -> a slot: the values as given with age 0 ("as of now", the rule of the
-// oracle's set_occlusion), stored over the bounding box of what differs from the background (the scalar level, or the shared
-// plane's effective values).  Synchronises (the box is needed on the host: slabs must fit it).
-int32_t exact_store(rbs_handle* h, int slot, const float* d_full, hipStream_t s)
-{
-    const float* bgref = nullptr;
-    if (h->stp) {
-        if (int32_t rc = exact_expand(h, -1, h->d_tmp_plane, s)) return rc;
-        bgref = h->d_tmp_plane;
-    }
-    const int init[4] = {h->cols, h->rows, 0, 0};
-    RBS_HIP(h, hipMemcpyAsync(h->d_bbox, init, sizeof(init), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(rbs::rbs_bbox_kernel, dim3((unsigned)((h->npx + 255) / 256)), dim3(256), 0, s, d_full, h->rows, h->cols, h->background, h->d_bbox, bgref);
-    RBS_HIP(h, hipGetLastError());
-    int box[4];
-    RBS_HIP(h, hipMemcpyAsync(box, h->d_bbox, sizeof(box), hipMemcpyDeviceToHost, s));
-    RBS_HIP(h, hipStreamSynchronize(s));
-    int4 r = make_int4(box[0], box[1], std::min(box[2], h->cols), box[3]);
-    if (r.z <= r.x || r.w <= r.y) r = make_int4(h->cols, h->rows, 0, 0);   // all background
-    const long area = r.z > r.x ? (long)(r.z - r.x) * (r.w - r.y) : 0;
-    if (h->slab_px && area > (long)h->slab_px) {
-        if (h->group || h->peer_world > 1)
-            return fail(h, RBS_ERR_OUT_OF_MEMORY,
-                        fmt("a plane whose values differ from the background over %ld px does not fit a slab of %d px (state_slab_px)", area, h->slab_px));
-        if (int32_t rc = drain(h, true)) return rc;
-        if (int32_t rc = grow_slabs(h, slab_for(h, (int)std::min<long>(area, h->npx)))) return rc;
-        if (area > (long)h->slab_px)
-            return fail(h, RBS_ERR_OUT_OF_MEMORY, fmt("a plane of %ld px does not fit a slab of %d px (state_slab_px)", area, h->slab_px));
-    }
-    if (area > 0) {
-        hipLaunchKernelGGL(rbs::rbs_pack_exact_kernel, dim3((unsigned)((area + 255) / 256)), dim3(256), 0, s, d_full, bgref, h->background, r, h->cols,
-                           h->slab_px ? r.x : 0, h->slab_px ? r.y : 0, h->slab_px ? r.z - r.x : h->cols,
-                           h->d_occ[h->cur] + (size_t)slot * h->plane_stride, h->slab_px ? h->slab_px : h->npx);
-        RBS_HIP(h, hipGetLastError());
-    }
-    hipLaunchKernelGGL(rbs::rbs_set_window_kernel, dim3(1), dim3(64), 0, s, h->d_win[h->cur] + slot, 1, r);
-    if (h->slab_px) hipLaunchKernelGGL(rbs::rbs_set_window_kernel, dim3(1), dim3(64), 0, s, h->d_reg[h->cur] + slot, 1, r);
-    RBS_HIP(h, hipGetLastError());
-    RBS_HIP(h, hipStreamSynchronize(s));
-    return RBS_OK;
-}
-
-// "A region did not fit its slab" (h_err[0], fetched by the synchronising entry points): the message
-// of the calls that cannot repair it themselves (asynchronous calls, the device tracker).
-int32_t check_slab_error(rbs_handle* h)
-{
-    if (!h->slab_px || !h->h_err[0]) return RBS_OK;
-    return fail(h, RBS_ERR_OUT_OF_MEMORY,
-                fmt("a particle's occlusion window (with its screen rectangle) exceeded the slab of %d px "
-                    "(rbs_config.state_slab_px) in a call that had already returned: its log-likelihood is NaN and its "
-                    "plane was reset to the background; the slabs have been enlarged for the calls that follow", h->slab_px));
-}
-
-// Every slot gets `new_slab` floats (> the current size).  A slot stores its region row-major from
-// its first float, so the planes move with one strided copy; the regions' tables stay as they are.
-// Only the CURRENT buffer holds state (the other one is written from scratch by the next updating
-// call).  The caller has drained the handle.
-// Bytes to ask hipMalloc for when `bytes` are needed for a plane buffer.  A buffer whose size has bit 31 set
-// (2-4 GiB, 6-8 GiB, ...) cannot be imported by another process on ROCm 7.2: hipIpcOpenMemHandle never
-// returns (measured, tools/dbg/ipc_attach_notorch.py: 13 900 x 38 400 px opens at once, 14 500 x 38 400 hangs,
-// 30 000 x 38 400 opens, 50 000 x 38 400 hangs).  Such sizes are rounded up to the next multiple of 4 GiB.
-size_t occ_alloc_bytes(size_t bytes)
-{
-    return (bytes & 0x80000000ull) ? ((bytes >> 32) + 1) << 32 : bytes;
-}
-
-int32_t grow_slabs(rbs_handle* h, int new_slab)
-{
-    new_slab = std::min(h->npx, (new_slab + 1023) & ~1023);
-    if (new_slab <= h->slab_px) return RBS_OK;
-    if (h->peer_world > 1)   // the other ranks address these slabs with a fixed stride through their mappings
-        return h->h_err[0] ? fail(h, RBS_ERR_OUT_OF_MEMORY,
-                                  fmt("a region of %d px does not fit the slab of %d px, and slabs cannot grow once the handle is "
-                                      "attached to other ranks (rbs_ipc_attach): create the handles with a larger state_slab_px",
-                                      h->h_err[1], h->slab_px))
-                           : RBS_OK;
-    float* nb[2] = {nullptr, nullptr};
-    const size_t new_stride = h->exact ? exact_stride((size_t)new_slab) : (size_t)new_slab;
-    const size_t bytes = sizeof(float) * new_stride * h->max_particles;
-    for (int k = 0; k < 2; ++k)
-        if (hipMalloc(&nb[k], occ_alloc_bytes(bytes)) != hipSuccess) {
-            (void)hipGetLastError();
-            (void)hipFree(nb[0]);
-            return fail(h, RBS_ERR_OUT_OF_MEMORY, fmt("enlarging the occlusion slabs from %d to %d px per slot needs 2 x %zu bytes more", h->slab_px, new_slab, bytes));
-        }
-    RBS_HIP(h, hipMemcpy2DAsync(nb[h->cur], sizeof(float) * new_stride, h->d_occ[h->cur], sizeof(float) * h->plane_stride,
-                                sizeof(float) * (size_t)h->slab_px, (size_t)h->max_particles, hipMemcpyDeviceToDevice, h->stream));
-    if (h->exact)   // ... and the slots' ages, which follow the values of a slot
-        RBS_HIP(h, hipMemcpy2DAsync(nb[h->cur] + new_slab, sizeof(float) * new_stride, h->d_occ[h->cur] + h->slab_px, sizeof(float) * h->plane_stride,
-                                    sizeof(unsigned short) * (size_t)h->slab_px, (size_t)h->max_particles, hipMemcpyDeviceToDevice, h->stream));
-    RBS_HIP(h, hipStreamSynchronize(h->stream));
-    (void)hipFree(h->d_occ[0]);
-    (void)hipFree(h->d_occ[1]);
-    h->d_occ[0] = nb[0];
-    h->d_occ[1] = nb[1];
-    h->slab_px = new_slab;
-    h->plane_stride = new_stride;
-    return RBS_OK;
-}
-
-// What a call must put back to be run again: an updating call only flips the buffers and moves the
-// background level on -- the planes it read are intact.
-// What a call that is taken back (a region did not fit its slab) must find as it was.  The shared trail's mode belongs to it:
-// the planes the repeated call reads are measured against whatever background -- shared plane or scalar -- the FIRST attempt
-// found, and an attempt that left the shared trail (or entered it, or re-based) has already switched the handle's view.
-struct CallState { int cur; int pending_frames; float background; bool stp; long stp_last_rebase, stp_rebases, stp_block_until; double area_frac; bool wide; long update_clock; };
-CallState save_call_state(const rbs_handle* h)
-{
-    return {h->cur, h->pending_frames, h->background, h->stp, h->stp_last_rebase, h->stp_rebases, h->stp_block_until, h->area_frac, h->wide, h->update_clock};
-}
-void restore_call_state(rbs_handle* h, const CallState& c)
-{
-    h->cur = c.cur; h->pending_frames = c.pending_frames; h->background = c.background; h->update_clock = c.update_clock;
-    h->stp = c.stp; h->stp_last_rebase = c.stp_last_rebase; h->stp_rebases = c.stp_rebases; h->stp_block_until = c.stp_block_until;
-    h->area_frac = c.area_frac; h->wide = c.wide;
-}
-
-// After a synchronising call on an idle handle: enlarge the slabs BEFORE a region fills one (the
-// regions move a few pixels per frame; three quarters full is the trigger).  Clears the flag.
-int32_t slab_housekeeping(rbs_handle* h)
-{
-    if (!h->slab_px) return RBS_OK;
-    const bool overflowed = h->h_err[0] != 0;
-    // drain (a host synchronisation of both streams) only when the slabs will really be reallocated: h_err[1] is a
-    // sticky maximum, and a slab that is already the whole frame, or large enough for it, has nothing to gain
-    const int target = (int)std::min<long>(h->npx, ((long)slab_for(h, h->h_err[1]) + 1023) & ~1023L);
-    const bool grow = (long)h->h_err[1] * 4 > (long)h->slab_px * 3 && target > h->slab_px && h->peer_world <= 1;
-    if (overflowed || grow) {
-        if (int32_t rc = drain(h, true)) return rc;
-        if (int32_t rc = grow_slabs(h, slab_for(h, h->h_err[1]))) return rc;
-    }
-    if (overflowed) {
-        RBS_HIP(h, hipMemsetAsync(h->d_err, 0, sizeof(int), h->stream));   // (the flag; the maximum stays)
-        h->h_err[0] = 0;
-    }
-    return RBS_OK;
-}
-
-// Make stream `s` (and the host, if sync) see the planes of the last updating call complete.
-int32_t drain(rbs_handle* h, bool host_sync)
-{
-    if (int32_t rc = flush_device_frame(h, h->stream)) return rc;
-    if (h->join_pending >= 0) {
-        RBS_HIP(h, hipStreamWaitEvent(h->stream, h->ev_join[h->join_pending], 0));
-        if (host_sync) RBS_HIP(h, hipEventSynchronize(h->ev_join[h->join_pending]));
-        h->join_pending = -1;
-    }
-    if (host_sync) {
-        RBS_HIP(h, hipStreamSynchronize(h->stream));
-        RBS_HIP(h, hipStreamSynchronize(h->copy_stream));
-    }
-    return RBS_OK;
-}
-
-}  // namespace
+// The occlusion planes' storage: materialize, slabs, stamped planes, grow_slabs, drain.
+#include "rbs_planes.h"
 
 // The pose assessor (rbs_assess_*): its kernels and host side (release and create_impl call into it).
 #include "rbsensor_assess.hip"
@@ -2069,262 +1467,8 @@ int32_t rbs_synchronize(rbs_handle* h)
     return rc;
 }
 
-int32_t rbs_get_occlusion(rbs_handle* h, int32_t slot, float* out)
-{
-    if (!h) return RBS_ERR_INVALID_ARGUMENT;
-    RBS_GROUP_SLOT(h, slot, rbs_get_occlusion(sh_, l_, out));
-    if (slot < 0 || slot >= h->max_particles || !out)
-        return fail(h, RBS_ERR_INVALID_ARGUMENT, fmt("get_occlusion: bad slot %d", slot));
-    RBS_HIP(h, hipSetDevice(h->device));
-    if (int32_t rc = drain(h, true)) return rc;
-    if (h->slab_px || h->exact) {
-        if (int32_t rc = h->exact ? exact_expand(h, slot, h->d_render, h->stream) : slab_expand(h, slot, h->d_render, h->stream)) return rc;
-        RBS_HIP(h, hipStreamSynchronize(h->stream));
-        RBS_HIP(h, hipMemcpy(out, h->d_render, sizeof(float) * h->npx, hipMemcpyDeviceToHost));
-        return RBS_OK;
-    }
-    if (int32_t rc = materialize(h, slot, h->stream)) return rc;
-    RBS_HIP(h, hipStreamSynchronize(h->stream));
-    RBS_HIP(h, hipMemcpy(out, h->d_occ[h->cur] + (size_t)slot * h->npx, sizeof(float) * h->npx,
-                         hipMemcpyDeviceToHost));
-    return RBS_OK;
-}
-
-int32_t rbs_set_occlusion(rbs_handle* h, int32_t slot, const float* plane)
-{
-    if (!h) return RBS_ERR_INVALID_ARGUMENT;
-    RBS_GROUP_SLOT(h, slot, rbs_set_occlusion(sh_, l_, plane));
-    if (slot < 0 || slot >= h->max_particles || !plane)
-        return fail(h, RBS_ERR_INVALID_ARGUMENT, fmt("set_occlusion: bad slot %d", slot));
-    RBS_HIP(h, hipSetDevice(h->device));
-    if (int32_t rc = drain(h, true)) return rc;
-    if (h->slab_px || h->exact) {
-        RBS_HIP(h, hipMemcpy(h->d_render, plane, sizeof(float) * h->npx, hipMemcpyHostToDevice));
-        return h->exact ? exact_store(h, slot, h->d_render, h->stream) : slab_store(h, slot, h->d_render, h->stream);
-    }
-    RBS_HIP(h, hipMemcpy(h->d_occ[h->cur] + (size_t)slot * h->npx, plane, sizeof(float) * h->npx,
-                         hipMemcpyHostToDevice));
-    if (h->windowed) {   // the whole plane is explicit now; the next updating call tightens it again
-        hipLaunchKernelGGL(rbs::rbs_set_window_kernel, dim3(1), dim3(64), 0, h->stream, h->d_win[h->cur] + slot,
-                           1, make_int4(0, 0, h->cols, h->rows));
-        RBS_HIP(h, hipGetLastError());
-        RBS_HIP(h, hipStreamSynchronize(h->stream));
-    }
-    return RBS_OK;
-}
-
-int32_t rbs_occlusion_device_ptr(rbs_handle* h, int32_t slot, void** out)
-{
-    if (!h) return RBS_ERR_INVALID_ARGUMENT;
-    RBS_GROUP_SLOT(h, slot, rbs_occlusion_device_ptr(sh_, l_, out));
-    if (slot < 0 || slot >= h->max_particles || !out)
-        return fail(h, RBS_ERR_INVALID_ARGUMENT, fmt("occlusion_device_ptr: bad slot %d", slot));
-    RBS_HIP(h, hipSetDevice(h->device));
-    if (h->exact) return fail(h, RBS_ERR_UNSUPPORTED, "occlusion_device_ptr: a slot of stamped planes (occlusion_mode REFERENCE) is not a float plane");
-    if (int32_t rc = drain(h, true)) return rc;   // planes complete before the caller touches them
-    if (int32_t rc = materialize(h, slot, h->stream)) return rc;   // and dense, whatever the caller does next
-    RBS_HIP(h, hipStreamSynchronize(h->stream));
-    *out = h->d_occ[h->cur] + (size_t)slot * h->npx;
-    return RBS_OK;
-}
-
-int32_t rbs_occlusion_next_device_ptr(rbs_handle* h, int32_t slot, void** out)
-{
-    if (!h) return RBS_ERR_INVALID_ARGUMENT;
-    RBS_GROUP_SLOT(h, slot, rbs_occlusion_next_device_ptr(sh_, l_, out));
-    if (slot < 0 || slot >= h->max_particles || !out)
-        return fail(h, RBS_ERR_INVALID_ARGUMENT, fmt("occlusion_next_device_ptr: bad slot %d", slot));
-    RBS_HIP(h, hipSetDevice(h->device));
-    if (h->slab_px) return fail(h, RBS_ERR_UNSUPPORTED, "occlusion_next_device_ptr: slots are slabs, not planes (state_slab_px)");
-    if (h->exact) return fail(h, RBS_ERR_UNSUPPORTED, "occlusion_next_device_ptr: a slot of stamped planes (occlusion_mode REFERENCE) is not a float plane");
-    if (int32_t rc = drain(h, true)) return rc;   // planes complete before the caller touches them
-    *out = h->d_occ[1 - h->cur] + (size_t)slot * h->npx;
-    return RBS_OK;
-}
-
-int32_t rbs_export_plane(rbs_handle* h, int32_t slot, void* d_dst, void* stream)
-{
-    if (!h) return RBS_ERR_INVALID_ARGUMENT;
-    RBS_GROUP_SLOT(h, slot, rbs_export_plane(sh_, l_, d_dst, stream));
-    if (slot < 0 || slot >= h->max_particles || !d_dst)
-        return fail(h, RBS_ERR_INVALID_ARGUMENT, fmt("export_plane: bad slot %d", slot));
-    RBS_HIP(h, hipSetDevice(h->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
-    if (h->join_pending >= 0) RBS_HIP(h, hipStreamWaitEvent(s, h->ev_join[h->join_pending], 0));
-    if (h->exact) return exact_expand(h, slot, static_cast<float*>(d_dst), s);
-    if (h->slab_px) return slab_expand(h, slot, static_cast<float*>(d_dst), s);
-    if (int32_t rc = materialize(h, slot, s)) return rc;
-    RBS_HIP(h, hipMemcpyAsync(d_dst, h->d_occ[h->cur] + (size_t)slot * h->npx, sizeof(float) * h->npx,
-                              hipMemcpyDeviceToDevice, s));
-    return RBS_OK;
-}
-
-int32_t rbs_import_plane(rbs_handle* h, int32_t slot, const void* d_src, void* stream)
-{
-    if (!h) return RBS_ERR_INVALID_ARGUMENT;
-    RBS_GROUP_SLOT(h, slot, rbs_import_plane(sh_, l_, d_src, stream));
-    if (slot < 0 || slot >= h->max_particles || !d_src)
-        return fail(h, RBS_ERR_INVALID_ARGUMENT, fmt("import_plane: bad slot %d", slot));
-    RBS_HIP(h, hipSetDevice(h->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
-    if (h->join_pending >= 0) RBS_HIP(h, hipStreamWaitEvent(s, h->ev_join[h->join_pending], 0));
-    if (h->exact) return exact_store(h, slot, static_cast<const float*>(d_src), s);   // (synchronises)
-    if (h->slab_px) return slab_store(h, slot, static_cast<const float*>(d_src), s);   // (synchronises: the box must fit)
-    RBS_HIP(h, hipMemcpyAsync(h->d_occ[h->cur] + (size_t)slot * h->npx, d_src, sizeof(float) * h->npx,
-                              hipMemcpyDeviceToDevice, s));
-    if (h->windowed) {
-        hipLaunchKernelGGL(rbs::rbs_set_window_kernel, dim3(1), dim3(64), 0, s, h->d_win[h->cur] + slot, 1,
-                           make_int4(0, 0, h->cols, h->rows));
-        RBS_HIP(h, hipGetLastError());
-    }
-    return RBS_OK;
-}
-
-int32_t rbs_stream_join(rbs_handle* h, void* stream)
-{
-    if (!h) return RBS_ERR_INVALID_ARGUMENT;
-    if (!h->shards.empty()) {
-        for (rbs_handle* sh_ : h->shards)
-            if (int32_t rc = rbs_stream_join(sh_, stream)) return gfail(h, sh_, rc);
-        return RBS_OK;
-    }
-    RBS_HIP(h, hipSetDevice(h->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
-    if (h->join_pending >= 0) RBS_HIP(h, hipStreamWaitEvent(s, h->ev_join[h->join_pending], 0));
-    return RBS_OK;
-}
-
-// A slot's window as the host needs it for the window-sized transport (one 16-byte read-back).
-static int32_t window_of(rbs_handle* h, int slot, hipStream_t s, int box[4])
-{
-    if (!h->windowed) { box[0] = 0; box[1] = 0; box[2] = h->cols; box[3] = h->rows; return RBS_OK; }
-    RBS_HIP(h, hipMemcpyAsync(box, h->d_win[h->cur] + slot, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
-    RBS_HIP(h, hipStreamSynchronize(s));
-    if (box[2] <= box[0] || box[3] <= box[1]) { box[0] = h->cols; box[1] = h->rows; box[2] = 0; box[3] = 0; }
-    return RBS_OK;
-}
-
-int32_t rbs_export_window(rbs_handle* h, int32_t slot, int32_t rect_out[4], void* d_payload, size_t capacity_floats, void* stream)
-{
-    if (!h) return RBS_ERR_INVALID_ARGUMENT;
-    RBS_GROUP_SLOT(h, slot, rbs_export_window(sh_, l_, rect_out, d_payload, capacity_floats, stream));
-    if (slot < 0 || slot >= h->max_particles || !rect_out)
-        return fail(h, RBS_ERR_INVALID_ARGUMENT, fmt("export_window: bad slot %d", slot));
-    RBS_HIP(h, hipSetDevice(h->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
-    if (h->join_pending >= 0) RBS_HIP(h, hipStreamWaitEvent(s, h->ev_join[h->join_pending], 0));
-    if (h->exact) {
-        // stamped planes travel as EFFECTIVE values (what the receiver's rbs_import_window takes "as of now"): the slot's plane is
-        // assembled beside the slots and its window cut out of it (shared trail: the whole plane, as below)
-        if (int32_t rc = exact_expand(h, slot, h->d_render, s)) return rc;
-        int box[4] = {0, 0, h->cols, h->rows};
-        if (!h->stp) if (int32_t rc = window_of(h, slot, s, box)) return rc;
-        for (int k = 0; k < 4; ++k) rect_out[k] = box[k];
-        const int w = box[2] - box[0], hh = box[3] - box[1];
-        if (w <= 0 || hh <= 0) return RBS_OK;
-        if ((size_t)w * (size_t)hh > capacity_floats || !d_payload)
-            return fail(h, RBS_ERR_INVALID_ARGUMENT, fmt("export_window: the window of slot %d holds %d x %d values, the buffer %zu", slot, w, hh, capacity_floats));
-        RBS_HIP(h, hipMemcpy2DAsync(d_payload, sizeof(float) * (size_t)w, h->d_render + (size_t)box[1] * h->cols + box[0], sizeof(float) * (size_t)h->cols,
-                                    sizeof(float) * (size_t)w, (size_t)hh, hipMemcpyDeviceToDevice, s));
-        return RBS_OK;
-    }
-    // (shared trail: outside its window the plane is the handle's background PLANE, which the receiver does not have -- the
-    // slot is made dense first and travels whole)
-    if (h->stp && h->slab_px) {   // (a slab cannot be made dense in place: the whole plane is assembled beside it and travels from there)
-        for (int k = 0; k < 4; ++k) rect_out[k] = k < 2 ? 0 : (k == 2 ? h->cols : h->rows);
-        if ((size_t)h->npx > capacity_floats || !d_payload)
-            return fail(h, RBS_ERR_INVALID_ARGUMENT, fmt("export_window: the plane of slot %d travels whole (%d values), the buffer holds %zu", slot, h->npx, capacity_floats));
-        return slab_expand(h, slot, static_cast<float*>(d_payload), s);
-    }
-    if (h->stp) if (int32_t rc = materialize(h, slot, s)) return rc;
-    int box[4];
-    if (int32_t rc = window_of(h, slot, s, box)) return rc;
-    for (int k = 0; k < 4; ++k) rect_out[k] = box[k];
-    const int w = box[2] - box[0], hh = box[3] - box[1];
-    if (w <= 0 || hh <= 0) return RBS_OK;   // all background: nothing to carry
-    if ((size_t)w * (size_t)hh > capacity_floats || !d_payload)
-        return fail(h, RBS_ERR_INVALID_ARGUMENT, fmt("export_window: the window of slot %d holds %d x %d values, the buffer %zu", slot, w, hh, capacity_floats));
-    // where the window's first value is stored, and the stored row length
-    const float* base = h->d_occ[h->cur] + (size_t)slot * h->plane_stride;
-    size_t src_pitch = sizeof(float) * (size_t)h->cols;
-    if (h->slab_px) {
-        int reg[4];
-        RBS_HIP(h, hipMemcpyAsync(reg, h->d_reg[h->cur] + slot, sizeof(reg), hipMemcpyDeviceToHost, s));
-        RBS_HIP(h, hipStreamSynchronize(s));
-        src_pitch = sizeof(float) * (size_t)(reg[2] - reg[0]);
-        base += (size_t)(box[1] - reg[1]) * (size_t)(reg[2] - reg[0]) + (size_t)(box[0] - reg[0]);
-    } else {
-        base += (size_t)box[1] * h->cols + box[0];
-    }
-    RBS_HIP(h, hipMemcpy2DAsync(d_payload, sizeof(float) * (size_t)w, base, src_pitch, sizeof(float) * (size_t)w, (size_t)hh,
-                                hipMemcpyDeviceToDevice, s));
-    return RBS_OK;
-}
-
-int32_t rbs_import_window(rbs_handle* h, int32_t slot, const int32_t rect[4], const void* d_payload, void* stream)
-{
-    if (!h) return RBS_ERR_INVALID_ARGUMENT;
-    RBS_GROUP_SLOT(h, slot, rbs_import_window(sh_, l_, rect, d_payload, stream));
-    if (slot < 0 || slot >= h->max_particles || !rect)
-        return fail(h, RBS_ERR_INVALID_ARGUMENT, fmt("import_window: bad slot %d", slot));
-    RBS_HIP(h, hipSetDevice(h->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
-    if (h->join_pending >= 0) RBS_HIP(h, hipStreamWaitEvent(s, h->ev_join[h->join_pending], 0));
-    int4 r = make_int4(rect[0], rect[1], rect[2], rect[3]);
-    const bool empty = r.z <= r.x || r.w <= r.y;
-    if (empty) r = make_int4(h->cols, h->rows, 0, 0);
-    else if (r.x < 0 || r.y < 0 || r.z > h->cols || r.w > h->rows || (h->windowed && ((r.x | r.z) & 3)) || !d_payload)
-        return fail(h, RBS_ERR_INVALID_ARGUMENT, fmt("import_window: bad rectangle (%d, %d, %d, %d)", rect[0], rect[1], rect[2], rect[3]));
-    const int w = r.z - r.x, hh = r.w - r.y;
-    float* dst = h->d_occ[h->cur] + (size_t)slot * h->plane_stride;
-    if ((h->stp && h->slab_px) || h->exact) {
-        // the sender's plane = its scalar background outside rect: assembled whole beside the slabs, stored like any plane handed in
-        hipLaunchKernelGGL(rbs::rbs_fill_kernel, dim3(256), dim3(256), 0, s, h->d_render, (size_t)h->npx, h->background);
-        RBS_HIP(h, hipGetLastError());
-        if (!empty)
-            RBS_HIP(h, hipMemcpy2DAsync(h->d_render + (size_t)r.y * h->cols + r.x, sizeof(float) * (size_t)h->cols, d_payload, sizeof(float) * (size_t)w,
-                                        sizeof(float) * (size_t)w, (size_t)hh, hipMemcpyDeviceToDevice, s));
-        return h->exact ? exact_store(h, slot, h->d_render, s) : slab_store(h, slot, h->d_render, s);
-    }
-    if (!h->windowed || h->stp) {
-        // whole planes without windows (or a handle whose implicit background is a plane of its own): the sender's scalar
-        // background has to be written out
-        hipLaunchKernelGGL(rbs::rbs_fill_kernel, dim3(256), dim3(256), 0, s, dst, (size_t)h->npx, h->background);
-        RBS_HIP(h, hipGetLastError());
-        if (!empty)
-            RBS_HIP(h, hipMemcpy2DAsync(dst + (size_t)r.y * h->cols + r.x, sizeof(float) * (size_t)h->cols, d_payload, sizeof(float) * (size_t)w,
-                                        sizeof(float) * (size_t)w, (size_t)hh, hipMemcpyDeviceToDevice, s));
-        if (h->stp) {
-            hipLaunchKernelGGL(rbs::rbs_set_window_kernel, dim3(1), dim3(64), 0, s, h->d_win[h->cur] + slot, 1, make_int4(0, 0, h->cols, h->rows));
-            RBS_HIP(h, hipGetLastError());
-        }
-        return RBS_OK;
-    }
-    if (h->slab_px) {
-        if (!empty && (long)w * hh > (long)h->slab_px) {
-            // a window handed in from a handle whose slabs have already grown (every rank enlarges its slabs on its own
-            // schedule: ADVICE r4): the slabs grow here as they do behind rbs_import_plane / rbs_set_occlusion (slab_store)
-            // -- on a handle of its own; the shards of a group and attached ranks keep one size among them
-            if (h->group || h->peer_world > 1)
-                return fail(h, RBS_ERR_OUT_OF_MEMORY, fmt("import_window: a window of %d x %d values does not fit a slab of %d px (state_slab_px)", w, hh, h->slab_px));
-            if (int32_t rc = drain(h, true)) return rc;
-            RBS_HIP(h, hipStreamSynchronize(s));   // (earlier imports on the caller's stream wrote into the buffers about to be replaced)
-            if (int32_t rc = grow_slabs(h, slab_for(h, (int)std::min<long>((long)w * hh, h->npx)))) return rc;
-            if ((long)w * hh > (long)h->slab_px)
-                return fail(h, RBS_ERR_OUT_OF_MEMORY, fmt("import_window: a window of %d x %d values does not fit a slab of %d px (state_slab_px)", w, hh, h->slab_px));
-            dst = h->d_occ[h->cur] + (size_t)slot * h->plane_stride;
-        }
-        if (!empty)   // the slot's stored region becomes the window itself, packed
-            RBS_HIP(h, hipMemcpyAsync(dst, d_payload, sizeof(float) * (size_t)w * (size_t)hh, hipMemcpyDeviceToDevice, s));
-        hipLaunchKernelGGL(rbs::rbs_set_window_kernel, dim3(1), dim3(64), 0, s, h->d_reg[h->cur] + slot, 1, r);
-    } else if (!empty) {
-        RBS_HIP(h, hipMemcpy2DAsync(dst + (size_t)r.y * h->cols + r.x, sizeof(float) * (size_t)h->cols, d_payload, sizeof(float) * (size_t)w,
-                                    sizeof(float) * (size_t)w, (size_t)hh, hipMemcpyDeviceToDevice, s));
-    }
-    hipLaunchKernelGGL(rbs::rbs_set_window_kernel, dim3(1), dim3(64), 0, s, h->d_win[h->cur] + slot, 1, r);
-    RBS_HIP(h, hipGetLastError());
-    return RBS_OK;
-}
+// the occlusion planes' slot entry points: rbs_get_occlusion .. rbs_import_window, rbs_stream_join, rbs_get_window
+#include "rbs_planes_api.h"
 
 // one process per GPU: rbs_ipc_export, rbs_ipc_attach, rbs_stage_windows, rbs_peer_resample
 #include "rbs_ipc.h"
@@ -2435,18 +1579,6 @@ int32_t rbs_raster_kernel_ms(rbs_handle* h, int32_t last_n, float* raster_kernel
     return RBS_OK;
 }
 
-int32_t rbs_get_window(rbs_handle* h, int32_t slot, int32_t out[4])
-{
-    if (!h) return RBS_ERR_INVALID_ARGUMENT;
-    RBS_GROUP_SLOT(h, slot, rbs_get_window(sh_, l_, out));
-    if (slot < 0 || slot >= h->max_particles || !out)
-        return fail(h, RBS_ERR_INVALID_ARGUMENT, fmt("get_window: bad slot %d", slot));
-    RBS_HIP(h, hipSetDevice(h->device));
-    if (int32_t rc = drain(h, true)) return rc;
-    RBS_HIP(h, hipMemcpy(out, h->d_win[h->cur] + slot, sizeof(int32_t) * 4, hipMemcpyDeviceToHost));
-    return RBS_OK;
-}
-
 int32_t rbs_set_option(rbs_handle* h, int32_t option, double value)
 {
     if (!h) return RBS_ERR_INVALID_ARGUMENT;
@@ -2513,641 +1645,10 @@ int32_t rbs_get_background(rbs_handle* h, float* out)
     return RBS_OK;
 }
 
-// ---------------------------------------------------------------------------- device tracker
 }  // extern "C"
 
-struct rbs_tracker {
-    const double* frame64 = nullptr;   // rbs_tracker_submit_f64: this submit's frame as doubles (tracker_submit_impl reads it instead of `frame`)
-    std::vector<float> frame_tmp;      // ... converted here where a float frame is needed (a sensor over several devices)
-    rbs_handle* s = nullptr;
-    rbt::TrackerDev T{};
-    std::vector<void*> allocs;
-    double* d_normals = nullptr;   // staging for host-supplied randomness
-    double* d_uniforms = nullptr;
-    std::string err;
-    // a sensor over several devices: one replica (all particle states + the filter's kernels) per
-    // shard; `s` is then the group handle and T is unused
-    std::vector<rbs_tracker*> reps;
-    // pipelining (rbs_tracker_submit / rbs_tracker_result): up to two frames in flight; per slot the
-    // host-supplied randomness (pinned staging + its device image) and the frame's result (pinned)
-    double* h_normals[2] = {nullptr, nullptr};
-    double* h_uniforms[2] = {nullptr, nullptr};
-    double* d_normals2[2] = {nullptr, nullptr};
-    double* d_uniforms2[2] = {nullptr, nullptr};
-    double* h_state[2] = {nullptr, nullptr};
-    int* h_flags[2] = {nullptr, nullptr};
-    int* h_serr[2] = {nullptr, nullptr};
-    hipEvent_t ev_res[2] = {nullptr, nullptr};
-    double* h_state_dev[2] = {nullptr, nullptr};   // h_state / h_flags as the device addresses them
-    int* h_flags_dev[2] = {nullptr, nullptr};
-    int32_t res_rc[2] = {0, 0};       // (a handle over several devices runs submit synchronously)
-    int res_seq[2] = {0, 0};          // the frame number the kernel that finishes slot k's frame stores into h_flags[k][2]
-    long submitted = 0, collected = 0;
-    bool recentre_pending = false;    // T.part_old still holds the particles before the last frame's re-centring
-    bool poisoned = false;            // a frame failed half-way (buffers partly swapped): rbs_tracker_initialize first
-};
-
-namespace {
-int32_t tfail(rbs_tracker* t, int32_t code, const std::string& msg) { t->err = msg; t->s->err = msg; return code; }
-
-#define RBT_HIP(t, call)                                                                       \
-    do {                                                                                       \
-        hipError_t e_ = (call);                                                                \
-        if (e_ != hipSuccess) {                                                                \
-            (void)hipGetLastError();                                                           \
-            return tfail(t, e_ == hipErrorOutOfMemory ? RBS_ERR_OUT_OF_MEMORY : RBS_ERR_HIP,   \
-                         fmt("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__)); \
-        }                                                                                      \
-    } while (0)
-
-template <typename X>
-int32_t talloc(rbs_tracker* t, X** p, size_t count)
-{
-    RBT_HIP(t, hipMalloc(p, sizeof(X) * (count ? count : 1)));
-    t->allocs.push_back(*p);
-    return RBS_OK;
-}
-}  // namespace
-
-namespace {
-// The filter step's weights and the tracker's mean: single-block kernels for few particles (the
-// launch chain is what counts there), grid kernels from kMultiBlockFrom particles on.
-void launch_weights(const rbt::TrackerDev& T, int updated, hipStream_t s)
-{
-    if (T.n < rbt::kMultiBlockFrom) {
-        hipLaunchKernelGGL(rbt::weights_kernel, dim3(1), dim3(1024), 0, s, T, updated);
-        return;
-    }
-    const int blocks = (T.n + rbt::kChunk - 1) / rbt::kChunk;
-    hipLaunchKernelGGL(rbt::weights_w1_kernel, dim3((unsigned)blocks), dim3(1024), 0, s, T, updated);
-    hipLaunchKernelGGL(rbt::weights_w2_kernel, dim3((unsigned)blocks), dim3(1024), 0, s, T);
-    hipLaunchKernelGGL(rbt::weights_w3_kernel, dim3(1), dim3(64), 0, s, T, blocks);
-    hipLaunchKernelGGL(rbt::weights_w4_kernel, dim3((unsigned)blocks), dim3(1024), 0, s, T);
-}
-void launch_mean(const rbt::TrackerDev& T, hipStream_t s)
-{
-    if (T.n < rbt::kMultiBlockFrom) {
-        hipLaunchKernelGGL(rbt::mean_kernel, dim3(1), dim3(1024), 0, s, T);
-        return;
-    }
-    const int blocks = (T.n + rbt::kChunk - 1) / rbt::kChunk;
-    hipLaunchKernelGGL(rbt::mean_m1_kernel, dim3((unsigned)blocks), dim3(1024), 0, s, T);
-    hipLaunchKernelGGL(rbt::mean_m2_kernel, dim3((unsigned)blocks), dim3(1024), 0, s, T);
-    hipLaunchKernelGGL(rbt::mean_m3_kernel, dim3(1), dim3(64), 0, s, T, blocks);
-}
-// The other steps of a frame, each with its launch geometry in one place: rbs_tracker_submit, the
-// tracker over several devices and the test build's filter probe (rbsensor_probes.hip) launch them
-// through these.
-inline dim3 per_particle_grid(const rbt::TrackerDev& T) { return dim3((unsigned)((T.n + 255) / 256)); }
-void launch_propagate(const rbt::TrackerDev& T, int b, int recentre, hipStream_t s)
-{
-    hipLaunchKernelGGL(rbt::propagate_kernel, per_particle_grid(T), dim3(256), 0, s, T, b, recentre);
-}
-void launch_resample_gather(const rbt::TrackerDev& T, int b, hipStream_t s)
-{
-    hipLaunchKernelGGL(rbt::resample_gather_kernel, dim3((unsigned)T.n), dim3(64), 0, s, T, b);
-}
-void launch_gather(const rbt::TrackerDev& T, hipStream_t s)
-{
-    hipLaunchKernelGGL(rbt::gather_kernel, dim3((unsigned)T.n), dim3(64), 0, s, T);
-}
-void launch_filter_tail(const rbt::TrackerDev& T, int b, int updated, hipStream_t s)
-{
-    hipLaunchKernelGGL(rbt::filter_tail_kernel, dim3(1), dim3(1024), 0, s, T, b, updated);
-}
-void launch_filter_step(const rbt::TrackerDev& T, int b, int updated, int last, hipStream_t s)
-{
-    hipLaunchKernelGGL(rbt::filter_step_kernel, dim3(1), dim3(1024), 0, s, T, b, updated, last);
-}
-void launch_recentre(const rbt::TrackerDev& T, double* particles, hipStream_t s)
-{
-    hipLaunchKernelGGL(rbt::recentre_kernel, per_particle_grid(T), dim3(256), 0, s, T, particles);
-}
-// after a sampling block's gather: the gathered arrays are the block's result
-void swap_gathered(rbt::TrackerDev& T)
-{
-    std::swap(T.part_old, T.part_old2);
-    std::swap(T.part_new, T.part_new2);
-    std::swap(T.noise, T.noise2);
-    std::swap(T.ll, T.ll2);
-    std::swap(T.idx, T.idx2);
-}
-
-// One device's tracker state.  cap > 0: the sensor is a shard of a group with `cap` slots per device.
-int32_t tracker_create_one(rbs_handle* sensor, const rbs_tracker_params* p, int n_dev, int cap, rbs_tracker** out)
-{
-    RBS_HIP(sensor, hipSetDevice(sensor->device));
-    rbs_tracker* t = new (std::nothrow) rbs_tracker;
-    if (!t) return fail(sensor, RBS_ERR_OUT_OF_MEMORY, "tracker_create: out of host memory");
-    t->s = sensor;
-    rbt::TrackerDev& T = t->T;
-    T.n = p->n_particles;
-    T.parts = sensor->n_bodies;
-    T.D = T.parts * rbt::kBody;
-    for (int k = 0; k < 3; ++k) { T.sigma[k] = p->linear_sigma[k]; T.sigma[3 + k] = p->angular_sigma[k]; }
-    T.vf = p->velocity_factor;
-    T.max_kl = p->max_kl_divergence;
-    const size_t n = (size_t)T.n, D = (size_t)T.D, P6 = (size_t)T.parts * 6;
-    int32_t rc = RBS_OK;
-    if ((rc = talloc(t, &T.part_old, n * D)) || (rc = talloc(t, &T.part_new, n * D)) ||
-        (rc = talloc(t, &T.part_old2, n * D)) || (rc = talloc(t, &T.part_new2, n * D)) ||
-        (rc = talloc(t, &T.noise, n * P6)) || (rc = talloc(t, &T.noise2, n * P6)) ||
-        (rc = talloc(t, &T.logw, n)) || (rc = talloc(t, &T.ll, n)) || (rc = talloc(t, &T.ll2, n)) ||
-        (rc = talloc(t, &T.ll_new, n)) || (rc = talloc(t, &T.idx, n)) || (rc = talloc(t, &T.idx2, n)) ||
-        (rc = talloc(t, &T.parents, n)) || (rc = talloc(t, &T.cdf, n)) || (rc = talloc(t, &T.deflt, D)) ||
-        (rc = talloc(t, &T.mean, D + (size_t)T.parts * 9)) || (rc = talloc(t, &T.poses, n * (size_t)T.parts * 12)) ||
-        (rc = talloc(t, &T.flag, 2)) || (rc = talloc(t, &T.red, (size_t)rbt::kRedBlocks * (3 + D))) ||
-        (rc = talloc(t, &t->d_normals, n * P6)) ||
-        (rc = talloc(t, &t->d_uniforms, n * (size_t)T.parts)) ||
-        (cap > 0 && ((rc = talloc(t, &T.layout, n)) || (rc = talloc(t, &T.ll_sorted, (size_t)n_dev * cap)) ||
-                     (rc = talloc(t, &T.poses_sorted, (size_t)cap * T.parts * 12)) || (rc = talloc(t, &T.idx_sorted, (size_t)cap))))) {
-        rbs_tracker_destroy(t);
-        return rc;
-    }
-    if (hipMemsetAsync(T.deflt, 0, sizeof(double) * D, sensor->stream) != hipSuccess) {
-        (void)hipGetLastError();
-        rbs_tracker_destroy(t);
-        return fail(sensor, RBS_ERR_HIP, "tracker_create: hipMemsetAsync failed");
-    }
-    t->d_normals2[0] = t->d_normals;
-    t->d_uniforms2[0] = t->d_uniforms;
-    if ((rc = talloc(t, &t->d_normals2[1], n * P6)) || (rc = talloc(t, &t->d_uniforms2[1], n * (size_t)T.parts))) {
-        rbs_tracker_destroy(t);
-        return rc;
-    }
-    for (int k = 0; k < 2; ++k) {
-        if (hipHostMalloc(&t->h_normals[k], sizeof(double) * n * P6, hipHostMallocDefault) != hipSuccess ||
-            hipHostMalloc(&t->h_uniforms[k], sizeof(double) * n * T.parts, hipHostMallocDefault) != hipSuccess ||
-            hipHostMalloc(&t->h_state[k], sizeof(double) * D, hipHostMallocDefault) != hipSuccess ||
-            hipHostMalloc(&t->h_flags[k], sizeof(int) * 4, hipHostMallocDefault) != hipSuccess ||
-            hipHostMalloc(&t->h_serr[k], 2 * sizeof(int), hipHostMallocDefault) != hipSuccess ||
-            hipEventCreateWithFlags(&t->ev_res[k], hipEventDisableTiming) != hipSuccess) {
-            (void)hipGetLastError();
-            rbs_tracker_destroy(t);
-            return fail(sensor, RBS_ERR_OUT_OF_MEMORY, "tracker_create: pinned host memory");
-        }
-        t->h_serr[k][0] = t->h_serr[k][1] = 0;
-        t->h_flags[k][2] = 0;
-        if (hipHostGetDevicePointer(reinterpret_cast<void**>(&t->h_state_dev[k]), t->h_state[k], 0) != hipSuccess ||
-            hipHostGetDevicePointer(reinterpret_cast<void**>(&t->h_flags_dev[k]), t->h_flags[k], 0) != hipSuccess) {
-            (void)hipGetLastError();
-            rbs_tracker_destroy(t);
-            return fail(sensor, RBS_ERR_HIP, "tracker_create: hipHostGetDevicePointer failed");
-        }
-    }
-    *out = t;
-    return RBS_OK;
-}
-}  // namespace
-
-extern "C" {
-
-int32_t rbs_tracker_create(rbs_handle* sensor, const rbs_tracker_params* p, rbs_tracker** out)
-{
-    if (!sensor || !out) return RBS_ERR_INVALID_ARGUMENT;
-    *out = nullptr;
-    const int total = sensor->shards.empty() ? sensor->max_particles : (int)sensor->shards.size() * sensor->shard_cap;
-    if (!p || p->n_particles <= 0 || p->n_particles > total)
-        return fail(sensor, RBS_ERR_INVALID_ARGUMENT, "tracker_create: n_particles outside 1..max_particles");
-    if (p->n_particles > rbt::kRedBlocks * rbt::kChunk)
-        return fail(sensor, RBS_ERR_INVALID_ARGUMENT, fmt("tracker_create: at most %d particles", rbt::kRedBlocks * rbt::kChunk));
-    if (sensor->shards.empty()) return tracker_create_one(sensor, p, 1, 0, out);
-    rbs_tracker* g = new (std::nothrow) rbs_tracker;
-    if (!g) return fail(sensor, RBS_ERR_OUT_OF_MEMORY, "tracker_create: out of host memory");
-    g->s = sensor;
-    for (rbs_handle* sh : sensor->shards) {
-        rbs_tracker* r = nullptr;
-        if (int32_t rc = tracker_create_one(sh, p, (int)sensor->shards.size(), sensor->shard_cap, &r)) {
-            sensor->err = sh->err;
-            rbs_tracker_destroy(g);
-            return rc;
-        }
-        g->reps.push_back(r);
-    }
-    *out = g;
-    return RBS_OK;
-}
-
-void rbs_tracker_destroy(rbs_tracker* t)
-{
-    if (!t) return;
-    if (!t->reps.empty() || !t->s->shards.empty()) {
-        for (rbs_tracker* r : t->reps) rbs_tracker_destroy(r);
-        delete t;
-        return;
-    }
-    (void)hipSetDevice(t->s->device);
-    (void)hipStreamSynchronize(t->s->stream);
-    for (void* p : t->allocs) (void)hipFree(p);
-    for (int k = 0; k < 2; ++k) {
-        if (t->h_normals[k]) (void)hipHostFree(t->h_normals[k]);
-        if (t->h_uniforms[k]) (void)hipHostFree(t->h_uniforms[k]);
-        if (t->h_state[k]) (void)hipHostFree(t->h_state[k]);
-        if (t->h_flags[k]) (void)hipHostFree(t->h_flags[k]);
-        if (t->h_serr[k]) (void)hipHostFree(t->h_serr[k]);
-        if (t->ev_res[k]) (void)hipEventDestroy(t->ev_res[k]);
-    }
-    delete t;
-}
-
-int32_t rbs_tracker_initialize(rbs_tracker* t, const double* default_state)
-{
-    if (!t) return RBS_ERR_INVALID_ARGUMENT;
-    if (!default_state) return tfail(t, RBS_ERR_INVALID_ARGUMENT, "tracker_initialize: null state");
-    t->submitted = t->collected = 0;
-    t->recentre_pending = false;
-    t->poisoned = false;
-    if (!t->reps.empty()) {
-        for (rbs_tracker* r : t->reps)
-            if (int32_t rc = rbs_tracker_initialize(r, default_state)) { t->s->err = r->s->err; return rc; }
-        for (rbs_handle* sh : t->s->shards) {   // the shards' resets left their streams idle: a clean slate for the group's ordering
-            RBT_HIP(t, hipSetDevice(sh->device));
-            RBT_HIP(t, hipEventRecord(sh->ev_done, sh->stream));
-        }
-        t->s->poisoned = false;
-        frame_abandon(t->s);
-        return RBS_OK;
-    }
-    rbt::TrackerDev& T = t->T;
-    RBT_HIP(t, hipSetDevice(t->s->device));
-    if (int32_t rc = rbs_reset(t->s)) return rc;
-    hipStream_t s = t->s->stream;
-    RBT_HIP(t, hipMemcpyAsync(T.deflt, default_state, sizeof(double) * T.D, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(rbt::init_kernel, dim3((unsigned)((T.n + 255) / 256)), dim3(256), 0, s, T);
-    RBT_HIP(t, hipGetLastError());
-    RBT_HIP(t, hipStreamSynchronize(s));
-    T.frame = 0;
-    for (int k = 0; k < 2; ++k) { t->h_flags[k][2] = 0; t->res_seq[k] = 0; }   // frame numbers start over
-    if (t->s->slab_px && !t->s->group) {
-        // Window-sized slabs: a tracker frame that overflows cannot be repeated, so the slabs are sized
-        // BEFORE the first frame -- one updating probe call of a single particle at the default pose
-        // measures the object's screen rectangle, the housekeeping enlarges the slabs to hold it with
-        // room to move, and the sensor is reset again.  From there on the regions grow a few pixels
-        // per frame and the housekeeping at every frame's result keeps ahead of them.
-        rbs_handle* h = t->s;
-        hipLaunchKernelGGL(rbt::default_pose_kernel, dim3(1), dim3(64), 0, s, T);
-        RBT_HIP(t, hipGetLastError());
-        if (int32_t rc = enqueue_loglikes(h, T.poses, T.idx, 1, true, T.ll_new, s)) return rc;
-        if (int32_t rc = drain(h, true)) return rc;
-        RBT_HIP(t, hipMemcpy(h->h_err, h->d_err, 2 * sizeof(int), hipMemcpyDeviceToHost));
-        if (int32_t rc = slab_housekeeping(h)) return rc;
-        if (int32_t rc = rbs_reset(h)) return rc;
-    }
-    return RBS_OK;
-}
-
-}  // extern "C" (group_tracker_track below needs C++ linkage)
-
-namespace {
-// One frame on a sensor over several devices.  Every device runs the whole filter on all the
-// particle states (identical inputs, identical code); the sensor call alone is sharded: device k
-// evaluates the particles laid out at slots [k cap, (k+1) cap) (layout_kernel), and the
-// log-likelihoods are exchanged with ONE all-gather per sampling block (RCCL over xGMI).
-int32_t group_tracker_track(rbs_tracker* t, const float* frame, const double* normals, const double* uniforms,
-                            uint64_t seed, double* out_state, int32_t* out_resamplings)
-{
-    rbs_handle* g = t->s;
-    const int nd = (int)g->shards.size(), cap = g->shard_cap;
-    if (frame)
-        if (int32_t rc = rbs_set_observation_f32(g, frame, (size_t)g->npx)) return rc;
-    std::vector<hipStream_t> streams(nd);
-    std::vector<double*> llbufs(nd);
-    for (int k = 0; k < nd; ++k) {
-        rbs_tracker* r = t->reps[k];
-        rbt::TrackerDev& T = r->T;
-        rbs_handle* h = r->s;
-        streams[k] = h->stream;
-        llbufs[k] = T.ll_sorted;
-        RBT_HIP(t, hipSetDevice(h->device));
-        const size_t n = (size_t)T.n;
-        T.normals = nullptr;
-        T.uniforms = nullptr;
-        if (normals) {
-            RBT_HIP(t, hipMemcpyAsync(r->d_normals, normals, sizeof(double) * n * T.parts * 6, hipMemcpyHostToDevice, h->stream));
-            T.normals = r->d_normals;
-        }
-        if (uniforms) {
-            RBT_HIP(t, hipMemcpyAsync(r->d_uniforms, uniforms, sizeof(double) * n * T.parts, hipMemcpyHostToDevice, h->stream));
-            T.uniforms = r->d_uniforms;
-        }
-        T.seed = seed;
-    }
-    const int parts = t->reps[0]->T.parts, n = t->reps[0]->T.n;
-    const dim3 g256((unsigned)((n + 255) / 256)), b256(256);
-    for (int b = 0; b < parts; ++b) {
-        const bool last = b == parts - 1;
-        for (int k = 0; k < nd; ++k) {
-            rbs_tracker* r = t->reps[k];
-            RBT_HIP(t, hipSetDevice(r->s->device));
-            launch_propagate(r->T, b, 0, streams[k]);
-            hipLaunchKernelGGL(rbt::layout_kernel, dim3(1), dim3(1024), 0, streams[k], r->T, nd, cap);
-            const int lo = std::min(n, k * cap), cnt = std::min(n, (k + 1) * cap) - lo;
-            if (cnt > 0)
-                hipLaunchKernelGGL(rbt::shard_gather_kernel, dim3((unsigned)((cnt + 255) / 256)), b256, 0, streams[k], r->T, lo, cnt);
-            RBT_HIP(t, hipGetLastError());
-        }
-        if (int32_t rc = group_begin_call(g, nullptr, last)) return rc;
-        for (int k = 0; k < nd; ++k) {
-            rbs_tracker* r = t->reps[k];
-            rbs_handle* h = r->s;
-            RBT_HIP(t, hipSetDevice(h->device));
-            const int lo = std::min(n, k * cap), cnt = std::min(n, (k + 1) * cap) - lo;
-            if (cnt > 0) {
-                if (int32_t rc = enqueue_loglikes(h, r->T.poses_sorted, r->T.idx_sorted, cnt, last, r->T.ll_sorted + lo, h->stream))
-                    return gfail(g, h, rc);
-            } else {
-                if (int32_t rc = advance_empty(h, last)) return gfail(g, h, rc);
-                RBT_HIP(t, hipEventRecord(h->ev_done, h->stream));
-            }
-        }
-        if (int32_t rc = group_allgather(g, llbufs.data(), (size_t)cap, streams.data())) return rc;
-        for (int k = 0; k < nd; ++k) {
-            rbs_tracker* r = t->reps[k];
-            rbt::TrackerDev& T = r->T;
-            RBT_HIP(t, hipSetDevice(r->s->device));
-            hipStream_t s = streams[k];
-            hipLaunchKernelGGL(rbt::shard_scatter_kernel, g256, b256, 0, s, T, last ? 1 : 0);
-            launch_weights(T, 0, s);
-            hipLaunchKernelGGL(rbt::resample_kernel, g256, b256, 0, s, T, b);
-            launch_gather(T, s);
-            RBT_HIP(t, hipGetLastError());
-            swap_gathered(T);
-        }
-    }
-    int flags[2] = {0, 0};
-    for (int k = 0; k < nd; ++k) {
-        rbs_tracker* r = t->reps[k];
-        rbt::TrackerDev& T = r->T;
-        RBT_HIP(t, hipSetDevice(r->s->device));
-        launch_mean(T, streams[k]);
-        launch_recentre(T, T.part_new, streams[k]);
-        RBT_HIP(t, hipGetLastError());
-        std::swap(T.part_old, T.part_new);   // this frame's particles are the next frame's old ones
-        if (k == 0) {
-            RBT_HIP(t, hipMemcpyAsync(out_state, T.deflt, sizeof(double) * T.D, hipMemcpyDeviceToHost, streams[k]));
-            RBT_HIP(t, hipMemcpyAsync(flags, T.flag, sizeof(flags), hipMemcpyDeviceToHost, streams[k]));
-        }
-        T.frame += 1;
-    }
-    for (int k = 0; k < nd; ++k) {   // the host frame / randomness buffers may be reused after this call
-        RBT_HIP(t, hipSetDevice(t->reps[k]->s->device));
-        RBT_HIP(t, hipStreamSynchronize(streams[k]));
-    }
-    if (out_resamplings) *out_resamplings = flags[1];
-    int32_t slab_rc = RBS_OK;
-    for (rbs_handle* sh : g->shards) {   // slabs: a region that did not fit, on any shard
-        if (!sh->slab_px) break;
-        RBT_HIP(t, hipSetDevice(sh->device));
-        RBT_HIP(t, hipMemcpy(sh->h_err, sh->d_err, 2 * sizeof(int), hipMemcpyDeviceToHost));
-        if (slab_rc == RBS_OK && check_slab_error(sh) != RBS_OK) slab_rc = gfail(g, sh, RBS_ERR_OUT_OF_MEMORY);
-    }
-    const std::string msg = g->err;
-    if (int32_t rc = group_grow_slabs(g, nullptr)) return rc;   // (every stream is idle here: enlarge before a region fills a slab)
-    if (slab_rc) g->err = msg;
-    return slab_rc;
-}
-}  // namespace
-
-extern "C" {
-
-// The body of rbs_tracker_submit; a failure in here happens after some of the frame's work was
-// enqueued and some of the tracker's buffers were swapped.
-static int32_t tracker_submit_impl(rbs_tracker* t, const float* frame, const double* normals, const double* uniforms, uint64_t seed)
-{
-    if (t->submitted - t->collected >= 2)
-        return tfail(t, RBS_ERR_INVALID_ARGUMENT, "tracker_submit: two frames are in flight already (call rbs_tracker_result)");
-    const int slot = (int)(t->submitted & 1);
-    const double* frame64 = t->frame64;
-    t->frame64 = nullptr;
-    if (frame64 && !t->reps.empty()) {   // (the sharded form uploads float frames: converted once here)
-        t->frame_tmp.resize((size_t)t->reps[0]->s->npx);
-        convert_f64_f32(t->frame_tmp.data(), frame64, t->frame_tmp.size());
-        frame = t->frame_tmp.data();
-        frame64 = nullptr;
-    }
-    if (!t->reps.empty()) {   // several devices: the frame runs to completion here, its result waits in the slot
-        rbs_tracker* r0 = t->reps[0];
-        t->res_rc[slot] = group_tracker_track(t, frame, normals, uniforms, seed, r0->h_state[slot], &r0->h_flags[slot][1]);
-        t->submitted += 1;
-        return t->res_rc[slot];
-    }
-    rbt::TrackerDev& T = t->T;
-    rbs_handle* h = t->s;
-    const BorrowedFrameGuard borrowed_guard{h};   // (the caller's frame is the caller's again when this returns, whatever happened)
-    RBT_HIP(t, hipSetDevice(h->device));
-    if ((frame || frame64) && h->npx <= 0) return tfail(t, RBS_ERR_INVALID_ARGUMENT, "tracker_submit: bad sensor");
-    hipStream_t s = h->stream;
-    const size_t n = (size_t)T.n;
-    T.normals = nullptr;
-    T.uniforms = nullptr;
-    // host-supplied randomness goes through pinned staging: the caller's buffers are free on return
-    if (normals) {
-        std::memcpy(t->h_normals[slot], normals, sizeof(double) * n * T.parts * 6);
-        RBT_HIP(t, hipMemcpyAsync(t->d_normals2[slot], t->h_normals[slot], sizeof(double) * n * T.parts * 6, hipMemcpyHostToDevice, s));
-        T.normals = t->d_normals2[slot];
-    }
-    if (uniforms) {
-        std::memcpy(t->h_uniforms[slot], uniforms, sizeof(double) * n * T.parts);
-        RBT_HIP(t, hipMemcpyAsync(t->d_uniforms2[slot], t->h_uniforms[slot], sizeof(double) * n * T.parts, hipMemcpyHostToDevice, s));
-        T.uniforms = t->d_uniforms2[slot];
-    }
-    T.seed = seed;
-    T.host_state = t->h_state_dev[slot];
-    T.host_flags = t->h_flags_dev[slot];
-    const char* nf = std::getenv("RBS_TRACKER_FUSED");
-    const bool fused = T.n <= rbt::kFusedFilterMax && !(nf && std::atoi(nf) == 0);
-    static const bool tail_on = [] { const char* e = std::getenv("RBS_TRACKER_TAIL"); return !(e && std::atoi(e) == 0); }();
-    const bool tail = !fused && tail_on && T.n < rbt::kMultiBlockFrom;   // (RBS_TRACKER_TAIL=0: the three separate launches, A/B)
-    for (int b = 0; b < T.parts; ++b) {
-        const bool last = b == T.parts - 1;
-        // (the transition fused into the sensor's rectangles kernel -- one launch less -- measured no
-        // gain: 3 987 against 3 976 frames/s at 2 000 particles)
-        launch_propagate(T, b, b == 0 && t->recentre_pending ? 1 : 0, s);
-        if (b == 0) t->recentre_pending = false;
-        RBT_HIP(t, hipGetLastError());
-        // the frame is handed over AFTER the first transition launch: the transition (and the
-        // sensor's rectangles kernel behind it) do not depend on it, and run while the host copies
-        // the frame into pinned memory and the copy engine uploads it
-        if (b == 0 && (frame || frame64)) {
-            // Few particles: the frame's own journey (staging copy, transfer, model terms: ~80 us) is most of a frame, and the sensor's
-            // GEOMETRY kernel does not need it -- the frame is handed to the sensor as a borrowed one and staged by enqueue_loglikes
-            // between the two kernels of the split launch (inside this call: the caller's buffer is free on return as before).  Above
-            // kTrackerSplitMax evaluations the one-kernel launch's shorter kernel time wins (RBS_TRACKER_SPLIT_MAX, 0: never).
-            const int split_max = h->tracker_split_max;
-            const bool idle = t->submitted == t->collected;   // (a frame already in flight -- look-ahead -- hides the journey by itself, and the one-kernel launch is the shorter)
-            if (idle && T.n * T.parts <= split_max && can_borrow(h)) {
-                if (int32_t rc = frame_begin(h)) return rc;
-                if (int32_t rc = frame_ready(h, h->stream)) return rc;
-                hand_over_borrowed(h, frame, frame64);   // (doubles, as dbot hands images over: converted while they are staged)
-            } else if (int32_t rc = frame64 ? rbs_set_observation(h, frame64, (size_t)h->npx) : rbs_set_observation_f32(h, frame, (size_t)h->npx)) return rc;
-        }
-        if (int32_t rc = enqueue_loglikes(h, T.poses, T.idx, T.n, last, T.ll_new, s)) return rc;
-        if (fused) {
-            launch_filter_step(T, b, last ? 1 : 0, last ? 1 : 0, s);
-        } else if (tail && last) {
-            // the estimate first (one launch, the result event right behind it), the gather after
-            launch_filter_tail(T, b, 1, s);
-            RBT_HIP(t, hipGetLastError());
-            if (h->slab_px) RBT_HIP(t, hipMemcpyAsync(t->h_serr[slot], h->d_err, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
-            RBT_HIP(t, hipEventRecord(t->ev_res[slot], s));
-            launch_gather(T, s);
-        } else {
-            launch_weights(T, last ? 1 : 0, s);
-            launch_resample_gather(T, b, s);
-        }
-        RBT_HIP(t, hipGetLastError());
-        swap_gathered(T);
-    }
-    if (!fused) {
-        // (re-centring inside the single mean block was tried: its two rounds of rotations per thread
-        // on one CU take longer than the separate launch, 25 us against 16.5 + 5)
-        if (!tail) launch_mean(T, s);
-        // the re-centring itself rides in the next frame's first transition launch (the thread that
-        // moves particle i re-centres it first); rbs_tracker_get applies it on demand
-        static const bool now = [] { const char* e = std::getenv("RBS_TRACKER_RECENTRE_NOW"); return e && std::atoi(e) != 0; }();
-        if (now) launch_recentre(T, T.part_new, s);
-        else t->recentre_pending = true;
-    }
-    RBT_HIP(t, hipGetLastError());
-    std::swap(T.part_old, T.part_new);   // this frame's particles are the next frame's old ones
-    // (the estimate and the flags were stored into h_state[slot] / h_flags[slot] by the kernel that
-    // finished them: no copies behind the last kernel)
-    if (!tail) {
-        if (h->slab_px) RBT_HIP(t, hipMemcpyAsync(t->h_serr[slot], h->d_err, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
-        RBT_HIP(t, hipEventRecord(t->ev_res[slot], s));
-    }
-    t->res_seq[slot] = (int)(T.frame + 1);
-    T.frame += 1;
-    t->res_rc[slot] = RBS_OK;
-    t->submitted += 1;
-    return RBS_OK;
-}
-
-int32_t rbs_tracker_submit(rbs_tracker* t, const float* frame, const double* normals, const double* uniforms, uint64_t seed)
-{
-    if (!t) return RBS_ERR_INVALID_ARGUMENT;
-    if (t->poisoned || t->s->poisoned)
-        return tfail(t, RBS_ERR_HIP, "tracker_submit: an earlier frame failed half-way (" + (t->s->poisoned ? t->s->poison_msg : t->err) +
-                                         "): call rbs_tracker_initialize");
-    const long before = t->submitted;
-    const int32_t rc = tracker_submit_impl(t, frame, normals, uniforms, seed);
-    if (rc != RBS_OK && !(rc == RBS_ERR_INVALID_ARGUMENT && t->submitted == before)) {
-        // drain what was enqueued and refuse further frames: the particle buffers are out of step
-        const std::string why = t->err.empty() ? t->s->err : t->err;
-        if (t->reps.empty()) { (void)hipSetDevice(t->s->device); (void)hipStreamSynchronize(t->s->stream); (void)hipStreamSynchronize(t->s->copy_stream); }
-        else for (rbs_tracker* r : t->reps) { (void)hipSetDevice(r->s->device); (void)hipStreamSynchronize(r->s->stream); (void)hipStreamSynchronize(r->s->copy_stream); }
-        (void)hipGetLastError();
-        t->poisoned = true;
-        t->err = why;
-        t->s->err = why;
-    }
-    return rc;
-}
-
-int32_t rbs_tracker_result(rbs_tracker* t, double* out_state, int32_t* out_resamplings)
-{
-    if (!t) return RBS_ERR_INVALID_ARGUMENT;
-    if (!out_state) return tfail(t, RBS_ERR_INVALID_ARGUMENT, "tracker_result: null output");
-    if (t->collected >= t->submitted) return tfail(t, RBS_ERR_INVALID_ARGUMENT, "tracker_result: no frame in flight");
-    const int slot = (int)(t->collected & 1);
-    t->collected += 1;
-    rbs_tracker* r = t->reps.empty() ? t : t->reps[0];
-    const int D = r->T.D;
-    if (t->reps.empty()) {
-        RBT_HIP(t, hipSetDevice(t->s->device));
-        // The kernel that finishes the frame stores the estimate into pinned (host-coherent) memory and
-        // the frame's number behind it with a system-scope release: spin on that number -- the signalling
-        // of the kernel's completion and the wake-up behind it cost several microseconds more.  The
-        // event is the fall-back (and the only way with slabs, whose error word arrives by a copy).
-        bool seen = false;
-        if (!t->s->slab_px && t->res_seq[slot] > 0) {
-            volatile int* seq = t->h_flags[slot] + 2;
-            for (long it = 0; it < 4000000 && !seen; ++it) {
-                seen = __atomic_load_n(seq, __ATOMIC_ACQUIRE) == t->res_seq[slot];
-                if (!seen && (it & 255) == 255 && hipEventQuery(t->ev_res[slot]) == hipSuccess) break;
-                if (!seen) __builtin_ia32_pause();
-            }
-        }
-        if (!seen) RBT_HIP(t, hipEventSynchronize(t->ev_res[slot]));
-    }
-    std::memcpy(out_state, r->h_state[slot], sizeof(double) * D);
-    if (out_resamplings) *out_resamplings = r->h_flags[slot][1];
-    if (!t->reps.empty()) return t->res_rc[slot];
-    if (t->submitted == t->collected) t->s->quiet = !t->s->async_outstanding;   // frame by frame: the next frame may travel in pieces
-    if (t->s->slab_px) {
-        // the frame has run: a region that did not fit cannot be repaired here (the filter has resampled
-        // on the contained particle's NaN) and is an error -- but the slabs are enlarged BEFORE that,
-        // whenever the largest region asked for has filled three quarters of one, at a frame boundary
-        // with nothing in flight (regions move a few pixels per frame)
-        rbs_handle* h = t->s;
-        h->h_err[0] = t->h_serr[slot][0];
-        h->h_err[1] = t->h_serr[slot][1];
-        const int32_t rc = check_slab_error(h);
-        const std::string msg = h->err;
-        if (t->submitted == t->collected)
-            if (int32_t rc2 = slab_housekeeping(h)) return rc2;
-        if (rc) { h->err = msg; t->err = msg; t->poisoned = true; }
-        return rc;
-    }
-    return RBS_OK;
-}
-
-int32_t rbs_tracker_submit_f64(rbs_tracker* t, const double* frame, const double* normals, const double* uniforms, uint64_t seed)
-{
-    if (!t) return RBS_ERR_INVALID_ARGUMENT;
-    t->frame64 = frame;
-    const int32_t rc = rbs_tracker_submit(t, nullptr, normals, uniforms, seed);
-    t->frame64 = nullptr;
-    return rc;
-}
-
-int32_t rbs_tracker_track_f64(rbs_tracker* t, const double* frame, const double* normals, const double* uniforms, uint64_t seed,
-                              double* out_state, int32_t* out_resamplings)
-{
-    if (!t) return RBS_ERR_INVALID_ARGUMENT;
-    t->frame64 = frame;
-    const int32_t rc = rbs_tracker_track(t, nullptr, normals, uniforms, seed, out_state, out_resamplings);
-    t->frame64 = nullptr;
-    return rc;
-}
-
-int32_t rbs_tracker_track(rbs_tracker* t, const float* frame, const double* normals,
-                          const double* uniforms, uint64_t seed, double* out_state,
-                          int32_t* out_resamplings)
-{
-    if (!t) return RBS_ERR_INVALID_ARGUMENT;
-    if (!out_state) return tfail(t, RBS_ERR_INVALID_ARGUMENT, "tracker_track: null output");
-    if (t->submitted != t->collected)
-        return tfail(t, RBS_ERR_INVALID_ARGUMENT, "tracker_track: frames submitted with rbs_tracker_submit are still in flight");
-    if (int32_t rc = rbs_tracker_submit(t, frame, normals, uniforms, seed)) {
-        if (t->submitted != t->collected) t->collected = t->submitted;   // (a group's frame that failed: nothing to collect)
-        return rc;
-    }
-    return rbs_tracker_result(t, out_state, out_resamplings);
-}
-
-int32_t rbs_tracker_get(rbs_tracker* t, double* particles, double* log_weights, int32_t* indices)
-{
-    if (!t) return RBS_ERR_INVALID_ARGUMENT;
-    if (!t->reps.empty()) {
-        for (rbs_tracker* r : t->reps) { RBT_HIP(t, hipSetDevice(r->s->device)); RBT_HIP(t, hipStreamSynchronize(r->s->stream)); }
-        return rbs_tracker_get(t->reps[0], particles, log_weights, indices);
-    }
-    rbt::TrackerDev& T = t->T;
-    RBT_HIP(t, hipSetDevice(t->s->device));
-    if (t->recentre_pending) {   // (deferred into the next frame's transition launch: apply it now)
-        launch_recentre(T, T.part_old, t->s->stream);
-        RBT_HIP(t, hipGetLastError());
-        t->recentre_pending = false;
-    }
-    RBT_HIP(t, hipStreamSynchronize(t->s->stream));
-    if (particles) RBT_HIP(t, hipMemcpy(particles, T.part_old, sizeof(double) * (size_t)T.n * T.D, hipMemcpyDeviceToHost));
-    if (log_weights) RBT_HIP(t, hipMemcpy(log_weights, T.logw, sizeof(double) * (size_t)T.n, hipMemcpyDeviceToHost));
-    if (indices) RBT_HIP(t, hipMemcpy(indices, T.idx, sizeof(int) * (size_t)T.n, hipMemcpyDeviceToHost));
-    return RBS_OK;
-}
-
-}  // extern "C"
+// The device tracker's host side (rbs_tracker_*).
+#include "rbs_tracker_api.h"
 
 // The robust Gaussian tracker (rbs_gauss_*): its kernels and host side.
 #include "rbsensor_gauss.hip"

@@ -9,7 +9,7 @@
 //
 // rbs_test_filter does the same for the particle filter's kernels (rbsensor_tracker.hip): it builds an rbt::TrackerDev from host
 // arrays, launches a caller-chosen order of the frame's steps through the launch_* helpers rbs_tracker_submit itself uses
-// (rbsensor_capi.hip: no kernel body and no launch geometry is restated here), and hands every array back:
+// (rbs_tracker_api.h: no kernel body and no launch geometry is restated here), and hands every array back:
 // tests/test_gpu_filter_kernels.py.
 //
 // rbs_test_find_* do the same for the object finder's kernels (rbsensor_find.hip), one entry point per launch helper
