@@ -51,6 +51,9 @@ EXPORTS = (
     "rbs_find_stage_ms", "rbs_find_last_error",
     "rbs_find_default_foreground", "rbs_find_set_foreground", "rbs_find_get_plane", "rbs_find_get_seed_frame",
     "rbs_find_default_refinement", "rbs_find_set_refinement", "rbs_find_get_covariance", "rbs_find_get_perturbations",
+    "rbs_find_scene_default_params", "rbs_find_scene_create", "rbs_find_scene_destroy", "rbs_find_scene_set_foreground",
+    "rbs_find_scene_set_refinement", "rbs_find_scene_run", "rbs_find_scene_get_order", "rbs_find_scene_get_residual",
+    "rbs_find_scene_body_finder", "rbs_find_scene_get_polish", "rbs_find_scene_stage_ms", "rbs_find_scene_last_error",
     "rbs_assess_default_params", "rbs_assess_poses", "rbs_assess_verdict", "rbs_assess_get_plane", "rbs_assess_kernel_ms",
     "rbs_contour_default_params", "rbs_contour_poses", "rbs_contour_verdict", "rbs_contour_kernel_ms",
 )
@@ -125,6 +128,19 @@ class RbsFindRefinement(C.Structure):
         ("mix", C.c_double),
         ("shrink", C.c_double),
         ("jitter", C.c_double),
+    ]
+
+
+class RbsFindSceneParams(C.Structure):
+    _fields_ = [
+        ("explain_sigmas", C.c_double),
+        ("explain_radius", C.c_int32),
+        ("polish_sweeps", C.c_int32),
+        ("polish_children", C.c_int32),
+        ("reserved", C.c_int32),
+        ("polish_sigma_translation", C.c_double),
+        ("polish_sigma_angle", C.c_double),
+        ("polish_decay", C.c_double),
     ]
 
 
@@ -396,6 +412,31 @@ def load():
     lib.rbs_find_get_perturbations.argtypes = [H, C.c_int32, dp, lp]
     lib.rbs_find_last_error.restype = C.c_char_p
     lib.rbs_find_last_error.argtypes = [H]
+    up = C.POINTER(C.c_uint32)
+    lib.rbs_find_scene_default_params.restype = None
+    lib.rbs_find_scene_default_params.argtypes = [C.POINTER(RbsFindSceneParams)]
+    lib.rbs_find_scene_create.restype = C.c_int32
+    lib.rbs_find_scene_create.argtypes = [H, C.POINTER(RbsFindParams), C.POINTER(RbsFindSceneParams), C.POINTER(H)]
+    lib.rbs_find_scene_destroy.restype = None
+    lib.rbs_find_scene_destroy.argtypes = [H]
+    lib.rbs_find_scene_set_foreground.restype = C.c_int32
+    lib.rbs_find_scene_set_foreground.argtypes = [H, C.POINTER(RbsFindForeground)]
+    lib.rbs_find_scene_set_refinement.restype = C.c_int32
+    lib.rbs_find_scene_set_refinement.argtypes = [H, C.POINTER(RbsFindRefinement)]
+    lib.rbs_find_scene_run.restype = C.c_int32
+    lib.rbs_find_scene_run.argtypes = [H, fp, C.c_uint32, dp, dp, dp, up, dp]
+    lib.rbs_find_scene_get_order.restype = C.c_int32
+    lib.rbs_find_scene_get_order.argtypes = [H, ip, ip, dp]
+    lib.rbs_find_scene_get_residual.restype = C.c_int32
+    lib.rbs_find_scene_get_residual.argtypes = [H, C.c_int32, fp]
+    lib.rbs_find_scene_body_finder.restype = H
+    lib.rbs_find_scene_body_finder.argtypes = [H, C.c_int32]
+    lib.rbs_find_scene_get_polish.restype = C.c_int32
+    lib.rbs_find_scene_get_polish.argtypes = [H, C.c_int32, dp, dp, ip, ip]
+    lib.rbs_find_scene_stage_ms.restype = C.c_int32
+    lib.rbs_find_scene_stage_ms.argtypes = [H, fp, fp]
+    lib.rbs_find_scene_last_error.restype = C.c_char_p
+    lib.rbs_find_scene_last_error.argtypes = [H]
     lib.rbs_assess_default_params.restype = None
     lib.rbs_assess_default_params.argtypes = [C.POINTER(RbsAssessParams)]
     lib.rbs_assess_poses.restype = C.c_int32

@@ -247,6 +247,22 @@ __device__ inline void child_normals(unsigned long long seed, int round, int k, 
     }
 }
 
+// step 6's perturbation of the pose P by the six normals nz: o := R(sa nz[0..2]) R | t + st nz[3..5]
+__device__ inline void perturb_pose(const double* __restrict__ P, const double* nz, double st, double sa, double* __restrict__ o)
+{
+    const double v[3] = {sa * nz[0], sa * nz[1], sa * nz[2]};
+    double A[9];
+    rotvec_matrix(v, A);
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+            o[3 * r + c] = A[3 * r] * P[c] + A[3 * r + 1] * P[3 + c] + A[3 * r + 2] * P[6 + c];
+    o[9] = P[9] + st * nz[3];
+    o[10] = P[10] + st * nz[4];
+    o[11] = P[11] + st * nz[5];
+}
+
 // One thread per child of round r: [S][children][12].
 __global__ __launch_bounds__(256) void rbs_find_children_kernel(const double* __restrict__ surv, int S, int children, int round,
                                                                 unsigned long long seed, double st, double sa,
@@ -264,17 +280,7 @@ __global__ __launch_bounds__(256) void rbs_find_children_kernel(const double* __
     }
     double nz[6];
     child_normals(seed, round, k, j, nz);
-    const double v[3] = {sa * nz[0], sa * nz[1], sa * nz[2]};
-    double A[9];
-    rotvec_matrix(v, A);
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-            o[3 * r + c] = A[3 * r] * P[c] + A[3 * r + 1] * P[3 + c] + A[3 * r + 2] * P[6 + c];
-    o[9] = P[9] + st * nz[3];
-    o[10] = P[10] + st * nz[4];
-    o[11] = P[11] + st * nz[5];
+    perturb_pose(P, nz, st, sa, o);
 }
 
 // One thread per survivor: its best child (ties: lowest j; NaN never beats a number) becomes the survivor.  All children NaN:
@@ -784,6 +790,7 @@ inline void launch_refine_update(hipStream_t st, const double* child_score, cons
 
 struct rbs_find {
     rbs_handle* s = nullptr;          // the sensor (borrowed)
+    int part = -1;                    // >= 0: the finder of that part of a sensor of several (rbsensor_find_scene.hip); -1: the sensor's one object
     rbs_find_params p{};
     rbs_handle* coarse = nullptr;     // scoring handles: coarse resolution (max_particles = batch) and the sensor's
     rbs_handle* full = nullptr;       //   (max_particles = n_survivors * children); one occlusion slot each
@@ -911,10 +918,27 @@ const char* find_check(const rbs_find_params* p)
     return nullptr;
 }
 
-// a scoring handle: the sensor's configuration at (rows, cols, K), one occlusion slot, whole planes
-int32_t make_scorer(rbs_find* f, int rows, int cols, const double* K, int max_particles, rbs_handle** out)
+// where part b's vertices and triangles begin in the sensor's concatenated arrays (elements, not coordinates)
+void part_offsets(const rbs_handle* s, int b, size_t* v0, size_t* t0)
 {
-    rbs_config c = f->s->cfg;
+    *v0 = *t0 = 0;
+    for (int i = 0; i < b; ++i) { *v0 += (size_t)s->cfg_vertex_counts[i]; *t0 += (size_t)s->cfg_triangle_counts[i]; }
+}
+
+// a scoring handle: the sensor's configuration at (rows, cols, K), one occlusion slot, whole planes; part >= 0: the one-body
+// model made of that part of the sensor's
+int32_t make_scorer(const rbs_handle* s, int part, std::string* err, int rows, int cols, const double* K, int max_particles, rbs_handle** out)
+{
+    rbs_config c = s->cfg;
+    if (part >= 0) {
+        size_t v0, t0;
+        part_offsets(s, part, &v0, &t0);
+        c.n_objects = 1;
+        c.vertices = s->cfg_vertices.data() + 3 * v0;
+        c.vertex_counts = s->cfg_vertex_counts.data() + part;
+        c.triangles = s->cfg_triangles.data() + 3 * t0;
+        c.triangle_counts = s->cfg_triangle_counts.data() + part;
+    }
     c.rows = rows;
     c.cols = cols;
     for (int i = 0; i < 9; ++i) c.K[i] = K[i];
@@ -923,7 +947,7 @@ int32_t make_scorer(rbs_find* f, int rows, int cols, const double* K, int max_pa
     c.device_ids = nullptr;
     c.state_slab_px = RBS_SLAB_WHOLE_PLANES;
     rbs_handle* h = new (std::nothrow) rbs_handle;
-    if (!h) return ffail(f, RBS_ERR_OUT_OF_MEMORY, "find_create: out of host memory");
+    if (!h) { *err = "find_create: out of host memory"; return RBS_ERR_OUT_OF_MEMORY; }
     h->occ_slots = 1;
     int32_t rc;
     try {
@@ -933,7 +957,7 @@ int32_t make_scorer(rbs_find* f, int rows, int cols, const double* K, int max_pa
         rc = RBS_ERR_OUT_OF_MEMORY;
     }
     if (rc != RBS_OK) {
-        f->err = "find_create: scoring handle: " + h->err;
+        *err = "find_create: scoring handle: " + h->err;
         release(h);
         return rc;
     }
@@ -957,6 +981,24 @@ rbf::HypParams hyp_params(const rbs_find* f)
     H.offset = f->offset;
     return H;
 }
+
+// the mean distance of n vertices from their mean: the default depth_offset
+double mean_vertex_distance(const double* V, size_t nv)
+{
+    double c[3] = {0.0, 0.0, 0.0};
+    for (size_t i = 0; i < nv; ++i)
+        for (int k = 0; k < 3; ++k) c[k] += V[3 * i + k];
+    for (int k = 0; k < 3; ++k) c[k] /= (double)nv;
+    double m = 0.0;
+    for (size_t i = 0; i < nv; ++i) {
+        const double dx = V[3 * i] - c[0], dy = V[3 * i + 1] - c[1], dz = V[3 * i + 2] - c[2];
+        m += std::sqrt(dx * dx + dy * dy + dz * dz);
+    }
+    return m / (double)nv;
+}
+
+int32_t find_create_part(rbs_handle* sensor, const rbs_find_params* p, int part, rbs_find** out);
+int32_t find_run(rbs_find* f, const float* frame, const float* d_frame, int32_t k, double* poses, double* scores, int32_t* n_out, int32_t* found);
 
 }  // namespace
 
@@ -1022,9 +1064,20 @@ int32_t rbs_find_create(rbs_handle* sensor, const rbs_find_params* p, rbs_find**
         return fail(sensor, RBS_ERR_UNSUPPORTED, "find_create: the finder runs on single-device handles only");
     if (sensor->n_bodies != 1)
         return fail(sensor, RBS_ERR_UNSUPPORTED, "find_create: the finder searches for one object (n_objects = 1)");
+    return find_create_part(sensor, p, -1, out);
+}
+
+}  // extern "C"
+
+namespace {
+
+// rbs_find_create behind its checks; part >= 0: the finder of that part of the sensor's model alone (a scene finder's)
+int32_t find_create_part(rbs_handle* sensor, const rbs_find_params* p, int part, rbs_find** out)
+{
     rbs_find* f = new (std::nothrow) rbs_find;
     if (!f) return fail(sensor, RBS_ERR_OUT_OF_MEMORY, "find_create: out of host memory");
     f->s = sensor;
+    f->part = part;
     f->p = *p;
     auto bail = [&](int32_t rc) { sensor->err = f->err; rbs_find_destroy(f); return rc; };
     const int rows = sensor->rows, cols = sensor->cols;
@@ -1036,23 +1089,15 @@ int32_t rbs_find_create(rbs_handle* sensor, const rbs_find_params* p, rbs_find**
     for (int i = 0; i < 9; ++i) f->cK[i] = sensor->cfg.K[i];
     for (int i = 0; i < 6; ++i) f->cK[i] /= (double)f->f;
     {   // depth offset: mean distance of the vertices from their mean
-        const std::vector<double>& V = sensor->cfg_vertices;
-        const size_t nv = V.size() / 3;
-        double c[3] = {0.0, 0.0, 0.0};
-        for (size_t i = 0; i < nv; ++i)
-            for (int k = 0; k < 3; ++k) c[k] += V[3 * i + k];
-        for (int k = 0; k < 3; ++k) c[k] /= (double)nv;
-        double m = 0.0;
-        for (size_t i = 0; i < nv; ++i) {
-            const double dx = V[3 * i] - c[0], dy = V[3 * i + 1] - c[1], dz = V[3 * i + 2] - c[2];
-            m += std::sqrt(dx * dx + dy * dy + dz * dz);
-        }
-        f->offset = p->depth_offset < 0.0 ? m / (double)nv : p->depth_offset;
+        size_t v0 = 0, t0 = 0;
+        if (part >= 0) part_offsets(sensor, part, &v0, &t0);
+        const size_t nv = part >= 0 ? (size_t)sensor->cfg_vertex_counts[part] : sensor->cfg_vertices.size() / 3;
+        f->offset = p->depth_offset < 0.0 ? mean_vertex_distance(sensor->cfg_vertices.data() + 3 * v0, nv) : p->depth_offset;
     }
     rbf::nms_thresholds(p->nms_translation, p->nms_angle, &f->t2, &f->trace_min);
     const int S = p->n_survivors, nch = S * p->children;
-    if (int32_t rc = make_scorer(f, f->crows, f->ccols, f->cK, p->batch, &f->coarse)) return bail(rc);
-    if (int32_t rc = make_scorer(f, rows, cols, sensor->cfg.K, nch, &f->full)) return bail(rc);
+    if (int32_t rc = make_scorer(sensor, part, &f->err, f->crows, f->ccols, f->cK, p->batch, &f->coarse)) return bail(rc);
+    if (int32_t rc = make_scorer(sensor, part, &f->err, rows, cols, sensor->cfg.K, nch, &f->full)) return bail(rc);
     f->st = f->coarse->stream;
     const long H = (long)p->max_seeds * p->n_rotations;
     f->tk_cap = rbf::topk_items(H, p->n_candidates) + rbf::kTopC;
@@ -1101,9 +1146,9 @@ int32_t rbs_find_create(rbs_handle* sensor, const rbs_find_params* p, rbs_find**
     return RBS_OK;
 }
 
-int32_t rbs_find_run(rbs_find* f, const float* frame, int32_t k, double* poses, double* scores, int32_t* n_out, int32_t* found)
+// rbs_find_run; d_frame != nullptr: the frame lies on the device already (its writers finished) and `frame` is not read
+int32_t find_run(rbs_find* f, const float* frame, const float* d_frame, int32_t k, double* poses, double* scores, int32_t* n_out, int32_t* found)
 {
-    if (!f) return RBS_ERR_INVALID_ARGUMENT;
     if (k < 0 || !n_out || !found) return ffail(f, RBS_ERR_INVALID_ARGUMENT, "find_run: k < 0 or a null n_out / found");
     *n_out = 0;
     *found = 0;
@@ -1112,7 +1157,8 @@ int32_t rbs_find_run(rbs_find* f, const float* frame, int32_t k, double* poses, 
     const rbs_find_params& p = f->p;
     const size_t npx = (size_t)s->npx;
     RBF_HIP(f, hipSetDevice(s->device));
-    if (frame) {
+    if (d_frame) {   // copied below, device to device
+    } else if (frame) {
         std::memcpy(f->h_frame, frame, sizeof(float) * npx);
     } else {   // the sensor's current observation, as rbs_get_observation reads it (waits for the sensor's queued work)
         if (int32_t rc = rbs_get_observation(s, f->h_frame)) return ffail(f, rc, "find_run: sensor: " + s->err);
@@ -1122,7 +1168,8 @@ int32_t rbs_find_run(rbs_find* f, const float* frame, int32_t k, double* poses, 
     RBF_RC(f, f->full, rbs_reset(f->full));
     hipStream_t st = f->st;
     RBF_HIP(f, hipEventRecord(f->ev[0], st));
-    RBF_HIP(f, hipMemcpyAsync(f->d_full, f->h_frame, sizeof(float) * npx, hipMemcpyHostToDevice, st));
+    if (d_frame) RBF_HIP(f, hipMemcpyAsync(f->d_full, d_frame, sizeof(float) * npx, hipMemcpyDeviceToDevice, st));
+    else RBF_HIP(f, hipMemcpyAsync(f->d_full, f->h_frame, sizeof(float) * npx, hipMemcpyHostToDevice, st));
     rbf::launch_subsample(st, f->d_full, s->cols, f->d_coarse, f->crows, f->ccols, f->f);
     const bool fg = f->fg.enabled != 0;
     double* d_rec = reinterpret_cast<double*>(f->d_info + 4);
@@ -1248,6 +1295,16 @@ int32_t rbs_find_run(rbs_find* f, const float* frame, int32_t k, double* poses, 
     if (K > 0 && scores) RBF_HIP(f, hipMemcpy(scores, f->d_final_score, sizeof(double) * K, hipMemcpyDeviceToHost));
     *n_out = K;
     return RBS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t rbs_find_run(rbs_find* f, const float* frame, int32_t k, double* poses, double* scores, int32_t* n_out, int32_t* found)
+{
+    if (!f) return RBS_ERR_INVALID_ARGUMENT;
+    return find_run(f, frame, nullptr, k, poses, scores, n_out, found);
 }
 
 int32_t rbs_find_get_stage(rbs_find* f, int32_t stage, int32_t round, double* poses, double* scores, int64_t* indices, int64_t* n,
@@ -1456,3 +1513,6 @@ int32_t rbs_find_stage_ms(rbs_find* f, float* out5)
 }
 
 }  // extern "C"
+
+// The scene finder (rbs_find_scene_*): the bodies of a model of several, over per-part finders of the above.
+#include "rbsensor_find_scene.hip"

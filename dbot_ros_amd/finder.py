@@ -113,18 +113,22 @@ class ObjectFinder:
         # step 6b, an ObjectFinder.Refinement; None: off (step 6's fixed schedule).  A plain attribute, not a dataclass field:
         # the fields besides `foreground` are rbs_find_params' own, one to one.
         refinement = None
+        # the optional `scene:` mapping, a SceneFinder.Parameters (several objects: node.build_scene_finder); None: its defaults
+        scene = None
 
         @classmethod
         def from_rosparam(cls, tree):
             """From the optional `object_finder:` mapping of the merged rosparam tree; every key is
             optional (angles in degrees: nms_angle_deg, sigma_angle_deg; foreground / refinement: mappings of Foreground's /
-            Refinement's fields)."""
+            Refinement's fields; scene: a mapping of SceneFinder.Parameters' fields)."""
             m = dict((tree or {}).get("object_finder") or {})
             p = cls()
             if "foreground" in m:
                 p.foreground = ObjectFinder.Foreground.from_mapping(m.pop("foreground"))
             if "refinement" in m:
                 p.refinement = ObjectFinder.Refinement.from_mapping(m.pop("refinement"))
+            if "scene" in m:
+                p.scene = SceneFinder.Parameters.from_mapping(m.pop("scene"))
             for k in ("nms_angle", "sigma_angle"):
                 if k + "_deg" in m:
                     m[k] = math.radians(float(m.pop(k + "_deg")))
@@ -301,3 +305,245 @@ class ObjectFinder:
         out = (C.c_float * 5)()
         self._check(self._lib.rbs_find_stage_ms(self._f, out))
         return list(out)
+
+
+@dataclass
+class SceneFindResult:
+    found: np.ndarray     # [B] bool: a searched body has a pose that passed min_score (given bodies: True)
+    searched: np.ndarray  # [B] bool
+    state: np.ndarray     # [B*12] one tracker state of all bodies (caller's mesh frames), for tracker.initialize([state])
+    states: np.ndarray    # [B, 12] the same, per body
+    poses: np.ndarray     # [B, 12] R row-major | t of the sensor's (centred) mesh frames; NaN: a searched body without a pose
+    scores: np.ndarray    # [B] each searched body's score on its residual frame (NaN: given, or no pose)
+    joint_score: float    # the B-body log-likelihood of `poses` on the frame (NaN: a body has no pose)
+    assessment: Optional[object] = None   # find(assess=PoseAssessor): the assess.Assessment of the B poses against the frame
+    confirmed: Optional[np.ndarray] = None   # ... and [B] bool: the body is searched and confirmed (None: no assessor, or a body without a pose)
+
+    @property
+    def all_found(self):
+        return bool(self.found.all())
+
+
+class _BodyFinder(ObjectFinder):
+    """A scene finder's finder of one body (rbs_find_scene_body_finder), borrowed: the inspection methods of
+    ObjectFinder (stage, plane, seed_frame, covariance, perturbations, stage_ms) read that body's last find."""
+
+    def __init__(self, scene, body):
+        self._lib = scene._lib
+        self.sensor = scene.sensor
+        self.params = scene.params
+        self.centers = scene.centers[body:body + 1]
+        self._scene = scene          # (keeps the owner alive)
+        self._f = C.c_void_p(self._lib.rbs_find_scene_body_finder(scene._f, body))
+        if not self._f.value:
+            raise ValueError(f"body {body} outside 0..{scene.parts - 1}")
+        self.foreground, self.refinement = scene.foreground, scene.refinement
+
+    def close(self):
+        self._f = C.c_void_p()
+
+    def find(self, *a, **k):
+        raise TypeError("a scene finder's body finder is borrowed: run SceneFinder.find")
+
+    set_foreground = set_refinement = find
+
+
+class SceneFinder:
+    """SceneFinder(sensor, object_model, params=None, scene=None, foreground=None, refinement=None).find(frame, search, given)
+    -> SceneFindResult: every body of a model of several from one depth frame (rbs_find_scene_*; the rule:
+    include/rbsensor_mi355x.h and DESIGN.md Appendix K).  params: ObjectFinder.Parameters, every body's find."""
+
+    @dataclass
+    class Parameters:
+        """rbs_find_scene_params.  explain_radius and the polish figures are unmeasured starting values."""
+        explain_sigmas: float = 3.0
+        explain_radius: int = 2
+        polish_sweeps: int = 2
+        polish_children: int = 64
+        polish_sigma_translation: float = 0.005
+        polish_sigma_angle: float = math.radians(5.0)
+        polish_decay: float = 0.6
+
+        @classmethod
+        def from_mapping(cls, m):
+            """From the optional `object_finder/scene:` mapping (the angle in degrees: polish_sigma_angle_deg)."""
+            m = dict(m or {})
+            g = cls()
+            if "polish_sigma_angle_deg" in m:
+                m["polish_sigma_angle"] = math.radians(float(m.pop("polish_sigma_angle_deg")))
+            names = [f.name for f in fields(cls)]
+            for k, v in m.items():
+                if k not in names:
+                    raise ValueError(f"object_finder/scene/{k}: unknown key (one of {sorted(names + ['polish_sigma_angle_deg'])})")
+                setattr(g, k, int(v) if isinstance(getattr(g, k), int) else float(v))
+            return g
+
+        def c_params(self):
+            p = _capi.RbsFindSceneParams()
+            for f in fields(self):
+                setattr(p, f.name, getattr(self, f.name))
+            p.reserved = 0
+            return p
+
+    def __init__(self, sensor, object_model, params=None, scene=None, foreground=None, refinement=None):
+        self._lib = _capi.load()
+        self.sensor = sensor
+        self.params = params or ObjectFinder.Parameters()
+        self.scene = scene or SceneFinder.Parameters()
+        self.centers = np.array(object_model.centers, dtype=np.float64).reshape(-1, 3)
+        self.parts = len(self.centers)
+        self._f = C.c_void_p()
+        cp, sp = self.params.c_params(), self.scene.c_params()
+        rc = self._lib.rbs_find_scene_create(sensor._h, C.byref(cp), C.byref(sp), C.byref(self._f))
+        if rc != 0:
+            self._f = C.c_void_p()
+            sensor._check(rc)
+        sensor._register_dependent(self)   # the scene finder borrows the sensor handle
+        self.foreground = self.refinement = None
+        foreground = self.params.foreground if foreground is None else foreground
+        refinement = self.params.refinement if refinement is None else refinement
+        try:
+            if foreground is not None:
+                self.set_foreground(foreground)
+            if refinement is not None:
+                self.set_refinement(refinement)
+        except Exception:
+            self.close()
+            raise
+
+    def close(self):
+        if getattr(self, "_f", None) is not None and self._f.value:
+            self._lib.rbs_find_scene_destroy(self._f)
+            self._f = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def _check(self, rc):
+        if rc != 0:
+            raise RbSensorError(rc, self._lib.rbs_find_scene_last_error(self._f).decode())
+
+    def set_foreground(self, foreground=None):
+        """Step 1b of every body's find, as ObjectFinder.set_foreground."""
+        on = foreground is not None and foreground.enabled
+        g = foreground.c_params() if on else None
+        self._check(self._lib.rbs_find_scene_set_foreground(self._f, C.byref(g) if on else None))
+        self.foreground = foreground if on else None
+
+    def set_refinement(self, refinement=None):
+        """Step 6b of every body's find, as ObjectFinder.set_refinement."""
+        on = refinement is not None and refinement.enabled
+        g = refinement.c_params() if on else None
+        self._check(self._lib.rbs_find_scene_set_refinement(self._f, C.byref(g) if on else None))
+        self.refinement = refinement if on else None
+
+    def mask_of(self, search):
+        """None: every body; an int: the mask itself; else the bodies' indices."""
+        if search is None:
+            return (1 << self.parts) - 1
+        if isinstance(search, (int, np.integer)):
+            return int(search)
+        m = 0
+        for b in search:
+            if not 0 <= int(b) < 32:
+                raise ValueError(f"search: body {b} outside 0..31")
+            m |= 1 << int(b)
+        return m
+
+    def poses_of_state(self, state):
+        """A tracker state [B*12] (caller's mesh frames) -> poses [B, 12] of the sensor's mesh frames."""
+        from .pose import pack_Rt, rotvec_to_matrix
+        s = np.asarray(state, dtype=np.float64).reshape(self.parts, 12)
+        R = rotvec_to_matrix(s[:, 3:6]).reshape(self.parts, 3, 3)
+        t = s[:, 0:3] + np.einsum("bij,bj->bi", R, self.centers)
+        return pack_Rt(R, t).reshape(self.parts, 12)
+
+    def find(self, frame=None, search=None, given=None, assess=None, given_poses=None):
+        """frame: rows*cols depth at the sensor's resolution (None: the sensor's current observation).  search: the bodies
+        to place (None: all; indices or a bit mask).  The others' poses: given, a tracker state [B*12] in the caller's mesh
+        frames (a tracker's estimate), or given_poses [B, 12] in the sensor's mesh frames, which come back bit for bit.
+        assess: a PoseAssessor over the same sensor -- the B poses are judged against the same frame and `confirmed` names
+        the searched bodies that read SUPPORTED (with the contour rule on: and PRESENT)."""
+        mask = self.mask_of(search)
+        B = self.parts
+        gp = None
+        if given_poses is not None:
+            gp = np.ascontiguousarray(given_poses, dtype=np.float64).reshape(B, 12)
+        elif given is not None:
+            gp = np.ascontiguousarray(self.poses_of_state(given))
+        img = None
+        if frame is not None:
+            img = np.ascontiguousarray(frame, dtype=np.float32).ravel()
+            if img.size != self.sensor.rows * self.sensor.cols:
+                raise ValueError(f"frame has {img.size} pixels, the sensor {self.sensor.rows * self.sensor.cols}")
+        poses = np.zeros((B, 12))
+        scores = np.zeros(B)
+        found, joint = C.c_uint32(), C.c_double()
+        dp = C.POINTER(C.c_double)
+        self._check(self._lib.rbs_find_scene_run(self._f, img.ctypes.data_as(C.POINTER(C.c_float)) if img is not None else None,
+                                                 C.c_uint32(mask & 0xFFFFFFFF), gp.ctypes.data_as(dp) if gp is not None else None,
+                                                 poses.ctypes.data_as(dp), scores.ctypes.data_as(dp), C.byref(found), C.byref(joint)))
+        searched = np.array([bool(mask >> b & 1) for b in range(B)])
+        fnd = np.array([bool(found.value >> b & 1) for b in range(B)]) | ~searched
+        states = np.full((B, 12), np.nan)
+        for b in range(B):
+            if np.isfinite(poses[b]).all():
+                R = poses[b, :9].reshape(3, 3)
+                states[b] = 0.0
+                states[b, 0:3] = poses[b, 9:12] - R @ self.centers[b]
+                states[b, 3:6] = matrix_to_rotvec(R)
+        res = SceneFindResult(fnd, searched, states.ravel().copy(), states, poses, scores, float(joint.value))
+        if assess is not None and np.isfinite(poses).all():
+            from .assess import SUPPORTED
+            res.assessment = assess.assess(poses[None], img)
+            ok = np.asarray(res.assessment.verdicts).reshape(-1)[:B] == SUPPORTED
+            if res.assessment.contour_verdicts is not None:
+                from .assess import CONTOUR_PRESENT
+                ok &= np.asarray(res.assessment.contour_verdicts).reshape(-1)[:B] == CONTOUR_PRESENT
+            res.confirmed = ok & searched
+        return res
+
+    def order(self):
+        """The last scene find's S1: (the searched bodies in the order taken, e [B])."""
+        order = (C.c_int32 * 32)()
+        n = C.c_int32()
+        e = np.zeros(self.parts)
+        self._check(self._lib.rbs_find_scene_get_order(self._f, order, C.byref(n), e.ctypes.data_as(C.POINTER(C.c_double))))
+        return [int(order[i]) for i in range(n.value)], e
+
+    def residual(self, body):
+        """The residual frame [rows, cols] float32 that searched body `body` was found on."""
+        out = np.zeros(self.sensor.rows * self.sensor.cols, dtype=np.float32)
+        self._check(self._lib.rbs_find_scene_get_residual(self._f, int(body), out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out.reshape(self.sensor.rows, self.sensor.cols)
+
+    def body_finder(self, body):
+        """Body `body`'s finder, borrowed, for inspection (ObjectFinder.stage and the like)."""
+        return _BodyFinder(self, int(body))
+
+    def polish(self, round):
+        """Polish round `round` of the last scene find: (children poses [n, B, 12], joint scores [n], the child taken)."""
+        n, best = C.c_int32(), C.c_int32()
+        self._check(self._lib.rbs_find_scene_get_polish(self._f, int(round), None, None, C.byref(n), None))
+        poses = np.zeros((n.value, self.parts, 12))
+        scores = np.zeros(n.value)
+        dp = C.POINTER(C.c_double)
+        self._check(self._lib.rbs_find_scene_get_polish(self._f, int(round), poses.ctypes.data_as(dp), scores.ctypes.data_as(dp),
+                                                        C.byref(n), C.byref(best)))
+        return poses, scores, int(best.value)
+
+    def stage_ms(self):
+        """ms of the last scene find: (per body [B], render kernel, residual kernel, polish, whole)."""
+        per = (C.c_float * max(self.parts, 1))()
+        out = (C.c_float * 4)()
+        self._check(self._lib.rbs_find_scene_stage_ms(self._f, per, out))
+        return list(per)[:self.parts], out[0], out[1], out[2], out[3]

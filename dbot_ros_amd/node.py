@@ -104,6 +104,28 @@ def build_object_finder(params, native_camera_matrix, mesh_package_path, device_
             object_model, camera_data)
 
 
+def build_scene_finder(params, native_camera_matrix, mesh_package_path, device_id=0, sensor=None):
+    """build_object_finder for a tree of several objects: a SceneFinder (dbot_ros_amd/finder.py) over every mesh of
+    object/meshes.  Its per-body search is the `object_finder:` mapping's (foreground: and refinement: included), its own
+    parameters the optional `object_finder/scene:` sub-mapping (SceneFinder.Parameters' fields; unknown keys: ValueError).
+    Returns (scene finder, object_model, camera_data); close the finder, then a sensor built here (finder.sensor)."""
+    from .finder import ObjectFinder, SceneFinder
+    pre = params["particle_filter"]
+    obj = params["object"]
+    ori = ObjectResourceIdentifier(mesh_package_path, obj["directory"], obj["meshes"])
+    vs, ts = SimpleWavefrontObjectModelLoader(ori).load()
+    object_model = ObjectModel(vs, ts, center=bool(pre["center_object_frame"]))
+    camera_data = CameraData.from_native(native_camera_matrix, int(params["resolution"]["width"]),
+                                         int(params["resolution"]["height"]), int(params["downsampling_factor"]))
+    finder_params = ObjectFinder.Parameters.from_rosparam(params)
+    if sensor is None:
+        params_obsrv = RbSensorBuilder.Parameters.from_rosparam(params)
+        params_obsrv.sample_count = 1
+        sensor = RbSensorBuilder(object_model, camera_data, params_obsrv, device_id=device_id).build()
+    return (SceneFinder(sensor, object_model, finder_params, finder_params.scene, foreground=finder_params.foreground,
+                        refinement=finder_params.refinement), object_model, camera_data)
+
+
 def to_eigen_vector(native_image, downsampling_factor):
     """ri::to_eigen_vector (R:source/dbot_ros/util/ros_interface.h:152-168) on the host."""
     img = np.asarray(native_image)
@@ -124,7 +146,8 @@ def replay_dataset(params, dataset, mesh_package_path, initial_states=None, devi
     same numbers); False drives tracker.track frame by frame as a live camera would.
     initial_states=None: the controller's auto_detect + auto_confirm path
     (R:source/dbot_ros/tracker/object_tracker_controller_service_node.cpp:143-167) -- the object is found on frame 0
-    by an object finder over the tracker's own sensor, and the tracker starts from its best state.
+    by an object finder over the tracker's own sensor, and the tracker starts from its best state; a tree of several
+    objects takes a scene finder (build_scene_finder) and starts from the one state of all its bodies.
     Returns (estimates [frames, parts*12], wall seconds of the tracking loop)."""
     import time
     tracker, object_model, camera_data, _ = build_particle_tracker(params, dataset.get_camera_matrix(0),
@@ -133,7 +156,17 @@ def replay_dataset(params, dataset, mesh_package_path, initial_states=None, devi
     try:
         n = dataset.size() if max_frames is None else min(max_frames, dataset.size())
         frames = [dataset.frame_vector(i, f) for i in range(n)]      # host decode outside the timed loop
-        if initial_states is None:
+        if initial_states is None and tracker.parts > 1:
+            finder, _, _ = build_scene_finder(params, dataset.get_camera_matrix(0), mesh_package_path, device_id=device_id,
+                                              sensor=tracker.sensor)
+            try:
+                found = finder.find(frames[0])
+            finally:
+                finder.close()
+            if not found.all_found:
+                raise RuntimeError("replay_dataset: the scene finder did not find every object on frame 0")
+            initial_states = [found.state]
+        elif initial_states is None:
             finder, _, _ = build_object_finder(params, dataset.get_camera_matrix(0), mesh_package_path, device_id=device_id,
                                                sensor=tracker.sensor)
             try:
@@ -172,8 +205,9 @@ def replay_dataset_supervised(params, dataset, mesh_package_path, initial_states
     fields), contour: (PoseAssessor.ContourParameters' fields; its presence, even empty, switches the contour rule on: a
     find is then confirmed only when its silhouette reads PRESENT too), contour_lost: (false; with contour: a body whose
     contour verdict is ABSENT makes the frame count as lost).  initial_states=None: the object is found on frame 0 and the find must be CONFIRMED -- the first returned pose
-    that reads SUPPORTED starts the tracker; none: RuntimeError.  With initial states and several objects there is no finder:
-    the supervisor only reports.  Returns (estimates [frames, parts*12], verdicts [frames, parts], events [frames] of
+    that reads SUPPORTED starts the tracker; none: RuntimeError.  Several objects: a scene finder (build_scene_finder) finds all of
+    them on frame 0 -- every body must be confirmed -- and re-finds the bodies that count as lost, given the others' estimates
+    (TrackSupervisor's find_bodies).  Returns (estimates [frames, parts*12], verdicts [frames, parts], events [frames] of
     None / "lost" / "reacquired" / "find_failed")."""
     from .assess import PoseAssessor
     from .supervisor import TrackSupervisor
@@ -193,7 +227,15 @@ def replay_dataset_supervised(params, dataset, mesh_package_path, initial_states
         n = dataset.size() if max_frames is None else min(max_frames, dataset.size())
         frames = [dataset.frame_vector(i, f) for i in range(n)]
         assessor = PoseAssessor(tracker.sensor, assess_params, contour_params)
-        find = None
+        find = find_bodies = None
+        if tracker.parts > 1:
+            finder, _, _ = build_scene_finder(params, dataset.get_camera_matrix(0), mesh_package_path, device_id=device_id,
+                                              sensor=tracker.sensor)
+
+            def find_bodies(frame, lost, estimate):
+                search = np.nonzero(lost)[0]
+                r = finder.find(frame, search=search, given=None if len(search) == tracker.parts else estimate, assess=assessor)
+                return r.state if r.confirmed is not None and bool(r.confirmed[search].all()) else None
         if tracker.parts == 1:
             finder, _, _ = build_object_finder(params, dataset.get_camera_matrix(0), mesh_package_path, device_id=device_id,
                                                sensor=tracker.sensor)
@@ -202,14 +244,12 @@ def replay_dataset_supervised(params, dataset, mesh_package_path, initial_states
                 r = finder.find(frame, assess=assessor)
                 return r.states[r.confirmed] if r.confirmed is not None and r.confirmed >= 0 else None
         if initial_states is None:
-            if find is None:
-                raise ValueError("replay_dataset_supervised: the object finder searches for one object; pass initial_states")
-            state = find(frames[0])
+            state = find(frames[0]) if find is not None else find_bodies(frames[0], np.ones(tracker.parts, dtype=bool), None)
             if state is None:
                 raise RuntimeError("replay_dataset_supervised: no find on frame 0 was confirmed by the assessor")
             initial_states = [state]
         tracker.initialize(initial_states)
-        sup = TrackSupervisor(tracker, assessor, find=find, lost_frames=int(m.get("lost_frames", 3)),
+        sup = TrackSupervisor(tracker, assessor, find=find, find_bodies=find_bodies, lost_frames=int(m.get("lost_frames", 3)),
                               occluded_frames=int(m.get("occluded_frames", 0)), contour_lost=bool(m.get("contour_lost", False)))
         ests, verdicts, events = [], [], []
         for fr in frames:

@@ -6,11 +6,11 @@ found pose that the assessor confirms.  Host logic only: the tracker, the assess
 """
 import numpy as np
 
-from .assess import CONTOUR_ABSENT, LOST, OCCLUDED, SUPPORTED
+from .assess import CONTOUR_ABSENT, CONTOUR_PRESENT, LOST, OCCLUDED, SUPPORTED
 
 
 class TrackSupervisor:
-    """TrackSupervisor(tracker, assessor, find=None, lost_frames=3, occluded_frames=0).step(frame) ->
+    """TrackSupervisor(tracker, assessor, find=None, lost_frames=3, occluded_frames=0, find_bodies=None).step(frame) ->
     (estimate, verdicts [parts], event).
 
     tracker   .track(frame) -> State, .initialize([state]), .parts; driven frame by frame only.
@@ -25,9 +25,16 @@ class TrackSupervisor:
     lost ends the run.  Other frames: event None.
     With the assessor's contour rule on (PoseAssessor(contour=...)) a found state must pass Assessment.confirmed_mask():
     SUPPORTED and its silhouette PRESENT.  contour_lost=True (it needs that rule) also counts a frame as lost when a
-    body's contour verdict is ABSENT."""
+    body's contour verdict is ABSENT.
+    find_bodies  None, or find_bodies(frame, lost [parts] bool, estimate) -> a State (parts*12) or None, for any number of
+    parts (a SceneFinder: dbot_ros_amd/finder.py): in place of `find`, at the same moments.  `lost` names the bodies that
+    make the frame count as lost (LOST, OCCLUDED for too long, or -- with contour_lost -- a silhouette that reads ABSENT);
+    only those are to be searched, the others keep the estimate's poses.  The found state is confirmed on the searched
+    bodies alone: each SUPPORTED (and PRESENT with the contour rule on); the others' verdicts do not count.  `find` and its
+    one-object limit stay as they are; both at once: ValueError."""
 
-    def __init__(self, tracker, assessor, find=None, lost_frames=3, occluded_frames=0, look_ahead=False, contour_lost=False):
+    def __init__(self, tracker, assessor, find=None, lost_frames=3, occluded_frames=0, look_ahead=False, contour_lost=False,
+                 find_bodies=None):
         if look_ahead:
             raise ValueError("TrackSupervisor drives the tracker frame by frame: a verdict decides what the next frame starts from")
         if int(lost_frames) < 1 or int(occluded_frames) < 0:
@@ -36,6 +43,9 @@ class TrackSupervisor:
         self.parts = int(tracker.parts)
         if find is not None and self.parts != 1:
             raise ValueError("TrackSupervisor: a finder searches for one object; this tracker has %d" % self.parts)
+        if find is not None and find_bodies is not None:
+            raise ValueError("TrackSupervisor: find and find_bodies are alternatives")
+        self.find_bodies = find_bodies
         self.lost_frames, self.occluded_frames = int(lost_frames), int(occluded_frames)
         self.contour_lost = bool(contour_lost)
         if self.contour_lost and getattr(assessor, "contour", None) is None:
@@ -57,16 +67,17 @@ class TrackSupervisor:
         self.last = self.assessor.assess_state(self.tracker, est, frame)
         verdicts = np.asarray(self.last.verdicts).reshape(-1)[:self.parts].copy()
         self.occluded_run = np.where(verdicts == OCCLUDED, self.occluded_run + 1, 0)
-        lost = bool((verdicts == LOST).any())
-        if self.occluded_frames > 0 and bool((self.occluded_run > self.occluded_frames).any()):
-            lost = True
-        if self.contour_lost and bool((np.asarray(self.last.contour_verdicts).reshape(-1)[:self.parts] == CONTOUR_ABSENT).any()):
-            lost = True
+        lost_bodies = verdicts == LOST                       # the bodies that make this frame count as lost
+        if self.occluded_frames > 0:
+            lost_bodies = lost_bodies | (self.occluded_run > self.occluded_frames)
+        if self.contour_lost:
+            lost_bodies = lost_bodies | (np.asarray(self.last.contour_verdicts).reshape(-1)[:self.parts] == CONTOUR_ABSENT)
+        lost = bool(lost_bodies.any())
         if not lost:
             self.lost_run, self.next_attempt = 0, None
             return est, verdicts, None
         self.lost_run += 1
-        if self.find is None:
+        if self.find is None and self.find_bodies is None:
             return est, verdicts, "lost" if self.lost_run % self.lost_frames == 0 else None
         if self.next_attempt is None:
             if self.lost_run < self.lost_frames:
@@ -76,14 +87,19 @@ class TrackSupervisor:
         if self.lost_run < self.next_attempt:
             return est, verdicts, None
         self.next_attempt = self.lost_run + self.lost_frames
-        state = self.find(frame)
+        state = self.find(frame) if self.find is not None else self.find_bodies(frame, lost_bodies.copy(), est)
         if state is None:
             return est, verdicts, "find_failed"
         state = np.asarray(state, dtype=np.float64).reshape(-1)
         found = self.assessor.assess_state(self.tracker, state, frame)
-        ok = bool((np.asarray(found.verdicts).reshape(-1) == SUPPORTED).all())
-        if getattr(found, "contour_verdicts", None) is not None:
-            ok = bool(found.confirmed_mask().all())
+        if self.find is not None:
+            ok = bool((np.asarray(found.verdicts).reshape(-1) == SUPPORTED).all())
+            if getattr(found, "contour_verdicts", None) is not None:
+                ok = bool(found.confirmed_mask().all())
+        else:   # only the searched bodies are confirmed
+            ok = bool((np.asarray(found.verdicts).reshape(-1)[:self.parts][lost_bodies] == SUPPORTED).all())
+            if getattr(found, "contour_verdicts", None) is not None:
+                ok = ok and bool((np.asarray(found.contour_verdicts).reshape(-1)[:self.parts][lost_bodies] == CONTOUR_PRESENT).all())
         if not ok:
             return est, verdicts, "find_failed"
         self.tracker.initialize([state])

@@ -8,6 +8,8 @@
 // States are in the caller's mesh frame (center_object_frame undone) with zero velocities; poses are R|t of the
 // sensor's (centred) mesh frame, as the C-ABI returns them.
 //
+// SceneFinder below mirrors the scene finder (rbs_find_scene_*) the same way, for models of several objects.
+//
 // Header-only; link with -lrbsensor_mi355x.  No CPU fallback: without a device the sensor cannot be built.
 #pragma once
 
@@ -143,6 +145,7 @@ public:
     rbs_find* handle() { return f_; }
 
 private:
+    friend class SceneFinder;   // (rotation_vector)
     /// row-major rotation matrix -> rotation vector (atan2 form, as dbot_ros_amd.pose.matrix_to_rotvec)
     static void rotation_vector(const Real* R, Real* rv)
     {
@@ -171,6 +174,106 @@ private:
     std::shared_ptr<ObjectModel> om_;
     int k_;
     rbs_find* f_ = nullptr;
+};
+
+/// The scene finder (rbs_find_scene_*): every body of a model of several from one depth frame.
+///     SceneFinder finder(sensor, object_model, find_params, scene_params);
+///     SceneFinder::Result r = finder.find(image);          // r.all_found() -> tracker->initialize({r.state})
+/// `search` names the bodies to place (bit b = body b; 0: all); the poses of the others are given, [B][12] in the sensor's
+/// mesh frames, and come back bit for bit.
+class SceneFinder
+{
+public:
+    typedef ObjectFinder::State State;
+    typedef ObjectFinder::Obsrv Obsrv;
+
+    /// rbs_find_scene_params with the library's defaults (the optional object_finder/scene: rosparam mapping overrides fields).
+    struct Parameters : rbs_find_scene_params {
+        Parameters() { rbs_find_scene_default_params(this); }
+    };
+
+    struct Result {
+        uint32_t searched = 0, found = 0;   // bit b: body b was searched / has a pose that passed min_score
+        State state = State(0);             // all bodies, the caller's mesh frames (valid when every body has a pose)
+        std::vector<Real> poses;            // [B][12]; NaN: a searched body without a pose
+        std::vector<Real> scores;           // [B] on each body's residual frame; NaN: given, or no pose
+        Real joint_score = 0;               // NaN: a body has no pose
+        bool all_found() const { return searched != 0 && (found & searched) == searched; }
+    };
+
+    SceneFinder(const std::shared_ptr<RbSensor<State>>& sensor, const std::shared_ptr<ObjectModel>& om,
+                const ObjectFinder::Parameters& p = ObjectFinder::Parameters(), const Parameters& sp = Parameters())
+        : sensor_(sensor), om_(om), parts_(om->count_parts())
+    {
+        if (rbs_find_scene_create(sensor_->handle(), &p, &sp, &f_) != RBS_OK)
+            throw std::runtime_error(std::string("SceneFinder: ") + rbs_last_error(sensor_->handle()));
+    }
+    ~SceneFinder() { rbs_find_scene_destroy(f_); }
+    SceneFinder(const SceneFinder&) = delete;
+    SceneFinder& operator=(const SceneFinder&) = delete;
+
+    int parts() const { return parts_; }
+
+    /// One scene find on `image` (the sensor's resolution; empty: the sensor's current observation).
+    Result find(const Obsrv& image = Obsrv(), uint32_t search = 0, const std::vector<Real>& given_poses = std::vector<Real>())
+    {
+        const size_t B = static_cast<size_t>(parts_);
+        Result r;
+        r.searched = search ? search : (parts_ >= 32 ? 0xFFFFFFFFu : (1u << parts_) - 1u);
+        if (!given_poses.empty() && given_poses.size() != 12 * B) throw std::invalid_argument("SceneFinder::find: given_poses is not [B][12]");
+        r.poses.assign(12 * B, 0.0);
+        r.scores.assign(B, 0.0);
+        if (rbs_find_scene_run(f_, image.empty() ? nullptr : image.data(), r.searched, given_poses.empty() ? nullptr : given_poses.data(),
+                               r.poses.data(), r.scores.data(), &r.found, &r.joint_score) != RBS_OK)
+            throw std::runtime_error(std::string("SceneFinder::find: ") + rbs_find_scene_last_error(f_));
+        const Real* c = om_->centers().data();
+        r.state = State(parts_);
+        for (size_t b = 0; b < B; ++b) {
+            const Real* P = r.poses.data() + 12 * b;
+            for (int k = 0; k < 3; ++k)
+                r.state.position(b)[k] = P[9 + k] - (P[3 * k] * c[3 * b] + P[3 * k + 1] * c[3 * b + 1] + P[3 * k + 2] * c[3 * b + 2]);
+            ObjectFinder::rotation_vector(P, r.state.euler_vector(b));
+        }
+        return r;
+    }
+
+    /// Steps 1b / 6b of every body's find; nullptr (or enabled == 0): off.  Bad values throw, the previous setting stays.
+    void set_foreground(const rbs_find_foreground* g)
+    {
+        if (rbs_find_scene_set_foreground(f_, g) != RBS_OK)
+            throw std::runtime_error(std::string("SceneFinder::set_foreground: ") + rbs_find_scene_last_error(f_));
+    }
+    void set_refinement(const rbs_find_refinement* g)
+    {
+        if (rbs_find_scene_set_refinement(f_, g) != RBS_OK)
+            throw std::runtime_error(std::string("SceneFinder::set_refinement: ") + rbs_find_scene_last_error(f_));
+    }
+
+    /// The last scene find's S1: the searched bodies in the order they were taken.
+    std::vector<int> order()
+    {
+        int32_t o[32], n = 0;
+        if (rbs_find_scene_get_order(f_, o, &n, nullptr) != RBS_OK)
+            throw std::runtime_error(std::string("SceneFinder::order: ") + rbs_find_scene_last_error(f_));
+        return std::vector<int>(o, o + n);
+    }
+
+    /// The residual frame searched body `body` was found on (rows x cols: the sensor's resolution).
+    std::vector<float> residual(int body, int rows, int cols)
+    {
+        std::vector<float> out(static_cast<size_t>(rows) * static_cast<size_t>(cols));
+        if (rbs_find_scene_get_residual(f_, body, out.data()) != RBS_OK)
+            throw std::runtime_error(std::string("SceneFinder::residual: ") + rbs_find_scene_last_error(f_));
+        return out;
+    }
+
+    rbs_find_scene* handle() { return f_; }
+
+private:
+    std::shared_ptr<RbSensor<State>> sensor_;
+    std::shared_ptr<ObjectModel> om_;
+    int parts_;
+    rbs_find_scene* f_ = nullptr;
 };
 
 }  // namespace dbot_amd

@@ -815,6 +815,101 @@ int32_t rbs_find_get_perturbations(rbs_find* f, int32_t round, double* d, int64_
 const char* rbs_find_last_error(const rbs_find* f);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * The scene finder: every body of a model of several from one depth frame (rbsensor_find_scene.hip; DESIGN.md
+ * Appendix K).  An object beside rbs_find, which keeps its one-object limit.  It places the bodies named in a `search`
+ * mask of a sensor of B bodies (1 <= B <= 16), given the poses of the others: greedily, body by body, each on a RESIDUAL
+ * FRAME from which what the bodies placed so far explain is taken out, and at the end all together under the B-body
+ * likelihood.  Everything below is binary64 with + - x / and comparisons and the finder's own steps, in the order written;
+ * tests/scene_find_twin.py restates it in numpy and takes every decision bit for bit.
+ *   S1 order     e_b = the mean distance of part b's vertices from their mean (rbs_find_create's depth_offset default, in
+ *                that order of operations).  The searched bodies are taken by e_b descending, ties to the lower b.
+ *   S2 residual  for the body about to be searched.  PLACED bodies are the given ones (not in `search`) and every searched
+ *                body already handled whose find returned a pose with `found` set.  d_c, for the placed bodies c, are the
+ *                assess rule's planes (the body rendered alone, +inf where it covers nothing); the owner of a pixel is the
+ *                nearest placed body, ties to the lowest; an owned pixel j with a finite reading y_j is SUPPORT by the
+ *                assess rule's test: d = d_owner(j), r = (double)y_j - (double)d,
+ *                tau = explain_sigmas x (model_sigma + sigma_factor x (d x d)), neither r < -tau nor r > tau.
+ *                Pixel i is EXPLAINED when (a) it is support, or (b) y_i is finite and some support pixel j of the
+ *                Chebyshev window |x_i - x_j| <= explain_radius, |y_i - y_j| <= explain_radius (clipped to the image) has
+ *                neither r < -tau nor r > tau with r = (double)y_i - (double)d(j) and tau from d(j).  (b) is an OR over j:
+ *                it does not depend on an order; explain_radius = 0 leaves (a).  residual(i) is the float quiet NaN
+ *                0x7FC00000 where i is explained and frame(i) bit for bit elsewhere, the frame's own NaNs included.  No
+ *                placed body: the residual is the frame.
+ *   S3 a body    rbs_find_run's steps 1-7 (with 1b / 6b as set on the scene finder) with the scene finder's
+ *                rbs_find_params, the same seed for every body, for the one-body model made of part b -- every other
+ *                rbs_config field the sensor's -- on the residual frame, for seeding and for scoring at both resolutions.
+ *                The likelihood skips a NaN reading: a hypothesis laid on an explained blob scores about 0, one on the
+ *                body's own blob its full support.  The body's pose is the best survivor, found_b is rbs_find_run's
+ *                `found`.  A body without a pose or without `found` is not placed.
+ *   S4 polish    only when every body of the model has a pose (else it is skipped and the joint score is NaN).  X is the
+ *                B poses; the ns searched bodies are polished in S1's order.  Round r = 0 .. polish_sweeps x ns - 1 moves
+ *                body c = order[r mod ns] in sweep w = r div ns with st = polish_sigma_translation x polish_decay^w,
+ *                sa = polish_sigma_angle x polish_decay^w (repeated multiplication, as step 6).  Child 0 is X; child j > 0
+ *                is X with body c's (R, t) replaced by step 6's perturbation R(sa n) R, t + st n', the six normals step 6's
+ *                Box-Muller pairs of Philox4x32-10 with key = seed and counter (j << 2 | p, (0x10000 + r) << 32 | c):
+ *                disjoint from step 6 (its round <= 64) and from step 1b (last word 0xFFFFFFFF).  All polish_children
+ *                children are scored on the ORIGINAL frame by a B-body scoring handle: rbs_loglikes(update = 0) on a
+ *                freshly reset handle of the sensor's configuration at its resolution, one occlusion slot, the finder's
+ *                fixed tile split.  X becomes the best child, ties to the lowest j, NaN never beats a number: the joint
+ *                score never goes down.  The joint score is the final X's; polish_sweeps = 0: X is scored once.
+ *   output       poses [B][12] (given bodies bit for bit; a searched body without a pose: NaN), per-body scores [B] (S3's
+ *                residual-frame score; NaN for given bodies and bodies without a pose), the found mask, the joint score.
+ *
+ * explain_sigmas = 3 is the assessor's reading of the sensor's own noise model.  explain_radius and the four polish
+ * figures are starting values that nobody has measured against data (policy, like Appendix J's): DESIGN.md Appendix K.
+ *
+ * A scene find does not touch the sensor's state, and frame == NULL reads the sensor's observation as rbs_find_run does.
+ * It owns one per-part finder per body and the B-body scoring handle (memory: B times a finder's, one frame per body for
+ * the residuals, B planes).  Limits: single-device handles (RBS_ERR_UNSUPPORTED otherwise).  RBS_ERR_INVALID_ARGUMENT,
+ * with the last find's results kept: search_mask 0 or with bits >= B, given_poses == NULL while a body is not searched,
+ * a given pose that is not finite, bad parameters.  Driven by one thread at a time; destroyed before its sensor. */
+typedef struct rbs_find_scene rbs_find_scene;
+
+typedef struct rbs_find_scene_params {   /* 48 bytes */
+    double explain_sigmas;             /* 3 (finite, > 0)                                                            */
+    int32_t explain_radius;            /* 2 pixels (0 .. 8) (policy, unmeasured)                                     */
+    int32_t polish_sweeps;             /* 2 (0 .. 8) (policy, unmeasured)                                            */
+    int32_t polish_children;           /* 64 (1 .. 1 024) (policy, unmeasured)                                       */
+    int32_t reserved;                  /* 0                                                                          */
+    double polish_sigma_translation;   /* 0.005 (metres; finite, >= 0) (policy, unmeasured)                          */
+    double polish_sigma_angle;         /* 5 degrees, in radians (finite, >= 0) (policy, unmeasured)                  */
+    double polish_decay;               /* 0.6, in (0, 1] (policy, unmeasured)                                        */
+} rbs_find_scene_params;
+
+/* The defaults above, stated once. */
+void rbs_find_scene_default_params(rbs_find_scene_params* p);
+/* The scene finder over the sensor's model, camera, parameters and device.  find_params: every body's find (S3);
+ * scene_params: NULL = the defaults. */
+int32_t rbs_find_scene_create(rbs_handle* sensor, const rbs_find_params* find_params, const rbs_find_scene_params* scene_params,
+                              rbs_find_scene** out);
+void rbs_find_scene_destroy(rbs_find_scene* f);
+/* Steps 1b / 6b of every body's find, as rbs_find_set_foreground / rbs_find_set_refinement. */
+int32_t rbs_find_scene_set_foreground(rbs_find_scene* f, const rbs_find_foreground* g);
+int32_t rbs_find_scene_set_refinement(rbs_find_scene* f, const rbs_find_refinement* g);
+/* One scene find.  frame: rows*cols floats (NULL: the sensor's current observation); search_mask: bit b = body b is
+ * searched; given_poses [B][12] (read for the bodies not searched; may be NULL when all are searched); out_poses [B][12],
+ * out_scores [B] (either may be NULL); *found_mask: bit b = searched body b has a pose with `found`; *joint_score. */
+int32_t rbs_find_scene_run(rbs_find_scene* f, const float* frame, uint32_t search_mask, const double* given_poses,
+                           double* out_poses, double* out_scores, uint32_t* found_mask, double* joint_score);
+/* Inspection of the last scene find, for the tests.  get_order: order [*n] := the searched bodies in S1's order, e [B]
+ * (may be NULL) := every body's e_b.  get_residual: out [rows*cols] := the residual frame searched body `body` was found on.
+ * body_finder: body b's finder, borrowed (NULL for a bad b): rbs_find_get_stage, _get_plane, _get_seed_frame,
+ * _get_covariance, _get_perturbations and _stage_ms read that body's last find; it must not be run or destroyed.
+ * get_polish: round `round`'s children poses [*n][B][12] and joint scores [*n] (either may be NULL), *best := the child
+ * taken; polish_sweeps = 0: round 0 is X alone, *n = 1.  A polish that was skipped, a bad round or body, no scene find
+ * yet: RBS_ERR_INVALID_ARGUMENT. */
+int32_t rbs_find_scene_get_order(rbs_find_scene* f, int32_t* order, int32_t* n, double* e);
+int32_t rbs_find_scene_get_residual(rbs_find_scene* f, int32_t body, float* out);
+rbs_find* rbs_find_scene_body_finder(rbs_find_scene* f, int32_t body);
+int32_t rbs_find_scene_get_polish(rbs_find_scene* f, int32_t round, double* poses, double* scores, int32_t* n, int32_t* best);
+/* Time of the last scene find in ms: per_body [B] (may be NULL) := each searched body's whole find (its device time, 0 for
+ * given bodies); out4 := the render kernel and the residual kernel (device time, summed over the searched bodies), the
+ * polish (device time), the whole scene find (host wall time, uploads and synchronisations included). */
+int32_t rbs_find_scene_stage_ms(rbs_find_scene* f, float* per_body, float* out4);
+/* Message of the last error on this scene finder. Never NULL. */
+const char* rbs_find_scene_last_error(const rbs_find_scene* f);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Poses judged against one depth frame (rbsensor_assess.hip).
  *
  * The reference leaves this judgement to a person: its controller shows the found pose in rviz and waits for a click

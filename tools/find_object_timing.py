@@ -24,6 +24,11 @@ the oracle's timing.  --refinement switches step 6b on (the library's default se
 Usage: python tools/find_object_timing.py [--finds N] [--oracle-poses P] [--cases m1,m2,m3,m4] [--foreground] [--seed-stride S]
                                           [--scene-seeds 101,102] [--refinement] [--sigma-angle DEG] [--sigma-translation M]
                                           [--rounds R]
+--objects m1,m2,m3 times the SCENE finder (rbs_find_scene_*) instead: one scene of those meshes placed apart at 640x480 per
+scene seed (tests/scene_find_scenes.py), the same switches for every body's find, --explain-radius / --polish-sweeps for the
+scene finder's own parameters.  Its cases: {"case", "size", "ms_per_scene_find", "stage_ms": {"per_body", "render",
+"residual", "polish", "whole"}, "order", "found", "bodies": [{"dt_mm", "iou", "score"}], "joint_score", "truth_joint_score",
+"meets_bar", ...}.
 """
 import os
 
@@ -158,6 +163,62 @@ def run_case(name, finds, oracle_poses, seed=101, foreground=False, seed_stride=
             "meets_bar": meets}
 
 
+def run_scene(names, finds, seed=101, foreground=False, seed_stride=None, refinement=False, sigma_angle=None, sigma_translation=None,
+              rounds=None, explain_radius=None, polish_sweeps=None):
+    import scene_find_scenes as ss
+    from dbot_ros_amd.assess import PoseAssessor
+    from dbot_ros_amd.finder import SceneFinder
+    s = ss.Scene(names, 640, 480, seed)
+    p = ObjectFinder.Parameters()
+    if seed_stride:
+        p.seed_stride = seed_stride
+    if sigma_angle is not None:
+        p.sigma_angle = math.radians(sigma_angle)
+    if sigma_translation is not None:
+        p.sigma_translation = sigma_translation
+    if rounds is not None:
+        p.rounds = rounds
+    sp = SceneFinder.Parameters()
+    if explain_radius is not None:
+        sp.explain_radius = explain_radius
+    if polish_sweeps is not None:
+        sp.polish_sweeps = polish_sweeps
+    with RbSensor(s.om, s.cam, s.P, max_particles=1) as sensor:
+        with SceneFinder(sensor, s.om, p, sp, foreground=ObjectFinder.Foreground() if foreground else None,
+                         refinement=ObjectFinder.Refinement() if refinement else None) as fnd:
+            fnd.find(s.frame)                                     # warm-up
+            t0 = time.perf_counter()
+            for _ in range(finds):
+                r = fnd.find(s.frame)
+            ms = (time.perf_counter() - t0) / finds * 1e3
+            per_body, render, residual, polish, whole = fnd.stage_ms()
+            order, _ = fnd.order()
+        a = PoseAssessor(sensor)
+
+        def planes(poses):
+            a.assess(np.asarray(poses)[None])
+            return [np.isfinite(a.plane(0, b)) for b in range(s.B)]
+        posed = np.isfinite(r.poses).all()
+        got, want = planes(np.where(np.isfinite(r.poses), r.poses, s.truth)), planes(s.truth)
+    with RbSensor(s.om, s.cam, s.P, max_particles=1024) as ref:
+        ref.reset()
+        ref.set_observation(s.frame)
+        truth_score = float(ref.loglikes_poses(np.repeat(s.truth[None], 1024, 0), np.zeros(1024, dtype=np.int32))[0])
+    bodies = [{"dt_mm": round(float(np.linalg.norm(r.poses[b, 9:] - s.truth[b, 9:])) * 1e3, 2),
+               "iou": round(float((got[b] & want[b]).sum() / max((got[b] | want[b]).sum(), 1)), 3),
+               "score": round(float(r.scores[b]), 1)} for b in range(s.B)]
+    meets = bool(posed and all(b["dt_mm"] < 10.0 and b["iou"] >= 0.85 for b in bodies) and
+                 r.joint_score >= truth_score - 0.02 * abs(truth_score))
+    return {"case": "+".join(names), "size": [640, 480], "ms_per_scene_find": round(ms, 2),
+            "stage_ms": {"per_body": [round(x, 3) for x in per_body], "render": round(render, 4), "residual": round(residual, 4),
+                         "polish": round(polish, 3), "whole": round(whole, 3)},
+            "order": order, "found": [bool(x) for x in r.found], "bodies": bodies,
+            "joint_score": round(float(r.joint_score), 1), "truth_joint_score": round(truth_score, 1), "meets_bar": meets,
+            "scene_seed": seed, "seed_stride": p.seed_stride, "foreground": bool(foreground), "refinement": bool(refinement),
+            "rounds": p.rounds, "sigma_angle_deg": round(math.degrees(p.sigma_angle), 3), "sigma_translation": p.sigma_translation,
+            "explain_radius": sp.explain_radius, "polish_sweeps": sp.polish_sweeps}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--finds", type=int, default=5)
@@ -170,7 +231,15 @@ def main():
     ap.add_argument("--sigma-angle", type=float, default=None, help="degrees")
     ap.add_argument("--sigma-translation", type=float, default=None, help="metres")
     ap.add_argument("--rounds", type=int, default=None)
+    ap.add_argument("--objects", default="", help="meshes of one scene, e.g. m1,m2,m3: time the scene finder")
+    ap.add_argument("--explain-radius", type=int, default=None)
+    ap.add_argument("--polish-sweeps", type=int, default=None)
     a = ap.parse_args()
+    if a.objects:
+        cases = [run_scene(tuple(a.objects.split(",")), a.finds, int(s), a.foreground, a.seed_stride, a.refinement, a.sigma_angle,
+                           a.sigma_translation, a.rounds, a.explain_radius, a.polish_sweeps) for s in a.scene_seeds.split(",")]
+        print(json.dumps({"tool": "find_object_timing", "cases": cases}))
+        return
     cases = [run_case(c, a.finds, a.oracle_poses, int(s), a.foreground, a.seed_stride, a.refinement, a.sigma_angle, a.sigma_translation,
                       a.rounds) for c in a.cases.split(",")
              for s in a.scene_seeds.split(",")]
