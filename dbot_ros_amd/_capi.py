@@ -51,6 +51,7 @@ EXPORTS = (
     "rbs_find_stage_ms", "rbs_find_last_error",
     "rbs_find_default_foreground", "rbs_find_set_foreground", "rbs_find_get_plane", "rbs_find_get_seed_frame",
     "rbs_find_default_refinement", "rbs_find_set_refinement", "rbs_find_get_covariance", "rbs_find_get_perturbations",
+    "rbs_find_default_gate", "rbs_find_set_gate", "rbs_find_get_evidence", "rbs_find_gate_ms", "rbs_find_scene_set_gate",
     "rbs_find_scene_default_params", "rbs_find_scene_create", "rbs_find_scene_destroy", "rbs_find_scene_set_foreground",
     "rbs_find_scene_set_refinement", "rbs_find_scene_run", "rbs_find_scene_get_order", "rbs_find_scene_get_residual",
     "rbs_find_scene_body_finder", "rbs_find_scene_get_polish", "rbs_find_scene_stage_ms", "rbs_find_scene_last_error",
@@ -128,6 +129,22 @@ class RbsFindRefinement(C.Structure):
         ("mix", C.c_double),
         ("shrink", C.c_double),
         ("jitter", C.c_double),
+    ]
+
+
+class RbsFindGate(C.Structure):
+    _fields_ = [
+        ("enabled", C.c_int32),
+        ("require_confirmed", C.c_int32),
+        ("radius", C.c_int32),
+        ("min_rim_pixels", C.c_int32),
+        ("min_pixels", C.c_int32),
+        ("sigmas", C.c_double),
+        ("min_support_fraction", C.c_double),
+        ("min_visible_fraction", C.c_double),
+        ("min_valid_fraction", C.c_double),
+        ("min_contour_fraction", C.c_double),
+        ("min_flush_fraction", C.c_double),
     ]
 
 
@@ -410,6 +427,14 @@ def load():
     lib.rbs_find_get_covariance.argtypes = [H, C.c_int32, dp, lp]
     lib.rbs_find_get_perturbations.restype = C.c_int32
     lib.rbs_find_get_perturbations.argtypes = [H, C.c_int32, dp, lp]
+    lib.rbs_find_default_gate.restype = None
+    lib.rbs_find_default_gate.argtypes = [C.POINTER(RbsFindGate)]
+    lib.rbs_find_set_gate.restype = C.c_int32
+    lib.rbs_find_set_gate.argtypes = [H, C.POINTER(RbsFindGate)]
+    lib.rbs_find_get_evidence.restype = C.c_int32
+    lib.rbs_find_get_evidence.argtypes = [H, C.c_int32, ip, ip, lp]
+    lib.rbs_find_gate_ms.restype = C.c_int32
+    lib.rbs_find_gate_ms.argtypes = [H, fp]
     lib.rbs_find_last_error.restype = C.c_char_p
     lib.rbs_find_last_error.argtypes = [H]
     up = C.POINTER(C.c_uint32)
@@ -423,6 +448,8 @@ def load():
     lib.rbs_find_scene_set_foreground.argtypes = [H, C.POINTER(RbsFindForeground)]
     lib.rbs_find_scene_set_refinement.restype = C.c_int32
     lib.rbs_find_scene_set_refinement.argtypes = [H, C.POINTER(RbsFindRefinement)]
+    lib.rbs_find_scene_set_gate.restype = C.c_int32
+    lib.rbs_find_scene_set_gate.argtypes = [H, C.POINTER(RbsFindGate)]
     lib.rbs_find_scene_run.restype = C.c_int32
     lib.rbs_find_scene_run.argtypes = [H, fp, C.c_uint32, dp, dp, dp, up, dp]
     lib.rbs_find_scene_get_order.restype = C.c_int32

@@ -17,6 +17,8 @@
 //   (rbs_findr_*_kernel)        opt-in step 6b (rbs_find_set_refinement) in place of step 6's fixed schedule: every survivor
 //                               carries a 6 x 6 search covariance; its children are drawn through the covariance's factor and
 //                               the covariance is re-estimated from the round's best children, all on the device
+//   (rbs_findc_*_kernel)        opt-in gate (rbs_find_set_gate; rbsensor_find_gate.hip): every hypothesis' assess and contour
+//                               evidence behind its coarse score (step 4b), the confirmed ones first in steps 5 and 7
 // Every order is fixed: the same frame gives the same bits, whatever `batch`.
 #include <climits>
 
@@ -788,6 +790,8 @@ inline void launch_refine_update(hipStream_t st, const double* child_score, cons
 
 }  // namespace rbf
 
+struct rbs_find_gate_state;          // rbsensor_find_gate.hip
+
 struct rbs_find {
     rbs_handle* s = nullptr;          // the sensor (borrowed)
     int part = -1;                    // >= 0: the finder of that part of a sensor of several (rbsensor_find_scene.hip); -1: the sensor's one object
@@ -817,6 +821,9 @@ struct rbs_find {
     double* d_cov = nullptr;          // [rounds + 1][S][36] the covariances entering each round, then the final ones
     double* d_fac = nullptr;          // [S][36] the current factors
     double* d_dd = nullptr;           // [rounds][S*children][6] the children's perturbations
+    // the gate (rbs_find_set_gate): allocated when first switched on
+    rbs_find_gate gt{};               // the setting of the next find
+    rbs_find_gate_state* gs = nullptr;
     double* d_hyp = nullptr;          // [batch][12]
     int* d_zero = nullptr;            // [max(batch, S*children)] parent indices: all 0
     double* d_score = nullptr;        // [max_seeds * n_rotations] coarse scores
@@ -842,6 +849,8 @@ struct rbs_find {
     bool have = false;
     bool fg_ran = false;              // with step 1b
     bool rf_ran = false;              // with step 6b
+    bool gt_ran = false;              // with the gate
+    float gms[2] = {};                // the evidence kernel's ms: step 4b, step 7
     double plane[rbf::kFgRecord] = {};
     int n_seeds = 0, n_valid = 0, n_cand = 0, n_surv = 0;
     long n_hyp = 0;
@@ -999,6 +1008,13 @@ double mean_vertex_distance(const double* V, size_t nv)
 
 int32_t find_create_part(rbs_handle* sensor, const rbs_find_params* p, int part, rbs_find** out);
 int32_t find_run(rbs_find* f, const float* frame, const float* d_frame, int32_t k, double* poses, double* scores, int32_t* n_out, int32_t* found);
+// rbsensor_find_gate.hip: the gate's part of a find, and its release
+int32_t gate_coarse(rbs_find* f, long h0, int nb, int batch_no);
+int32_t gate_select(rbs_find* f, int nc);
+int32_t gate_result(rbs_find* f, int S, int batches);
+void gate_times(rbs_find* f, int batches, bool with_result);
+int32_t gate_first_class(rbs_find* f, int* c0);
+void gate_release(rbs_find* f);
 
 }  // namespace
 
@@ -1042,6 +1058,7 @@ void rbs_find_destroy(rbs_find* f)
                     (void*)f->d_child, (void*)f->d_child_score, (void*)f->d_final, (void*)f->d_final_score, (void*)f->d_final_idx,
                     (void*)f->d_seedframe, (void*)f->d_planes, (void*)f->d_counts, (void*)f->d_cov, (void*)f->d_fac, (void*)f->d_dd})
         if (q) (void)hipFree(q);
+    gate_release(f);
     if (f->h_frame) (void)hipHostFree(f->h_frame);
     if (f->h_info) (void)hipHostFree(f->h_info);
     for (hipEvent_t& e : f->ev)
@@ -1194,6 +1211,9 @@ int32_t find_run(rbs_find* f, const float* frame, const float* d_frame, int32_t 
     f->n_valid = f->h_info[1];
     f->fg_ran = fg;
     f->rf_ran = false;
+    const bool gate = f->gt.enabled != 0;
+    f->gt_ran = gate;
+    f->gms[0] = f->gms[1] = 0.f;
     for (double& v : f->plane) v = 0.0;
     if (fg) {
         std::memcpy(f->plane, f->h_info + 4, sizeof(f->plane));
@@ -1210,20 +1230,27 @@ int32_t find_run(rbs_find* f, const float* frame, const float* d_frame, int32_t 
     }
     // coarse scores, `batch` hypotheses per launch
     const rbf::HypParams HP = hyp_params(f);
-    for (long h0 = 0; h0 < f->n_hyp; h0 += p.batch) {
+    int batches = 0;
+    for (long h0 = 0; h0 < f->n_hyp; h0 += p.batch, ++batches) {
         const int nb = (int)std::min<long>(p.batch, f->n_hyp - h0);
         rbf::launch_hyp(st, HP, h0, nb, f->d_hyp);
         RBF_HIP(f, hipGetLastError());
         RBF_RC(f, f->coarse, rbs_loglikes_device(f->coarse, f->d_hyp, f->d_zero, nb, 0, f->d_score + h0, st));
+        if (gate)   // step 4b: the same poses' evidence
+            if (int32_t rc = gate_coarse(f, h0, nb, batches)) return rc;
     }
     RBF_HIP(f, hipEventRecord(f->ev[2], st));
     // selection: top n_candidates, then the suppression
     const int nc = (int)std::min<long>(p.n_candidates, f->n_hyp);
     const double* ts;
     const long long* ti;
-    if (int32_t rc = find_topk(f, f->d_score, nullptr, f->n_hyp, nc, &ts, &ti)) return rc;
-    RBF_HIP(f, hipMemcpyAsync(f->d_cand_score, ts, sizeof(double) * nc, hipMemcpyDeviceToDevice, st));
-    RBF_HIP(f, hipMemcpyAsync(f->d_cand_idx, ti, sizeof(long long) * nc, hipMemcpyDeviceToDevice, st));
+    if (gate) {   // the confirmed hypotheses first
+        if (int32_t rc = gate_select(f, nc)) return rc;
+    } else {
+        if (int32_t rc = find_topk(f, f->d_score, nullptr, f->n_hyp, nc, &ts, &ti)) return rc;
+        RBF_HIP(f, hipMemcpyAsync(f->d_cand_score, ts, sizeof(double) * nc, hipMemcpyDeviceToDevice, st));
+        RBF_HIP(f, hipMemcpyAsync(f->d_cand_idx, ti, sizeof(long long) * nc, hipMemcpyDeviceToDevice, st));
+    }
     rbf::launch_gather(st, HP, f->d_cand_idx, nc, f->d_cand_pose);
     rbf::launch_nms_keep(st, f->d_cand_pose, f->d_cand_score, f->d_cand_idx, nc, f->t2, f->trace_min, p.n_survivors, f->d_kept,
                          f->d_info + 2, f->d_surv0, f->d_surv0_score, f->d_surv0_idx);
@@ -1269,10 +1296,14 @@ int32_t find_run(rbs_find* f, const float* frame, const float* d_frame, int32_t 
         if (p.rounds == 0) {   // no refinement: the survivors are scored once at the sensor's resolution
             RBF_RC(f, f->full, rbs_loglikes_device(f->full, f->d_surv, f->d_zero, S, 0, f->d_surv_score, st));
         }
-        const double* fs;
-        const long long* fi;
-        if (int32_t rc = find_topk(f, f->d_surv_score, nullptr, S, S, &fs, &fi)) return rc;
-        RBF_HIP(f, hipMemcpyAsync(f->d_final_idx, fi, sizeof(long long) * S, hipMemcpyDeviceToDevice, st));
+        if (gate) {   // step 7's evidence, and the confirmed survivors first
+            if (int32_t rc = gate_result(f, S, batches)) return rc;
+        } else {
+            const double* fs;
+            const long long* fi;
+            if (int32_t rc = find_topk(f, f->d_surv_score, nullptr, S, S, &fs, &fi)) return rc;
+            RBF_HIP(f, hipMemcpyAsync(f->d_final_idx, fi, sizeof(long long) * S, hipMemcpyDeviceToDevice, st));
+        }
         rbf::launch_order(st, f->d_surv, f->d_surv_score, f->d_final_idx, S, f->d_final, f->d_final_score);
         RBF_HIP(f, hipGetLastError());
     }
@@ -1284,12 +1315,18 @@ int32_t find_run(rbs_find* f, const float* frame, const float* d_frame, int32_t 
     (void)hipEventElapsedTime(&f->ms[2], f->ev[2], f->ev[3]);
     (void)hipEventElapsedTime(&f->ms[3], f->ev[3], f->ev[4]);
     (void)hipEventElapsedTime(&f->ms[4], f->ev[0], f->ev[4]);
+    if (gate) gate_times(f, batches, S > 0);
     f->have = true;
     const int K = std::min(k, S);
     if (S > 0) {
         double best = 0.0;
         RBF_HIP(f, hipMemcpy(&best, f->d_final_score, sizeof(double), hipMemcpyDeviceToHost));
         *found = best >= p.min_score ? 1 : 0;
+        if (gate && f->gt.require_confirmed) {   // pose 0 must be confirmed too
+            int c0 = 1;
+            if (int32_t rc = gate_first_class(f, &c0)) return rc;
+            if (c0 != 0) *found = 0;
+        }
     }
     if (K > 0 && poses) RBF_HIP(f, hipMemcpy(poses, f->d_final, sizeof(double) * 12 * K, hipMemcpyDeviceToHost));
     if (K > 0 && scores) RBF_HIP(f, hipMemcpy(scores, f->d_final_score, sizeof(double) * K, hipMemcpyDeviceToHost));
@@ -1513,6 +1550,9 @@ int32_t rbs_find_stage_ms(rbs_find* f, float* out5)
 }
 
 }  // extern "C"
+
+// The gate (rbs_find_set_gate, rbs_find_get_evidence): the rbs_findc_* kernels and what find_run calls of them.
+#include "rbsensor_find_gate.hip"
 
 // The scene finder (rbs_find_scene_*): the bodies of a model of several, over per-part finders of the above.
 #include "rbsensor_find_scene.hip"

@@ -371,6 +371,16 @@ int32_t rbs_find_scene_set_refinement(rbs_find_scene* f, const rbs_find_refineme
     return RBS_OK;
 }
 
+int32_t rbs_find_scene_set_gate(rbs_find_scene* f, const rbs_find_gate* g)
+{
+    if (!f) return RBS_ERR_INVALID_ARGUMENT;
+    if (g && g->enabled != 0)
+        if (const char* bad = gate_check(g)) return sfail(f, RBS_ERR_INVALID_ARGUMENT, std::string("find gate: ") + bad);
+    for (int b = 0; b < f->B; ++b)
+        if (int32_t rc = rbs_find_set_gate(f->body[b], g)) return sfail(f, rc, f->body[b]->err);
+    return RBS_OK;
+}
+
 int32_t rbs_find_scene_run(rbs_find_scene* f, const float* frame, uint32_t search_mask, const double* given_poses, double* out_poses,
                            double* out_scores, uint32_t* found_mask, double* joint_score)
 {

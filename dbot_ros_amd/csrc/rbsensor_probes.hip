@@ -18,6 +18,7 @@
 // the device before the launch and back after it, so what the kernel left alone -- the tail included -- is seen.
 // rbs_test_findfg_* are the same for step 1b's four launch helpers: tests/test_gpu_find_foreground_kernels.py.
 // rbs_test_findr_* are the same for step 6b's launch helpers: tests/test_gpu_find_refinement_kernels.py.
+// rbs_test_findc_evidence is the gate's evidence kernel alone, over a sensor's geometry: tests/test_gpu_find_gate_kernels.py.
 //
 // rbs_test_prep does the same for the rectangles kernel (rbsensor_kernels.hip prep_particles): it builds a DevParams from host
 // arrays -- no sensor handle, no mesh: the rectangle reads the vertices only -- and launches rbs_prep_kernel,
@@ -756,6 +757,30 @@ int32_t rbs_test_findr_update(const double* child_score, const double* dd, int32
     if (B.err == hipSuccess) { rbf::launch_refine_update(nullptr, dscore, ddd, S, children, U, dcov, dcov, dfac); B.ran(); }
     B.fetch(cov, dcov, 36 * K);
     B.fetch(fac, dfac, 36 * K);
+    return B.status();
+}
+
+// ---- the gate (rbs_findc_evidence_kernel): tests/test_gpu_find_gate_kernels.py
+// The evidence of poses [n][12] against frame [rows * cols] through the one-body sensor h's geometry, alone on the null stream:
+// rec [n + tail][10] and cls [n + tail] IN and OUT.  g: the rule (checked as rbs_find_set_gate checks it).
+int32_t rbs_test_findc_evidence(rbs_handle* h, const rbs_find_gate* g, const float* frame, const double* poses, int32_t n, int32_t* rec,
+                                int32_t* cls, int64_t tail)
+{
+    namespace pr = rbs::probe;
+    if (!h || !g || !frame || !poses || !rec || !cls || n < 0 || tail < 0 || pr::probe_refused(n) || pr::probe_refused(tail) ||
+        h->n_bodies != 1 || !h->shards.empty() || h->group || h->peer_world > 1 || gate_check(g))
+        return RBS_ERR_INVALID_ARGUMENT;
+    if (n == 0) return RBS_OK;
+    if (hipSetDevice(h->device) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) return RBS_ERR_HIP;
+    const size_t K = (size_t)n + (size_t)tail;
+    pr::Buffers B;
+    const float* dframe = B.make<float>((size_t)h->npx, frame);
+    const double* dposes = B.make<double>(12 * (size_t)n, poses);
+    int* drec = B.make<int>(rbf::kEvFields * K, rec);
+    int* dcls = B.make<int>(K, cls);
+    if (B.err == hipSuccess) { rbf::launch_evidence(nullptr, h, *g, dframe, dposes, n, drec, dcls); B.ran(); }
+    B.fetch(rec, drec, rbf::kEvFields * K);
+    B.fetch(cls, dcls, K);
     return B.status();
 }
 

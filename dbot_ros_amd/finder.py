@@ -27,6 +27,7 @@ class FindResult:
     scores: np.ndarray    # [K] log-likelihoods at the sensor's resolution
     assessment: Optional[object] = None   # find(assess=PoseAssessor): the assess.Assessment of the K poses against the frame
     confirmed: Optional[int] = None       # ... and the first pose whose verdict is SUPPORTED (-1: none)
+    classes: Optional[np.ndarray] = None  # the gate on: [K] int32, 0 = the pose is confirmed (SUPPORTED and PRESENT); None: the stage off
 
 
 # the dominant plane of the last find (step 1b): 1 / z = a u + b v + c over the coarse pixels (u, v)
@@ -34,7 +35,7 @@ Plane = namedtuple("Plane", "accepted a b c count n_valid trial masked")
 
 
 class ObjectFinder:
-    """ObjectFinder(sensor, object_model, params, foreground=None, refinement=None).find(frame=None) -> FindResult."""
+    """ObjectFinder(sensor, object_model, params, foreground=None, refinement=None, gate=None).find(frame=None) -> FindResult."""
 
     @dataclass
     class Foreground:
@@ -89,6 +90,40 @@ class ObjectFinder:
             return g
 
     @dataclass
+    class Gate:
+        """The silhouette gate (rbs_find_gate; steps 4b, 5 and 7): every hypothesis' assess and contour evidence, the
+        confirmed ones first.  The fields besides the two switches are rbs_assess_params' and rbs_contour_params'."""
+        enabled: bool = True
+        require_confirmed: bool = False
+        radius: int = 2
+        min_rim_pixels: int = 16
+        min_pixels: int = 16
+        sigmas: float = 3.0
+        min_support_fraction: float = 0.5
+        min_visible_fraction: float = 0.25
+        min_valid_fraction: float = 0.5
+        min_contour_fraction: float = 0.3
+        min_flush_fraction: float = 0.5
+
+        @classmethod
+        def from_mapping(cls, m):
+            g = cls()
+            names = [f.name for f in fields(cls)]
+            for k, v in dict(m or {}).items():
+                if k not in names:
+                    raise ValueError(f"object_finder/gate/{k}: unknown key (one of {sorted(names)})")
+                cur = getattr(g, k)
+                setattr(g, k, bool(v) if isinstance(cur, bool) else int(v) if isinstance(cur, int) else float(v))
+            return g
+
+        def c_params(self):
+            g = _capi.RbsFindGate()
+            whole = ("enabled", "require_confirmed", "radius", "min_rim_pixels", "min_pixels")
+            for f in fields(self):
+                setattr(g, f.name, int(getattr(self, f.name)) if f.name in whole else getattr(self, f.name))
+            return g
+
+    @dataclass
     class Parameters:
         coarse_downsampling: int = 0          # 0: the largest of {1, 2, 4} leaving >= 160 columns
         seed_stride: int = 4
@@ -113,20 +148,24 @@ class ObjectFinder:
         # step 6b, an ObjectFinder.Refinement; None: off (step 6's fixed schedule).  A plain attribute, not a dataclass field:
         # the fields besides `foreground` are rbs_find_params' own, one to one.
         refinement = None
+        # the gate, an ObjectFinder.Gate; None: off.  A plain attribute as well
+        gate = None
         # the optional `scene:` mapping, a SceneFinder.Parameters (several objects: node.build_scene_finder); None: its defaults
         scene = None
 
         @classmethod
         def from_rosparam(cls, tree):
             """From the optional `object_finder:` mapping of the merged rosparam tree; every key is
-            optional (angles in degrees: nms_angle_deg, sigma_angle_deg; foreground / refinement: mappings of Foreground's /
-            Refinement's fields; scene: a mapping of SceneFinder.Parameters' fields)."""
+            optional (angles in degrees: nms_angle_deg, sigma_angle_deg; foreground / refinement / gate: mappings of
+            Foreground's / Refinement's / Gate's fields; scene: a mapping of SceneFinder.Parameters' fields)."""
             m = dict((tree or {}).get("object_finder") or {})
             p = cls()
             if "foreground" in m:
                 p.foreground = ObjectFinder.Foreground.from_mapping(m.pop("foreground"))
             if "refinement" in m:
                 p.refinement = ObjectFinder.Refinement.from_mapping(m.pop("refinement"))
+            if "gate" in m:
+                p.gate = ObjectFinder.Gate.from_mapping(m.pop("gate"))
             if "scene" in m:
                 p.scene = SceneFinder.Parameters.from_mapping(m.pop("scene"))
             for k in ("nms_angle", "sigma_angle"):
@@ -146,7 +185,7 @@ class ObjectFinder:
                     setattr(p, f.name, getattr(self, f.name))
             return p
 
-    def __init__(self, sensor, object_model, params=None, foreground=None, refinement=None):
+    def __init__(self, sensor, object_model, params=None, foreground=None, refinement=None, gate=None):
         self._lib = _capi.load()
         self.sensor = sensor
         self.params = params or ObjectFinder.Parameters()
@@ -162,11 +201,15 @@ class ObjectFinder:
         foreground = self.params.foreground if foreground is None else foreground
         self.refinement = None
         refinement = self.params.refinement if refinement is None else refinement
+        self.gate = None
+        gate = self.params.gate if gate is None else gate
         try:
             if foreground is not None:
                 self.set_foreground(foreground)
             if refinement is not None:
                 self.set_refinement(refinement)
+            if gate is not None:
+                self.set_gate(gate)
         except Exception:
             self.close()
             raise
@@ -219,6 +262,8 @@ class ObjectFinder:
             states[i, 0:3] = poses[i, 9:12] - R @ c
             states[i, 3:6] = matrix_to_rotvec(R)
         res = FindResult(bool(found.value), states, poses, scores)
+        if self.gate is not None:
+            res.classes = self.evidence(_capi.RBS_FIND_RESULT)[1][:K]
         if assess is not None:
             from .assess import SUPPORTED
             res.confirmed = -1
@@ -268,6 +313,37 @@ class ObjectFinder:
         g = refinement.c_params()
         self._check(self._lib.rbs_find_set_refinement(self._f, C.byref(g)))
         self.refinement = refinement
+
+    def set_gate(self, gate=None):
+        """The gate for the finds from the next one on; None (or enabled = False): off.  Bad values raise, and the previous
+        setting stays."""
+        if gate is None or not gate.enabled:
+            self._check(self._lib.rbs_find_set_gate(self._f, None))
+            self.gate = None
+            return
+        g = gate.c_params()
+        self._check(self._lib.rbs_find_set_gate(self._f, C.byref(g)))
+        self.gate = gate
+
+    def evidence(self, stage):
+        """The last find's evidence of `stage` ("coarse", "candidates", "survivors" or "result"), in that stage's order:
+        (records [n, 10] int32 = rendered, valid, support, in_front, behind, rim, valid, flush, in_front, beyond;
+        classes [n] int32).  The gate only."""
+        if isinstance(stage, str):
+            stage = {"coarse": 1, "candidates": 2, "survivors": 3, "result": 5}[stage]
+        n = C.c_int64()
+        ip = C.POINTER(C.c_int32)
+        self._check(self._lib.rbs_find_get_evidence(self._f, stage, None, None, C.byref(n)))
+        rec = np.zeros((int(n.value), 10), dtype=np.int32)
+        cls = np.zeros(int(n.value), dtype=np.int32)
+        self._check(self._lib.rbs_find_get_evidence(self._f, stage, rec.ctypes.data_as(ip), cls.ctypes.data_as(ip), C.byref(n)))
+        return rec, cls
+
+    def gate_ms(self):
+        """Device ms of the last find's evidence kernel: step 4b, step 7."""
+        out = (C.c_float * 2)()
+        self._check(self._lib.rbs_find_gate_ms(self._f, out))
+        return list(out)
 
     def covariance(self, round):
         """The last find's covariances entering `round` [survivors, 6, 6] (round = rounds: the final ones); step 6b only."""
@@ -326,7 +402,7 @@ class SceneFindResult:
 
 class _BodyFinder(ObjectFinder):
     """A scene finder's finder of one body (rbs_find_scene_body_finder), borrowed: the inspection methods of
-    ObjectFinder (stage, plane, seed_frame, covariance, perturbations, stage_ms) read that body's last find."""
+    ObjectFinder (stage, plane, seed_frame, covariance, perturbations, evidence, stage_ms, gate_ms) read that body's last find."""
 
     def __init__(self, scene, body):
         self._lib = scene._lib
@@ -337,7 +413,7 @@ class _BodyFinder(ObjectFinder):
         self._f = C.c_void_p(self._lib.rbs_find_scene_body_finder(scene._f, body))
         if not self._f.value:
             raise ValueError(f"body {body} outside 0..{scene.parts - 1}")
-        self.foreground, self.refinement = scene.foreground, scene.refinement
+        self.foreground, self.refinement, self.gate = scene.foreground, scene.refinement, scene.gate
 
     def close(self):
         self._f = C.c_void_p()
@@ -345,11 +421,11 @@ class _BodyFinder(ObjectFinder):
     def find(self, *a, **k):
         raise TypeError("a scene finder's body finder is borrowed: run SceneFinder.find")
 
-    set_foreground = set_refinement = find
+    set_foreground = set_refinement = set_gate = find
 
 
 class SceneFinder:
-    """SceneFinder(sensor, object_model, params=None, scene=None, foreground=None, refinement=None).find(frame, search, given)
+    """SceneFinder(sensor, object_model, params=None, scene=None, foreground=None, refinement=None, gate=None).find(frame, search, given)
     -> SceneFindResult: every body of a model of several from one depth frame (rbs_find_scene_*; the rule:
     include/rbsensor_mi355x.h and DESIGN.md Appendix K).  params: ObjectFinder.Parameters, every body's find."""
 
@@ -385,7 +461,7 @@ class SceneFinder:
             p.reserved = 0
             return p
 
-    def __init__(self, sensor, object_model, params=None, scene=None, foreground=None, refinement=None):
+    def __init__(self, sensor, object_model, params=None, scene=None, foreground=None, refinement=None, gate=None):
         self._lib = _capi.load()
         self.sensor = sensor
         self.params = params or ObjectFinder.Parameters()
@@ -399,14 +475,17 @@ class SceneFinder:
             self._f = C.c_void_p()
             sensor._check(rc)
         sensor._register_dependent(self)   # the scene finder borrows the sensor handle
-        self.foreground = self.refinement = None
+        self.foreground = self.refinement = self.gate = None
         foreground = self.params.foreground if foreground is None else foreground
         refinement = self.params.refinement if refinement is None else refinement
+        gate = self.params.gate if gate is None else gate
         try:
             if foreground is not None:
                 self.set_foreground(foreground)
             if refinement is not None:
                 self.set_refinement(refinement)
+            if gate is not None:
+                self.set_gate(gate)
         except Exception:
             self.close()
             raise
@@ -445,6 +524,14 @@ class SceneFinder:
         g = refinement.c_params() if on else None
         self._check(self._lib.rbs_find_scene_set_refinement(self._f, C.byref(g) if on else None))
         self.refinement = refinement if on else None
+
+    def set_gate(self, gate=None):
+        """The gate of every body's find, as ObjectFinder.set_gate.  With require_confirmed a body without a confirmed
+        pose is not placed: `found` is False for it."""
+        on = gate is not None and gate.enabled
+        g = gate.c_params() if on else None
+        self._check(self._lib.rbs_find_scene_set_gate(self._f, C.byref(g) if on else None))
+        self.gate = gate if on else None
 
     def mask_of(self, search):
         """None: every body; an int: the mask itself; else the bodies' indices."""

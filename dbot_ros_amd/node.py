@@ -84,7 +84,7 @@ def build_gaussian_tracker(params, native_camera_matrix, mesh_package_path, devi
 def build_object_finder(params, native_camera_matrix, mesh_package_path, device_id=0, sensor=None):
     """The object finder that stands in for the controller's FindObject service
     (R:source/dbot_ros/tracker/object_tracker_controller_service_node.cpp:143-167): the object model and camera data
-    assembled as build_particle_tracker does, its parameters from the optional `object_finder:` mapping (its `foreground:` sub-mapping switches step 1b on, its `refinement:` sub-mapping step 6b).  sensor: a
+    assembled as build_particle_tracker does, its parameters from the optional `object_finder:` mapping (its `foreground:` sub-mapping switches step 1b on, its `refinement:` sub-mapping step 6b, its `gate:` sub-mapping the silhouette gate).  sensor: a
     sensor to search with (a tracker's own); None builds one from the tree.  Returns (finder, object_model,
     camera_data); close the finder, then a sensor built here (finder.sensor)."""
     from .finder import ObjectFinder
@@ -100,13 +100,14 @@ def build_object_finder(params, native_camera_matrix, mesh_package_path, device_
         params_obsrv.sample_count = 1
         sensor = RbSensorBuilder(object_model, camera_data, params_obsrv, device_id=device_id).build()
     finder_params = ObjectFinder.Parameters.from_rosparam(params)   # object_finder/foreground, /refinement: steps 1b and 6b, passed through
-    return (ObjectFinder(sensor, object_model, finder_params, foreground=finder_params.foreground, refinement=finder_params.refinement),
+    return (ObjectFinder(sensor, object_model, finder_params, foreground=finder_params.foreground, refinement=finder_params.refinement,
+                         gate=finder_params.gate),
             object_model, camera_data)
 
 
 def build_scene_finder(params, native_camera_matrix, mesh_package_path, device_id=0, sensor=None):
     """build_object_finder for a tree of several objects: a SceneFinder (dbot_ros_amd/finder.py) over every mesh of
-    object/meshes.  Its per-body search is the `object_finder:` mapping's (foreground: and refinement: included), its own
+    object/meshes.  Its per-body search is the `object_finder:` mapping's (foreground:, refinement: and gate: included), its own
     parameters the optional `object_finder/scene:` sub-mapping (SceneFinder.Parameters' fields; unknown keys: ValueError).
     Returns (scene finder, object_model, camera_data); close the finder, then a sensor built here (finder.sensor)."""
     from .finder import ObjectFinder, SceneFinder
@@ -123,7 +124,7 @@ def build_scene_finder(params, native_camera_matrix, mesh_package_path, device_i
         params_obsrv.sample_count = 1
         sensor = RbSensorBuilder(object_model, camera_data, params_obsrv, device_id=device_id).build()
     return (SceneFinder(sensor, object_model, finder_params, finder_params.scene, foreground=finder_params.foreground,
-                        refinement=finder_params.refinement), object_model, camera_data)
+                        refinement=finder_params.refinement, gate=finder_params.gate), object_model, camera_data)
 
 
 def to_eigen_vector(native_image, downsampling_factor):

@@ -44,6 +44,16 @@ public:
         Refinement() { rbs_find_default_refinement(this); }
     };
 
+    /// rbs_find_gate with the two rules' defaults, enabled (steps 4b, 5 and 7: the confirmed poses first).
+    struct Gate : rbs_find_gate {
+        Gate() { rbs_find_default_gate(this); }
+    };
+
+    /// The last find's evidence of one stage (rbs_find_get_evidence): records [n][10], classes [n] (0: confirmed).
+    struct Evidence {
+        std::vector<int32_t> records, classes;
+    };
+
     /// The last find's dominant plane, 1 / z = a u + b v + c over the coarse pixels (rbs_find_get_plane).
     struct Plane {
         bool accepted = false;
@@ -104,6 +114,27 @@ public:
     {
         if (rbs_find_set_refinement(f_, g) != RBS_OK)
             throw std::runtime_error(std::string("ObjectFinder::set_refinement: ") + rbs_find_last_error(f_));
+    }
+
+    /// The gate for the finds from the next one on; nullptr (or enabled == 0): off.  Bad values throw, the previous setting stays.
+    void set_gate(const rbs_find_gate* g)
+    {
+        if (rbs_find_set_gate(f_, g) != RBS_OK)
+            throw std::runtime_error(std::string("ObjectFinder::set_gate: ") + rbs_find_last_error(f_));
+    }
+
+    /// The last find's evidence of RBS_FIND_COARSE, _CANDIDATES, _SURVIVORS or _RESULT, in that stage's order; the gate only.
+    Evidence evidence(int stage)
+    {
+        int64_t n = 0;
+        if (rbs_find_get_evidence(f_, stage, nullptr, nullptr, &n) != RBS_OK)
+            throw std::runtime_error(std::string("ObjectFinder::evidence: ") + rbs_find_last_error(f_));
+        Evidence e;
+        e.records.assign(10 * static_cast<size_t>(n), 0);
+        e.classes.assign(static_cast<size_t>(n), 0);
+        if (rbs_find_get_evidence(f_, stage, e.records.data(), e.classes.data(), &n) != RBS_OK)
+            throw std::runtime_error(std::string("ObjectFinder::evidence: ") + rbs_find_last_error(f_));
+        return e;
     }
 
     /// The last find's covariances entering `round` (round == rounds: the final ones), [survivors][36] row-major; step 6b only.
@@ -247,6 +278,12 @@ public:
     {
         if (rbs_find_scene_set_refinement(f_, g) != RBS_OK)
             throw std::runtime_error(std::string("SceneFinder::set_refinement: ") + rbs_find_scene_last_error(f_));
+    }
+    /// The gate of every body's find (ObjectFinder::Gate); with require_confirmed a body without a confirmed pose is not placed.
+    void set_gate(const rbs_find_gate* g)
+    {
+        if (rbs_find_scene_set_gate(f_, g) != RBS_OK)
+            throw std::runtime_error(std::string("SceneFinder::set_gate: ") + rbs_find_scene_last_error(f_));
     }
 
     /// The last scene find's S1: the searched bodies in the order they were taken.

@@ -676,6 +676,22 @@ int32_t rbs_gauss_result(rbs_gauss* g, double* out_state, double* out_cov);
  *                   b = 2 pi s / 1.533751168755204288118041, q = (x, y, z, w) = (r sin a, r cos a, R sin b,
  *                   R cos b).  Hypothesis h = seed * n_rotations + rotation, generated on the device in binary64.
  *   4 coarse scores every hypothesis at the coarse resolution, `batch` at a time.
+ *   4b evidence     opt-in (rbs_find_set_gate; off by default), the silhouette gate.  For every hypothesis h, against the
+ *                   coarse frame (the frame step 4 scores on, not the seeding frame): the assess record (rendered, valid,
+ *                   support, in_front, behind) and the contour record (rim, valid, flush, in_front, beyond) of its pose, by
+ *                   exactly the definitions of rbs_assess_poses / rbs_contour_poses for a one-body model: the render culls as
+ *                   rbs_render_depth's, tau = sigmas x (model_sigma + sigma_factor x (d x d)) in binary64, the anchor is the
+ *                   maximum over the Chebyshev window of `radius`.  The verdicts are taken on the device with the binary64
+ *                   comparisons of rbs_assess_verdict and rbs_contour_verdict, and the class c(h) is 0 when they are
+ *                   RBS_ASSESS_SUPPORTED and RBS_CONTOUR_PRESENT (the pose is CONFIRMED), else 1.  With the gate on:
+ *                   step 5's candidates are the n_candidates first hypotheses in the order (c ascending, score descending,
+ *                   h ascending), NaN never -- the chunked top-k run twice, over class 0 with every other score NaN and then
+ *                   over class 1 to fill up, which is exact -- and the suppression, unchanged, runs in that order.  In step 7
+ *                   the sorted survivors get the same evidence at the sensor's resolution against the frame the find was
+ *                   given (in a scene find: the residual frame), the output order is (c ascending, score descending, survivor
+ *                   index ascending) with the NaN scores last in survivor order as before, and with require_confirmed set
+ *                   found = 1 only when pose 0 has c = 0 and its score >= min_score; with it clear, found keeps its meaning
+ *                   and is applied to pose 0 of the new order.
  *   5 selection     the n_candidates best in the order (score descending, hypothesis ascending), NaN never;
  *                   then a greedy non-maximum suppression in that order: a candidate is dropped when a kept one
  *                   has |t - t'|^2 <= nms_translation^2 AND trace(R^T R') >= 1 + 2 cos(nms_angle); at most
@@ -811,6 +827,37 @@ int32_t rbs_find_get_covariance(rbs_find* f, int32_t round, double* cov, int64_t
 /* The perturbations d of round `round`'s children (0 .. rounds - 1), for the tests: *n := survivors * children,
  * d (may be NULL) [*n][6], in RBS_FIND_CHILDREN's order. */
 int32_t rbs_find_get_perturbations(rbs_find* f, int32_t round, double* d, int64_t* n);
+/* Step 4b, the silhouette gate, and what it changes in steps 5 and 7.  The fields are rbs_assess_params' and
+ * rbs_contour_params', with the same limits.  Memory, allocated when the stage is first switched on: 44 bytes per hypothesis
+ * (max_seeds x n_rotations of them: ten int32 counts and the class, written batch by batch and kept for
+ * rbs_find_get_evidence), 8 bytes per hypothesis for the gated order's masked scores, and 88 per survivor. */
+typedef struct rbs_find_gate {
+    int32_t enabled;               /* 0: the stage is off (a new finder)                                            */
+    int32_t require_confirmed;     /* 0; 1: found also needs pose 0 to be confirmed                                 */
+    int32_t radius;                /* 2 (1 .. 8): rbs_contour_params.radius                                         */
+    int32_t min_rim_pixels;        /* 16                                                                            */
+    int32_t min_pixels;            /* 16: rbs_assess_params.min_pixels                                              */
+    double sigmas;                 /* 3                                                                             */
+    double min_support_fraction;   /* 0.5                                                                           */
+    double min_visible_fraction;   /* 0.25                                                                          */
+    double min_valid_fraction;     /* 0.5                                                                           */
+    double min_contour_fraction;   /* 0.3                                                                           */
+    double min_flush_fraction;     /* 0.5 (not read by the class; checked as rbs_contour_params')                   */
+} rbs_find_gate;
+/* The two rules' defaults with enabled = 1 and require_confirmed = 0, stated once. */
+void rbs_find_default_gate(rbs_find_gate* g);
+/* The setting of the finds from the next rbs_find_run on.  NULL or enabled == 0: the stage is off, and a find is bit for
+ * bit that of a finder never configured, launch for launch.  Bad values: RBS_ERR_INVALID_ARGUMENT, and the previous setting
+ * stays. */
+int32_t rbs_find_set_gate(rbs_find* f, const rbs_find_gate* g);
+/* The last find's evidence, each in that stage's order: RBS_FIND_COARSE (every hypothesis), RBS_FIND_CANDIDATES and
+ * RBS_FIND_SURVIVORS (step 4b's records of those hypotheses) and RBS_FIND_RESULT (step 7's records).  *n := the stage's
+ * count; records (may be NULL) [*n][10] := rendered, valid, support, in_front, behind, rim, valid, flush, in_front, beyond;
+ * classes (may be NULL) [*n].  The last find ran without the gate, or another stage: RBS_ERR_INVALID_ARGUMENT. */
+int32_t rbs_find_get_evidence(rbs_find* f, int32_t stage, int32_t* records, int32_t* classes, int64_t* n);
+/* Device time of the last find's evidence kernel in ms: step 4b's launches (they run behind the scoring calls, inside
+ * rbs_find_stage_ms [1]) and step 7's (inside [3]). */
+int32_t rbs_find_gate_ms(rbs_find* f, float* out2);
 /* Message of the last error on this finder. Never NULL. */
 const char* rbs_find_last_error(const rbs_find* f);
 
@@ -886,6 +933,9 @@ void rbs_find_scene_destroy(rbs_find_scene* f);
 /* Steps 1b / 6b of every body's find, as rbs_find_set_foreground / rbs_find_set_refinement. */
 int32_t rbs_find_scene_set_foreground(rbs_find_scene* f, const rbs_find_foreground* g);
 int32_t rbs_find_scene_set_refinement(rbs_find_scene* f, const rbs_find_refinement* g);
+/* The gate of every body's find, as rbs_find_set_gate.  With require_confirmed, S3 leaves a body without a confirmed pose
+ * unplaced: its bit is clear in found_mask and the bodies after it do not explain its pixels away. */
+int32_t rbs_find_scene_set_gate(rbs_find_scene* f, const rbs_find_gate* g);
 /* One scene find.  frame: rows*cols floats (NULL: the sensor's current observation); search_mask: bit b = body b is
  * searched; given_poses [B][12] (read for the bodies not searched; may be NULL when all are searched); out_poses [B][12],
  * out_scores [B] (either may be NULL); *found_mask: bit b = searched body b has a pose with `found`; *joint_score. */

@@ -21,9 +21,12 @@ took away (rbs_find_get_plane); seeds_by_label: the find's seeds on the backgrou
 from the noise-free scene); meets_bar: translation < 1 cm, IoU >= 0.85, score >= 0.98 x the truth's.  --oracle-poses 0 skips
 the oracle's timing.  --refinement switches step 6b on (the library's default setting); --sigma-angle (degrees),
 --sigma-translation (metres) and --rounds set the search's start and length for either refinement.
+--gate switches the silhouette gate on (the library's default setting; --require-confirmed: found needs a confirmed pose 0);
+a case then carries "gate": the confirmed hypotheses / candidates / finals and the evidence kernel's two times (step 4b's lie
+inside stage_ms "coarse", step 7's inside "refinement"); per body for a scene, with the body's nearest candidate.
 Usage: python tools/find_object_timing.py [--finds N] [--oracle-poses P] [--cases m1,m2,m3,m4] [--foreground] [--seed-stride S]
                                           [--scene-seeds 101,102] [--refinement] [--sigma-angle DEG] [--sigma-translation M]
-                                          [--rounds R]
+                                          [--rounds R] [--gate [--require-confirmed]]
 --objects m1,m2,m3 times the SCENE finder (rbs_find_scene_*) instead: one scene of those meshes placed apart at 640x480 per
 scene seed (tests/scene_find_scenes.py), the same switches for every body's find, --explain-radius / --polish-sweeps for the
 scene finder's own parameters.  Its cases: {"case", "size", "ms_per_scene_find", "stage_ms": {"per_body", "render",
@@ -98,8 +101,19 @@ def oracle_s_per_pose(om, K, rows, cols, P, frame, poses):
     return s
 
 
+def gate_of(gate, require_confirmed):
+    return ObjectFinder.Gate(require_confirmed=bool(require_confirmed)) if gate else None
+
+
+def gate_report(fnd):
+    """The gate's figures of fnd's last find: confirmed hypotheses / candidates / finals and the evidence kernel's two times."""
+    ms = fnd.gate_ms()
+    return {"confirmed": {st: int((fnd.evidence(st)[1] == 0).sum()) for st in ("coarse", "candidates", "result")},
+            "evidence_ms": {"step_4b": round(ms[0], 3), "step_7": round(ms[1], 3)}}
+
+
 def run_case(name, finds, oracle_poses, seed=101, foreground=False, seed_stride=None, refinement=False, sigma_angle=None,
-             sigma_translation=None, rounds=None):
+             sigma_translation=None, rounds=None, gate=False, require_confirmed=False):
     mesh, cols, rows = CASES[name]
     om, cam, P = sc.make_scene((mesh,), cols, rows, max_particles=1)
     with RbSensor(om, cam, P, max_particles=1) as sensor:
@@ -114,7 +128,7 @@ def run_case(name, finds, oracle_poses, seed=101, foreground=False, seed_stride=
         if rounds is not None:
             p.rounds = rounds
         with ObjectFinder(sensor, om, p, foreground=ObjectFinder.Foreground() if foreground else None,
-                          refinement=ObjectFinder.Refinement() if refinement else None) as fnd:
+                          refinement=ObjectFinder.Refinement() if refinement else None, gate=gate_of(gate, require_confirmed)) as fnd:
             fnd.find(frame)                                       # warm-up
             t0 = time.perf_counter()
             for _ in range(finds):
@@ -123,6 +137,7 @@ def run_case(name, finds, oracle_poses, seed=101, foreground=False, seed_stride=
             st = fnd.stage_ms()
             seeds, _, _, info = fnd.stage("seeds")
             plane = fnd.plane()._asdict() if foreground else None
+            gated = gate_report(fnd) if gate else None
             cp, _, _, _ = fnd.stage("candidates")
             sp, _, _, _ = fnd.stage("survivors")
             kp, _, _, _ = fnd.stage("children", p.rounds - 1) if p.rounds else (np.zeros((0, 12)),) * 4
@@ -158,13 +173,14 @@ def run_case(name, finds, oracle_poses, seed=101, foreground=False, seed_stride=
             "found": found, "nearest_candidate": nearest(cp, truth), "nearest_survivor": nearest(sp, truth),
             "scene_seed": seed, "seed_stride": p.seed_stride, "foreground": bool(foreground), "plane": plane,
             "refinement": bool(refinement), "rounds": p.rounds, "sigma_angle_deg": round(math.degrees(p.sigma_angle), 3),
-            "sigma_translation": p.sigma_translation,
+            "sigma_translation": p.sigma_translation, "gate": gated, "require_confirmed": bool(gate and require_confirmed),
+            "found_flag": bool(r.found),
             "seeds_by_label": dict(zip(("plane", "object", "occluder"), (int((seed_labels == k).sum()) for k in range(3)))),
             "meets_bar": meets}
 
 
 def run_scene(names, finds, seed=101, foreground=False, seed_stride=None, refinement=False, sigma_angle=None, sigma_translation=None,
-              rounds=None, explain_radius=None, polish_sweeps=None):
+              rounds=None, explain_radius=None, polish_sweeps=None, gate=False, require_confirmed=False):
     import scene_find_scenes as ss
     from dbot_ros_amd.assess import PoseAssessor
     from dbot_ros_amd.finder import SceneFinder
@@ -185,7 +201,7 @@ def run_scene(names, finds, seed=101, foreground=False, seed_stride=None, refine
         sp.polish_sweeps = polish_sweeps
     with RbSensor(s.om, s.cam, s.P, max_particles=1) as sensor:
         with SceneFinder(sensor, s.om, p, sp, foreground=ObjectFinder.Foreground() if foreground else None,
-                         refinement=ObjectFinder.Refinement() if refinement else None) as fnd:
+                         refinement=ObjectFinder.Refinement() if refinement else None, gate=gate_of(gate, require_confirmed)) as fnd:
             fnd.find(s.frame)                                     # warm-up
             t0 = time.perf_counter()
             for _ in range(finds):
@@ -193,6 +209,13 @@ def run_scene(names, finds, seed=101, foreground=False, seed_stride=None, refine
             ms = (time.perf_counter() - t0) / finds * 1e3
             per_body, render, residual, polish, whole = fnd.stage_ms()
             order, _ = fnd.order()
+            gated = None
+            if gate:   # per searched body: the gate's figures, the coarse stage's time beside them, the nearest candidate
+                gated = []
+                for b in range(s.B):
+                    body = fnd.body_finder(b)
+                    gated.append(dict(gate_report(body), coarse_ms=round(body.stage_ms()[1], 3),
+                                      nearest_candidate=nearest(body.stage("candidates")[0], s.truth[b])))
         a = PoseAssessor(sensor)
 
         def planes(poses):
@@ -216,7 +239,8 @@ def run_scene(names, finds, seed=101, foreground=False, seed_stride=None, refine
             "joint_score": round(float(r.joint_score), 1), "truth_joint_score": round(truth_score, 1), "meets_bar": meets,
             "scene_seed": seed, "seed_stride": p.seed_stride, "foreground": bool(foreground), "refinement": bool(refinement),
             "rounds": p.rounds, "sigma_angle_deg": round(math.degrees(p.sigma_angle), 3), "sigma_translation": p.sigma_translation,
-            "explain_radius": sp.explain_radius, "polish_sweeps": sp.polish_sweeps}
+            "explain_radius": sp.explain_radius, "polish_sweeps": sp.polish_sweeps, "gate": gated,
+            "require_confirmed": bool(gate and require_confirmed)}
 
 
 def main():
@@ -234,14 +258,16 @@ def main():
     ap.add_argument("--objects", default="", help="meshes of one scene, e.g. m1,m2,m3: time the scene finder")
     ap.add_argument("--explain-radius", type=int, default=None)
     ap.add_argument("--polish-sweeps", type=int, default=None)
+    ap.add_argument("--gate", action="store_true", help="the silhouette gate at the library's defaults")
+    ap.add_argument("--require-confirmed", action="store_true", help="with --gate: found needs a confirmed pose 0")
     a = ap.parse_args()
     if a.objects:
         cases = [run_scene(tuple(a.objects.split(",")), a.finds, int(s), a.foreground, a.seed_stride, a.refinement, a.sigma_angle,
-                           a.sigma_translation, a.rounds, a.explain_radius, a.polish_sweeps) for s in a.scene_seeds.split(",")]
+                           a.sigma_translation, a.rounds, a.explain_radius, a.polish_sweeps, a.gate, a.require_confirmed) for s in a.scene_seeds.split(",")]
         print(json.dumps({"tool": "find_object_timing", "cases": cases}))
         return
     cases = [run_case(c, a.finds, a.oracle_poses, int(s), a.foreground, a.seed_stride, a.refinement, a.sigma_angle, a.sigma_translation,
-                      a.rounds) for c in a.cases.split(",")
+                      a.rounds, a.gate, a.require_confirmed) for c in a.cases.split(",")
              for s in a.scene_seeds.split(",")]
     print(json.dumps({"tool": "find_object_timing", "cases": cases}))
 
