@@ -43,7 +43,7 @@ EXPORTS = (
     "rbs_last_kernel_ms", "rbs_timing_summary",
     "rbs_tracker_create", "rbs_tracker_destroy", "rbs_tracker_initialize", "rbs_tracker_track",
     "rbs_tracker_submit", "rbs_tracker_result", "rbs_tracker_track_f64", "rbs_tracker_submit_f64",
-    "rbs_tracker_get",
+    "rbs_tracker_get", "rbs_tracker_set_posterior", "rbs_tracker_posterior", "rbs_tracker_posterior_ms",
     "rbs_gauss_create", "rbs_gauss_destroy", "rbs_gauss_initialize", "rbs_gauss_track", "rbs_gauss_track_f64",
     "rbs_gauss_get_prior", "rbs_gauss_get_sigma_poses", "rbs_gauss_get_render", "rbs_gauss_get_moments",
     "rbs_gauss_kernel_ms", "rbs_gauss_submit", "rbs_gauss_submit_f64", "rbs_gauss_result",
@@ -70,6 +70,16 @@ class RbsTrackerParams(C.Structure):
         ("velocity_factor", C.c_double),
         ("max_kl_divergence", C.c_double),
         ("n_particles", C.c_int32),
+    ]
+
+
+class RbsTrackerPosteriorInfo(C.Structure):
+    _fields_ = [
+        ("n", C.c_int32),
+        ("survivors", C.c_int32),
+        ("resampled", C.c_int32),
+        ("frame", C.c_int32),
+        ("ess", C.c_double),
     ]
 
 
@@ -372,6 +382,12 @@ def load():
     lib.rbs_tracker_result.argtypes = [H, dp, ip]
     lib.rbs_tracker_get.restype = C.c_int32
     lib.rbs_tracker_get.argtypes = [H, dp, dp, ip]
+    lib.rbs_tracker_set_posterior.restype = C.c_int32
+    lib.rbs_tracker_set_posterior.argtypes = [H, C.c_int32]
+    lib.rbs_tracker_posterior.restype = C.c_int32
+    lib.rbs_tracker_posterior.argtypes = [H, C.POINTER(RbsTrackerPosteriorInfo), dp, dp]
+    lib.rbs_tracker_posterior_ms.restype = C.c_int32
+    lib.rbs_tracker_posterior_ms.argtypes = [H, fp]
     lib.rbs_gauss_create.restype = C.c_int32
     lib.rbs_gauss_create.argtypes = [H, C.POINTER(RbsGaussParams), C.POINTER(H)]
     lib.rbs_gauss_destroy.restype = None

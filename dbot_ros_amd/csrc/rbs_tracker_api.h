@@ -32,6 +32,18 @@ struct rbs_tracker {
     long submitted = 0, collected = 0;
     bool recentre_pending = false;    // T.part_old still holds the particles before the last frame's re-centring
     bool poisoned = false;            // a frame failed half-way (buffers partly swapped): rbs_tracker_initialize first
+    // the posterior report (rbs_tracker_set_posterior, rbsensor_posterior.hip): off by default.  Per in-flight frame a pinned
+    // slot the frame's last kernels write ([1 + D + D D] doubles, then 4 ints) and the event recorded behind them;
+    // rbs_tracker_result copies the slot into `post` / `post_i`, so the slot is free for the next-but-one submit.
+    bool post_on = false, post_valid = false, post_ready = false;   // post_ready: every buffer and event below exists
+    rbt::PostDev P{};
+    double* h_post[2] = {nullptr, nullptr};
+    double* h_post_dev[2] = {nullptr, nullptr};
+    hipEvent_t ev_post[2] = {nullptr, nullptr};
+    hipEvent_t ev_post0[2] = {nullptr, nullptr};   // in front of the report's first launch: its device time (rbs_tracker_posterior_ms)
+    float post_ms = 0.f;
+    std::vector<double> post;
+    int32_t post_i[4] = {0, 0, 0, 0};
 };
 
 namespace {
@@ -109,6 +121,23 @@ void launch_filter_step(const rbt::TrackerDev& T, int b, int updated, int last, 
 void launch_recentre(const rbt::TrackerDev& T, double* particles, hipStream_t s)
 {
     hipLaunchKernelGGL(rbt::recentre_kernel, per_particle_grid(T), dim3(256), 0, s, T, particles);
+}
+// The posterior report of the population in `particles` (the frame's last launches; recentred: 0 = the re-centring is
+// pending and T.mean holds what it needs -- one launch in front re-centres a copy of the poses): one block below
+// kMultiBlockFrom particles, five grid launches from there on.
+void launch_posterior(const rbt::TrackerDev& T, const rbt::PostDev& P, const double* particles, int recentred, hipStream_t s)
+{
+    if (!recentred) hipLaunchKernelGGL(rbt::rbs_post_recentre_kernel, per_particle_grid(T), dim3(256), 0, s, T, P, particles);
+    if (T.n < rbt::kMultiBlockFrom) {
+        hipLaunchKernelGGL(rbt::rbs_post_kernel, dim3(1), dim3(1024), 0, s, T, P, particles, recentred);
+        return;
+    }
+    const unsigned blocks = (unsigned)rbt::post_blocks(T.n), G = (unsigned)(T.D / 6);
+    hipLaunchKernelGGL(rbt::rbs_post_max_kernel, dim3(blocks), dim3(1024), 0, s, T, P);
+    hipLaunchKernelGGL(rbt::rbs_post_sums_kernel, dim3(blocks), dim3(1024), 0, s, T, P, particles, recentred);
+    hipLaunchKernelGGL(rbt::rbs_post_mean_kernel, dim3(1), dim3(1024), 0, s, T, P, (int)blocks);
+    hipLaunchKernelGGL(rbt::rbs_post_cov_kernel, dim3(blocks, G * (G + 1)), dim3(1024), 0, s, T, P, particles, recentred);
+    hipLaunchKernelGGL(rbt::rbs_post_cov_fold_kernel, dim3(1), dim3(1024), 0, s, T, P, (int)blocks);
 }
 // after a sampling block's gather: the gathered arrays are the block's result
 void swap_gathered(rbt::TrackerDev& T)
@@ -233,6 +262,9 @@ void rbs_tracker_destroy(rbs_tracker* t)
         if (t->h_flags[k]) (void)hipHostFree(t->h_flags[k]);
         if (t->h_serr[k]) (void)hipHostFree(t->h_serr[k]);
         if (t->ev_res[k]) (void)hipEventDestroy(t->ev_res[k]);
+        if (t->h_post[k]) (void)hipHostFree(t->h_post[k]);
+        if (t->ev_post[k]) (void)hipEventDestroy(t->ev_post[k]);
+        if (t->ev_post0[k]) (void)hipEventDestroy(t->ev_post0[k]);
     }
     delete t;
 }
@@ -244,6 +276,7 @@ int32_t rbs_tracker_initialize(rbs_tracker* t, const double* default_state)
     t->submitted = t->collected = 0;
     t->recentre_pending = false;
     t->poisoned = false;
+    t->post_valid = false;
     if (!t->reps.empty()) {
         for (rbs_tracker* r : t->reps)
             if (int32_t rc = rbs_tracker_initialize(r, default_state)) { t->s->err = r->s->err; return rc; }
@@ -485,6 +518,7 @@ static int32_t tracker_submit_impl(rbs_tracker* t, const float* frame, const dou
         RBT_HIP(t, hipGetLastError());
         swap_gathered(T);
     }
+    bool recentred = fused;   // (filter_step_kernel re-centres behind its mean)
     if (!fused) {
         // (re-centring inside the single mean block was tried: its two rounds of rotations per thread
         // on one CU take longer than the separate launch, 25 us against 16.5 + 5)
@@ -494,8 +528,21 @@ static int32_t tracker_submit_impl(rbs_tracker* t, const float* frame, const dou
         static const bool now = [] { const char* e = std::getenv("RBS_TRACKER_RECENTRE_NOW"); return e && std::atoi(e) != 0; }();
         if (now) launch_recentre(T, T.part_new, s);
         else t->recentre_pending = true;
+        recentred = now;
     }
     RBT_HIP(t, hipGetLastError());
+    if (t->post_on) {
+        // the report of the population this frame leaves in T.part_new (named here, before the swap below renames it), behind
+        // the frame's last kernel -- in the tail route behind the gather -- and an event of its own: the estimate's sequence
+        // number and ev_res do not wait for it
+        rbt::PostDev P = t->P;
+        P.out = t->h_post_dev[slot];
+        P.out_i = reinterpret_cast<int*>(P.out + rbt::post_out_doubles(T.D));
+        RBT_HIP(t, hipEventRecord(t->ev_post0[slot], s));
+        launch_posterior(T, P, T.part_new, recentred ? 1 : 0, s);
+        RBT_HIP(t, hipGetLastError());
+        RBT_HIP(t, hipEventRecord(t->ev_post[slot], s));
+    }
     std::swap(T.part_old, T.part_new);   // this frame's particles are the next frame's old ones
     // (the estimate and the flags were stored into h_state[slot] / h_flags[slot] by the kernel that
     // finished them: no copies behind the last kernel)
@@ -556,6 +603,14 @@ int32_t rbs_tracker_result(rbs_tracker* t, double* out_state, int32_t* out_resam
             }
         }
         if (!seen) RBT_HIP(t, hipEventSynchronize(t->ev_res[slot]));
+        if (t->post_on) {   // the report is finished behind the estimate: wait for it and take it out of the slot
+            RBT_HIP(t, hipEventSynchronize(t->ev_post[slot]));
+            const size_t nd = rbt::post_out_doubles(D);
+            std::memcpy(t->post.data(), t->h_post[slot], sizeof(double) * nd);
+            std::memcpy(t->post_i, t->h_post[slot] + nd, sizeof(t->post_i));
+            if (hipEventElapsedTime(&t->post_ms, t->ev_post0[slot], t->ev_post[slot]) != hipSuccess) { (void)hipGetLastError(); t->post_ms = 0.f; }
+            t->post_valid = true;
+        }
     }
     std::memcpy(out_state, r->h_state[slot], sizeof(double) * D);
     if (out_resamplings) *out_resamplings = r->h_flags[slot][1];
@@ -631,6 +686,69 @@ int32_t rbs_tracker_get(rbs_tracker* t, double* particles, double* log_weights, 
     if (particles) RBT_HIP(t, hipMemcpy(particles, T.part_old, sizeof(double) * (size_t)T.n * T.D, hipMemcpyDeviceToHost));
     if (log_weights) RBT_HIP(t, hipMemcpy(log_weights, T.logw, sizeof(double) * (size_t)T.n, hipMemcpyDeviceToHost));
     if (indices) RBT_HIP(t, hipMemcpy(indices, T.idx, sizeof(int) * (size_t)T.n, hipMemcpyDeviceToHost));
+    return RBS_OK;
+}
+
+int32_t rbs_tracker_set_posterior(rbs_tracker* t, int32_t enable)
+{
+    if (!t) return RBS_ERR_INVALID_ARGUMENT;
+    if (!t->reps.empty() || !t->s->shards.empty())
+        return tfail(t, RBS_ERR_UNSUPPORTED, "tracker_set_posterior: single-device trackers only");
+    if (t->submitted != t->collected)
+        return tfail(t, RBS_ERR_INVALID_ARGUMENT, "tracker_set_posterior: frames are in flight (call rbs_tracker_result)");
+    rbt::TrackerDev& T = t->T;
+    if (enable && !t->post_ready) {
+        // every buffer is made once, each only where an earlier attempt that failed half-way has not left it; the report is
+        // switched on only when all of them exist
+        RBT_HIP(t, hipSetDevice(t->s->device));
+        const size_t nd = rbt::post_out_doubles(T.D);
+        if (!t->P.pose) if (int32_t rc = talloc(t, &t->P.pose, (size_t)T.n * T.parts * 6)) return rc;
+        if (!t->P.e) if (int32_t rc = talloc(t, &t->P.e, (size_t)T.n)) return rc;
+        if (T.n >= rbt::kMultiBlockFrom) {
+            if (!t->P.partials) if (int32_t rc = talloc(t, &t->P.partials, rbt::post_partials_doubles(T.n, T.D))) return rc;
+            if (!t->P.bitmap) if (int32_t rc = talloc(t, &t->P.bitmap, (size_t)(T.n + 31) / 32)) return rc;
+        }
+        t->post.assign(nd, 0.0);
+        for (int k = 0; k < 2; ++k) {
+            if (!t->h_post[k]) RBT_HIP(t, hipHostMalloc(&t->h_post[k], sizeof(double) * nd + 4 * sizeof(int), hipHostMallocDefault));
+            if (!t->h_post_dev[k]) RBT_HIP(t, hipHostGetDevicePointer(reinterpret_cast<void**>(&t->h_post_dev[k]), t->h_post[k], 0));
+            if (!t->ev_post[k]) RBT_HIP(t, hipEventCreate(&t->ev_post[k]));
+            if (!t->ev_post0[k]) RBT_HIP(t, hipEventCreate(&t->ev_post0[k]));
+        }
+        t->post_ready = true;
+    }
+    t->post_on = enable != 0;
+    t->post_valid = false;
+    return RBS_OK;
+}
+
+int32_t rbs_tracker_posterior(rbs_tracker* t, rbs_tracker_posterior_info* info, double* mean, double* cov)
+{
+    if (!t) return RBS_ERR_INVALID_ARGUMENT;
+    if (t->poisoned || t->s->poisoned)
+        return tfail(t, RBS_ERR_HIP, "tracker_posterior: an earlier frame failed half-way (" + (t->s->poisoned ? t->s->poison_msg : t->err) +
+                                         "): call rbs_tracker_initialize");
+    if (!t->post_on) return tfail(t, RBS_ERR_INVALID_ARGUMENT, "tracker_posterior: the report is off (rbs_tracker_set_posterior)");
+    if (!t->post_valid) return tfail(t, RBS_ERR_INVALID_ARGUMENT, "tracker_posterior: no frame has been handed out since rbs_tracker_initialize");
+    const size_t D = (size_t)t->T.D;
+    if (info) {
+        info->n = t->post_i[0];
+        info->survivors = t->post_i[1];
+        info->resampled = t->post_i[2];
+        info->frame = t->post_i[3];
+        info->ess = t->post[0];
+    }
+    if (mean) std::memcpy(mean, t->post.data() + 1, sizeof(double) * D);
+    if (cov) std::memcpy(cov, t->post.data() + 1 + D, sizeof(double) * D * D);
+    return RBS_OK;
+}
+
+int32_t rbs_tracker_posterior_ms(rbs_tracker* t, float* ms)
+{
+    if (!t) return RBS_ERR_INVALID_ARGUMENT;
+    if (!ms) return tfail(t, RBS_ERR_INVALID_ARGUMENT, "tracker_posterior_ms: null output");
+    if (!t->post_on || !t->post_valid) return tfail(t, RBS_ERR_INVALID_ARGUMENT, "tracker_posterior_ms: no report has been handed out");
+    *ms = t->post_ms;
     return RBS_OK;
 }
 

@@ -20,6 +20,7 @@
 // This file itself: release / create_impl, several devices, and the remaining extern "C" sensor entry points.
 #include "rbsensor_kernels.hip"
 #include "rbsensor_tracker.hip"
+#include "rbsensor_posterior.hip"
 #include "rbsensor_peers.hip"
 #include "rbs_mesh.h"
 

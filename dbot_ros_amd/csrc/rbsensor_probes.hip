@@ -10,7 +10,8 @@
 // rbs_test_filter does the same for the particle filter's kernels (rbsensor_tracker.hip): it builds an rbt::TrackerDev from host
 // arrays, launches a caller-chosen order of the frame's steps through the launch_* helpers rbs_tracker_submit itself uses
 // (rbs_tracker_api.h: no kernel body and no launch geometry is restated here), and hands every array back:
-// tests/test_gpu_filter_kernels.py.
+// tests/test_gpu_filter_kernels.py.  rbs_test_posterior is the same for the posterior report's kernels (rbsensor_posterior.hip,
+// launch_posterior): tests/test_gpu_tracker_posterior.py.
 //
 // rbs_test_find_* do the same for the object finder's kernels (rbsensor_find.hip), one entry point per launch helper
 // (rbf::launch_*, the ones rbs_find_run itself calls): tests/test_gpu_finder_kernels.py.  Every output array there is IN and
@@ -417,6 +418,48 @@ extern "C" int32_t rbs_test_filter(const rbs_test_filter_io* io, const rbs_test_
     }
     if (h_state) (void)hipHostFree(h_state);
     if (h_flags) (void)hipHostFree(h_flags);
+    return B.status();
+}
+
+// ---------------------------------------------------------------------------- the posterior report's kernels
+// Planted particles [n][parts * 12], log-weights [n], slot map [n], the mean rows and transposed mean rotations
+// [parts * 12 + parts * 9] recentre_body reads, and the re-centred flag, through launch_posterior -- the helper
+// rbs_tracker_submit itself calls: out [1 + D + D D] := ess, mean, cov; out_i [4] := n, survivors, resampled, frame + 1.
+// particles, logw and idx come back as the device holds them afterwards (the kernels must have left them alone).
+extern "C" int32_t rbs_test_posterior(int32_t n, int32_t parts, double* particles, double* logw, int32_t* idx, const double* mean,
+                                      int32_t recentred, int32_t resampled, uint64_t frame, double* out, int32_t* out_i)
+{
+    namespace pr = rbs::probe;
+    if (n < 1 || n > rbt::kRedBlocks * rbt::kChunk || parts < 1 || parts > rbs::kMaxBodies) return RBS_ERR_INVALID_ARGUMENT;
+    if (!particles || !logw || !idx || !mean || !out || !out_i) return RBS_ERR_INVALID_ARGUMENT;
+    const size_t N = (size_t)n, D = (size_t)parts * rbt::kBody, nd = rbt::post_out_doubles((int)D);
+    const int flags[2] = {resampled ? 1 : 0, 0};
+    pr::Buffers B;
+    rbt::TrackerDev T{};
+    T.n = n; T.parts = parts; T.D = (int)D; T.frame = frame;
+    double* part = B.make<double>(N * D, particles);
+    T.logw = B.make<double>(N, logw);
+    T.idx = B.make<int>(N, idx);
+    T.mean = B.make<double>(D + (size_t)parts * 9, mean);
+    T.flag = B.make<int>(2, flags);
+    rbt::PostDev P{};
+    P.pose = B.make<double>(N * parts * 6);
+    P.e = B.make<double>(N);
+    P.partials = B.make<double>(rbt::post_partials_doubles(n, (int)D));
+    P.bitmap = B.make<unsigned>((N + 31) / 32);
+    P.out = B.make<double>(nd);
+    P.out_i = B.make<int>(4);
+    if (B.err == hipSuccess) B.err = hipMemset(P.out, 0xff, sizeof(double) * nd);
+    if (B.err == hipSuccess) B.err = hipMemset(P.bitmap, 0xff, sizeof(unsigned) * ((N + 31) / 32));   // (the kernels clear it themselves)
+    if (B.err == hipSuccess) {
+        launch_posterior(T, P, part, recentred ? 1 : 0, nullptr);
+        B.ran();
+    }
+    B.fetch(out, P.out, nd);
+    B.fetch(out_i, P.out_i, 4);
+    B.fetch(particles, part, N * D);
+    B.fetch(logw, T.logw, N);
+    B.fetch(idx, T.idx, N);
     return B.status();
 }
 

@@ -26,9 +26,12 @@ def load_rosparams(*yaml_paths):
 
 
 def build_particle_tracker(params, native_camera_matrix, mesh_package_path, device_id=0, rng=None,
-                           device_filter=True, seed=0):
-    """params: merged rosparam tree.  Returns (tracker, object_model, camera_data, ori)."""
+                           device_filter=True, seed=0, posterior=False):
+    """params: merged rosparam tree.  Returns (tracker, object_model, camera_data, ori).
+    posterior: switch the device tracker's posterior report on (tracker.posterior() after every frame); the optional key
+    particle_filter/posterior of the tree does the same (absent: off -- the reference's YAML files parse unchanged)."""
     pre = params["particle_filter"]
+    posterior = bool(posterior) or bool(pre.get("posterior", False))
     # ---- object model (node :78-97)
     obj = params["object"]
     ori = ObjectResourceIdentifier(mesh_package_path, obj["directory"], obj["meshes"])
@@ -47,7 +50,7 @@ def build_particle_tracker(params, native_camera_matrix, mesh_package_path, devi
     params_tracker = ParticleTrackerBuilder.Parameters.from_rosparam(params, params_obsrv.sample_count)
     if device_filter:
         tracker = DeviceParticleTracker(transition, sensor, object_model, params_tracker, rng,
-                                        device_rng=rng is None, seed=seed)
+                                        device_rng=rng is None, seed=seed, posterior=posterior)
     else:
         tracker = ParticleTracker(transition, sensor, object_model, params_tracker, rng)
     return tracker, object_model, camera_data, ori
@@ -136,7 +139,7 @@ def to_eigen_vector(native_image, downsampling_factor):
 
 
 def replay_dataset(params, dataset, mesh_package_path, initial_states=None, device_id=0, seed=0, max_frames=None,
-                   look_ahead=False):
+                   look_ahead=False, posterior=False):
     """Run the tracker over a recorded TrackingDataset (dbot_ros_amd.dataset) the way
     the node runs over live topics: K from the bag's camera_info (frame 0, as GetCameraMatrix does,
     R:source/dbot_ros/util/tracking_dataset.cpp:157-164), every depth image sub-sampled by
@@ -149,10 +152,13 @@ def replay_dataset(params, dataset, mesh_package_path, initial_states=None, devi
     (R:source/dbot_ros/tracker/object_tracker_controller_service_node.cpp:143-167) -- the object is found on frame 0
     by an object finder over the tracker's own sensor, and the tracker starts from its best state; a tree of several
     objects takes a scene finder (build_scene_finder) and starts from the one state of all its bodies.
-    Returns (estimates [frames, parts*12], wall seconds of the tracking loop)."""
+    posterior: the device's posterior report (tracker.posterior()) is switched on and collected after every estimate.
+    Returns (estimates [frames, parts*12], wall seconds of the tracking loop); with posterior additionally the list of
+    per-frame tracker.Posterior reports."""
     import time
     tracker, object_model, camera_data, _ = build_particle_tracker(params, dataset.get_camera_matrix(0),
-                                                                   mesh_package_path, device_id=device_id, seed=seed)
+                                                                   mesh_package_path, device_id=device_id, seed=seed,
+                                                                   posterior=posterior)
     f = int(params["downsampling_factor"])
     try:
         n = dataset.size() if max_frames is None else min(max_frames, dataset.size())
@@ -178,21 +184,28 @@ def replay_dataset(params, dataset, mesh_package_path, initial_states=None, devi
                 raise RuntimeError("replay_dataset: the object finder found no object on frame 0")
             initial_states = [found.states[0]]
         tracker.initialize(initial_states)
-        ests = []
+        ests, reports = [], []
+
+        def collect(est):
+            ests.append(est)
+            if posterior:
+                reports.append(tracker.posterior())
         t0 = time.perf_counter()
         if look_ahead and hasattr(tracker, "submit") and frames:
             tracker.submit(frames[0])
             for fr in frames[1:]:
                 tracker.submit(fr)
-                ests.append(tracker.result())
-            ests.append(tracker.result())
+                collect(tracker.result())
+            collect(tracker.result())
         else:
             for fr in frames:
-                ests.append(tracker.track(fr))
+                collect(tracker.track(fr))
         wall = time.perf_counter() - t0
     finally:
         tracker.close()
         tracker.sensor.close()
+    if posterior:
+        return np.array(ests), wall, reports
     return np.array(ests), wall
 
 

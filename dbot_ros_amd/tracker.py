@@ -23,6 +23,49 @@ from .pose import matrix_to_rotvec, pack_Rt, rotvec_to_matrix
 BODY = 12
 
 
+@dataclass
+class Posterior:
+    """What a particle tracker knows about its own estimate after a frame (include/rbsensor_mi355x.h, "Posterior report").
+    mean [D], cov [D, D]: weighted moments of the re-centred particle deltas, D = 12 per body (position, rotation vector,
+    linear and angular velocity), MODEL coordinates: translations add in the camera frame, rotations multiply from the left.
+    ess: effective sample size; survivors: distinct occlusion slots among the particles; resampled: the frame's last
+    sampling block resampled; n: particles; frame: frames tracked since initialize."""
+    mean: np.ndarray
+    cov: np.ndarray
+    ess: float
+    survivors: int
+    resampled: bool
+    n: int
+    frame: int = 0
+
+
+def posterior_of(particles, log_weights, indices, resampled=False, frame=0):
+    """The rule of the posterior report in numpy -- the restatement the device kernels (csrc/rbsensor_posterior.hip) are
+    tested against.  particles [n, D] re-centred deltas, log_weights [n] (-inf: no contribution), indices [n].
+    Two passes: the mean, then central moments; the upper triangle mirrored."""
+    x = np.asarray(particles, dtype=np.float64)
+    x = x.reshape(x.shape[0], -1)
+    lw = np.asarray(log_weights, dtype=np.float64)
+    e = np.exp(lw - lw.max())
+    S = e.sum()
+    mean = (e[:, None] * x).sum(axis=0) / S
+    d = x - mean
+    full = (e[:, None] * d).T @ d / S
+    cov = np.triu(full) + np.triu(full, 1).T
+    return Posterior(mean=mean, cov=cov, ess=float(S * S / (e * e).sum()), survivors=int(np.unique(np.asarray(indices)).size),
+                     resampled=bool(resampled), n=int(x.shape[0]), frame=int(frame))
+
+
+def object_frame_jacobian(R, c):
+    """d(published pose) / d(model pose), 6 x 6, to first order.  With center_object_frame the published position is
+    p = t - R c (R: the body's absolute rotation, c: its centring offset); a model perturbation (dt, dtheta) -- dtheta
+    from the left, R' = R(dtheta) R -- moves it by dp = dt + [R c]x dtheta and turns the published rotation by dtheta."""
+    v = np.asarray(R, dtype=np.float64) @ np.asarray(c, dtype=np.float64)
+    J = np.eye(6)
+    J[0:3, 3:6] = np.array([[0.0, -v[2], v[1]], [v[2], 0.0, -v[0]], [-v[1], v[0], 0.0]])
+    return J
+
+
 class ObjectTransitionBuilder:
     @dataclass
     class Parameters:
@@ -110,6 +153,7 @@ class ParticleTracker:
         self.indices = np.zeros(self.n, dtype=np.int32)
         self.moving_average = None
         self.n_resamplings = 0
+        self._resampled, self._frames = False, 0
 
     # -- State <-> model coordinates ---------------------------------------------------------
     def _to_model(self, state):
@@ -138,6 +182,7 @@ class ParticleTracker:
         self.loglikes[:] = 0.0
         self.indices[:] = 0
         self.moving_average = None
+        self._resampled, self._frames = False, 0
         self.sensor.reset()
 
     def absolute_poses(self, particles):
@@ -173,7 +218,8 @@ class ParticleTracker:
             self.log_weights += new_ll - self.loglikes
             self.loglikes = new_ll
             w = flt.normalized_weights(self.log_weights)
-            if flt.kl_to_uniform(w) > self.params.max_kl_divergence:
+            self._resampled = bool(flt.kl_to_uniform(w) > self.params.max_kl_divergence)
+            if self._resampled:
                 parents = flt.multinomial_resample(w, uniforms[b])
                 self.n_resamplings += 1
                 self.indices = self.indices[parents].copy()
@@ -194,10 +240,32 @@ class ParticleTracker:
             p[:, b, 0:3] -= mean[b, 0:3]
             Rd = rotvec_to_matrix(p[:, b, 3:6]) @ Rm.T
             p[:, b, 3:6] = _rotvecs(Rd)
+        self._frames += 1
         est = self._from_model(self.default)
         rate = self.params.moving_average_update_rate
         self.moving_average = est if self.moving_average is None else rate * est + (1 - rate) * self.moving_average
         return self.moving_average.copy()
+
+    # -- the spread of the last estimate -------------------------------------------------------
+    def posterior(self):
+        """Posterior of the population the last frame left behind (posterior_of on this tracker's own arrays)."""
+        if self._frames == 0:
+            raise ValueError("posterior: no frame has been tracked since initialize")
+        return posterior_of(self.particles, self.log_weights, self.indices, self._resampled, self._frames)
+
+    def pose_covariance(self, posterior):
+        """[parts, 6, 6]: per body the covariance of the PUBLISHED pose (position, rotation; camera frame, left
+        perturbation) -- J C J^T with object_frame_jacobian when center_object_frame moves the published position to
+        t - R c, the model block itself otherwise.  R is taken from the last estimate (self.default)."""
+        z = self.default.reshape(self.parts, BODY)
+        out = np.empty((self.parts, 6, 6))
+        for b in range(self.parts):
+            C = posterior.cov[BODY * b:BODY * b + 6, BODY * b:BODY * b + 6]
+            if self.params.center_object_frame:
+                J = object_frame_jacobian(rotvec_to_matrix(z[b, 3:6]), self.centers[b])
+                C = J @ C @ J.T
+            out[b] = C
+        return out
 
     # -- the last estimate judged against its frame (dbot_ros_amd/assess.py) -------------------
     _in_flight = 0   # frames submitted and not yet collected (the device trackers' submit / result)
@@ -234,7 +302,7 @@ class DeviceParticleTracker(ParticleTracker):
     device_rng=True the normals/uniforms are drawn on the device (Philox), otherwise they come
     from this object's numpy Generator exactly as in the host tracker."""
 
-    def __init__(self, transition, sensor, object_model, params, rng=None, device_rng=False, seed=0):
+    def __init__(self, transition, sensor, object_model, params, rng=None, device_rng=False, seed=0, posterior=False):
         import ctypes as C
         from . import _capi
         super().__init__(transition, sensor, object_model, params, rng)
@@ -252,6 +320,30 @@ class DeviceParticleTracker(ParticleTracker):
         if rc != 0:
             sensor._check(rc)
         sensor._register_dependent(self)   # the C tracker borrows the sensor handle
+        if posterior:
+            self.set_posterior(True)
+
+    def set_posterior(self, enable):
+        """Switch the device's posterior report on or off (rbs_tracker_set_posterior; refused with frames in flight)."""
+        self.sensor._check(self._lib.rbs_tracker_set_posterior(self._t, 1 if enable else 0))
+
+    def posterior(self):
+        """The report of the frame most recently handed out by track() / result() (rbs_tracker_posterior), reduced on
+        the device; needs posterior=True (or set_posterior(True)) -- an RbSensorError otherwise."""
+        C = self._C
+        D = self.parts * BODY
+        info = self._capi.RbsTrackerPosteriorInfo()
+        mean, cov = np.empty(D), np.empty((D, D))
+        dp = C.POINTER(C.c_double)
+        self.sensor._check(self._lib.rbs_tracker_posterior(self._t, C.byref(info), mean.ctypes.data_as(dp), cov.ctypes.data_as(dp)))
+        return Posterior(mean=mean, cov=cov, ess=float(info.ess), survivors=int(info.survivors), resampled=bool(info.resampled),
+                         n=int(info.n), frame=int(info.frame))
+
+    def posterior_ms(self):
+        """Device time of the last report's kernels in milliseconds (rbs_tracker_posterior_ms)."""
+        ms = self._C.c_float()
+        self.sensor._check(self._lib.rbs_tracker_posterior_ms(self._t, self._C.byref(ms)))
+        return float(ms.value)
 
     def close(self):
         if getattr(self, "_t", None) is not None and self._t.value:

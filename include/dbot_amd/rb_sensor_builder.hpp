@@ -435,6 +435,74 @@ public:
     }
     int resamplings() const { return resamplings_; }
 
+    /// The posterior report of the frame most recently handed out by track() / result() (rbs_tracker_posterior): weighted
+    /// mean [D] and covariance [D][D] (row-major) of the re-centred particle deltas, D = 12 per body -- position, rotation
+    /// vector, linear and angular velocity; MODEL coordinates: translations add in the camera frame, rotations multiply from
+    /// the left -- and the health of the sample.
+    struct Posterior {
+        std::vector<Real> mean, cov;
+        Real ess = 0;
+        int survivors = 0;
+        bool resampled = false;
+        int n = 0;
+        int frame = 0;
+    };
+    /// Switch the report on or off (off by default; refused while frames are in flight).
+    void enable_posterior(bool on) { check(rbs_tracker_set_posterior(t_, on ? 1 : 0)); }
+    Posterior posterior() const
+    {
+        const size_t D = static_cast<size_t>(parts_) * 12;
+        Posterior p;
+        p.mean.resize(D);
+        p.cov.resize(D * D);
+        rbs_tracker_posterior_info info{};
+        check(rbs_tracker_posterior(t_, &info, p.mean.data(), p.cov.data()));
+        p.ess = info.ess;
+        p.survivors = info.survivors;
+        p.resampled = info.resampled != 0;
+        p.n = info.n;
+        p.frame = info.frame;
+        return p;
+    }
+    /// Per body the 6 x 6 covariance (row-major, [parts][36]) of the PUBLISHED pose -- position, rotation; camera frame,
+    /// left perturbation.  With center_object_frame the published position is t - R c, to first order
+    /// dp = dt + [R c]x dtheta: J C J^T with J = [[I, [R c]x], [0, I]], R the body's rotation in the last estimate and c
+    /// its centring offset; the model block itself otherwise.
+    std::vector<Real> pose_covariance(const Posterior& p) const
+    {
+        const size_t D = static_cast<size_t>(parts_) * 12;
+        std::vector<Real> out(static_cast<size_t>(parts_) * 36);
+        for (int b = 0; b < parts_; ++b) {
+            Real J[36] = {0}, C[36], JC[36];
+            for (int k = 0; k < 6; ++k) J[7 * k] = 1.0;
+            if (center_) {
+                Real R[9];
+                State::rotation_matrix(model_.euler_vector(b), R);
+                const Real* c = om_->centers().data() + 3 * b;
+                Real v[3];
+                for (int r = 0; r < 3; ++r) v[r] = R[3 * r] * c[0] + R[3 * r + 1] * c[1] + R[3 * r + 2] * c[2];
+                J[0 * 6 + 4] = -v[2]; J[0 * 6 + 5] = v[1];
+                J[1 * 6 + 3] = v[2];  J[1 * 6 + 5] = -v[0];
+                J[2 * 6 + 3] = -v[1]; J[2 * 6 + 4] = v[0];
+            }
+            for (int r = 0; r < 6; ++r)
+                for (int k = 0; k < 6; ++k) C[6 * r + k] = p.cov[(12 * b + r) * D + 12 * b + k];
+            for (int r = 0; r < 6; ++r)
+                for (int k = 0; k < 6; ++k) {
+                    Real s = 0;
+                    for (int j = 0; j < 6; ++j) s += J[6 * r + j] * C[6 * j + k];
+                    JC[6 * r + k] = s;
+                }
+            for (int r = 0; r < 6; ++r)
+                for (int k = 0; k < 6; ++k) {
+                    Real s = 0;
+                    for (int j = 0; j < 6; ++j) s += JC[6 * r + j] * J[6 * k + j];
+                    out[static_cast<size_t>(b) * 36 + 6 * r + k] = s;
+                }
+        }
+        return out;
+    }
+
 private:
     void check(int32_t rc) const
     {
@@ -443,6 +511,7 @@ private:
     State averaged(const State& model, int32_t nres)
     {
         resamplings_ = nres;
+        model_ = model;
         State est = from_model(model);
         if (!have_average_) { average_ = est; have_average_ = true; }
         else
@@ -473,6 +542,7 @@ private:
     int parts_;
     rbs_tracker* t_ = nullptr;
     State average_{1};
+    State model_{1};   // the last estimate in model coordinates (pose_covariance's rotation)
     bool have_average_ = false;
     int resamplings_ = 0;
 };

@@ -561,6 +561,51 @@ int32_t rbs_tracker_submit_f64(rbs_tracker* t, const double* frame, const double
  * (any pointer may be NULL). */
 int32_t rbs_tracker_get(rbs_tracker* t, double* particles, double* log_weights, int32_t* indices);
 
+/* Posterior report (opt-in): what the filter knows about its own estimate, reduced on the device at the end of every
+ * frame -- the spread a consumer fuses or gates with (a PoseWithCovariance), and the health of the sample.
+ *
+ * The rule.  At the end of a frame, after the last sampling block's resampling and gather, the tracker holds n particles:
+ * x_i in R^D, D = 12 n_objects, the RE-CENTRED deltas -- exactly what rbs_tracker_get returns after that frame (pose
+ * components relative to the frame's estimate, velocities as they are) -- their log-weights lw_i and the occlusion slot
+ * map idx_i.  With m = max lw, e_i = exp(lw_i - m), S = sum e_i (lw_i = -inf: e_i = 0, the particle contributes nothing; at
+ * least one lw_i is finite, as the filter's own weights require -- with all of them -inf the moments and ess are NaN):
+ *   mean[c]   = (sum e_i x_i[c]) / S
+ *   cov[a][b] = (sum e_i (x_i[a] - mean[a]) (x_i[b] - mean[b])) / S      two passes: the mean first, then central moments
+ *               (raw moments minus mean mean^T cancel on the velocities); the upper triangle is computed and mirrored,
+ *               so the matrix is symmetric bit for bit
+ *   ess       = S^2 / sum e_i^2
+ *   survivors = the number of distinct values among idx_i: distinct occlusion planes alive, i.e. distinct parents of the
+ *               last block's resampling; n when that block did not resample
+ *   resampled = the last block's resampling decision;  n;  frame = frames tracked since rbs_tracker_initialize (1, 2, ...)
+ * Every sum is taken in binary64 in a fixed order that depends on n only (no floating-point atomics): two runs give the
+ * same bits, and so do frame by frame and look-ahead.  Below 8 192 particles one block reduces, from there on a grid with
+ * per-block partials folded in block order; the two forms may differ from each other in the last bits.
+ * Convention.  Components per body: position (3), rotation vector (3), linear velocity (3), angular velocity (3), bodies in
+ * order.  Pose rows and columns need no conversion for the MODEL frame: translation deltas add in the camera frame, rotation
+ * deltas multiply from the left, R = R(delta) R(default) -- a left perturbation in camera axes.  (The host mirrors convert
+ * to the published pose of a centred mesh.)
+ *
+ * rbs_tracker_set_posterior: enable != 0 switches the report on (allocating its buffers the first time), 0 off.  Off --
+ * the default -- a frame enqueues exactly what it did before the report existed.  Frames in flight:
+ * RBS_ERR_INVALID_ARGUMENT; a tracker over several devices: RBS_ERR_UNSUPPORTED.  The filter itself is not touched: estimates
+ * and particles are bit for bit those of a tracker with the report off.
+ * rbs_tracker_posterior: the report of the frame most recently handed out by rbs_tracker_result / rbs_tracker_track*
+ * (with look-ahead: of frame k after result(k), while k + 1 is in flight).  mean [D], cov [D][D] row-major; info, mean, cov
+ * may each be NULL.  RBS_ERR_INVALID_ARGUMENT while the report is off, before the first frame, and after
+ * rbs_tracker_initialize until the next result; a poisoned tracker's error otherwise. */
+typedef struct rbs_tracker_posterior_info {
+    int32_t n;            /* particles */
+    int32_t survivors;    /* distinct occlusion slots among the particles */
+    int32_t resampled;    /* 1: the frame's last sampling block resampled */
+    int32_t frame;        /* frames tracked since rbs_tracker_initialize */
+    double ess;           /* effective sample size, 1 .. n */
+} rbs_tracker_posterior_info;
+int32_t rbs_tracker_set_posterior(rbs_tracker* t, int32_t enable);
+int32_t rbs_tracker_posterior(rbs_tracker* t, rbs_tracker_posterior_info* info, double* mean, double* cov);
+/* Device time of that report's kernels, first launch to last (HIP events on the tracker's stream), in milliseconds.
+ * RBS_ERR_INVALID_ARGUMENT wherever rbs_tracker_posterior has no report. */
+int32_t rbs_tracker_posterior_ms(rbs_tracker* t, float* ms);
+
 /* ------------------------------------------------------------------------------------------
  * Robust Gaussian tracker (the reference's second tracker, R:source/dbot_ros/tracker/gaussian_tracker_node.cpp):
  * an unscented-transform Gaussian filter over the object state with pixels as conditionally independent

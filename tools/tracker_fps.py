@@ -3,7 +3,12 @@
 -- set_observation + transition + loglikes(update) + weights + KL + resample + mean -- on a
 30-frame synthetic sequence (object translating 2 mm and rotating 1 degree per frame), for
 {200, 2 000, 20 000} particles on one MI355X.  Two variants per count: filter='device' (rbs_tracker_*: transition, weights, KL,
-resampling, mean on the GPU, one host sync per frame) and filter='host' (numpy mirror).  Prints one JSON line per particle count."""
+resampling, mean on the GPU, one host sync per frame) and filter='host' (numpy mirror).  Prints one JSON line per particle count.
+
+    tracker_fps.py [COUNTS [MESHES]] --posterior [--repeats R]
+the device tracker's posterior report (rbs_tracker_set_posterior) off and on, alternating in ONE process after a warm-up, frame
+by frame and with look-ahead (two frames in flight): frames/s of each (median and range over the repeats -- the range is the
+run-to-run spread a difference has to exceed) and the report's kernels' device time from events.  One JSON line per count."""
 import json
 import os
 import sys
@@ -19,7 +24,82 @@ from dbot_ros_amd.tracker import (DeviceParticleTracker, ObjectTransitionBuilder
                                   ParticleTrackerBuilder)
 
 
+def posterior_main(argv):
+    """--posterior: see the module's docstring."""
+    repeats = 5
+    if "--repeats" in argv:
+        k = argv.index("--repeats")
+        repeats = int(argv[k + 1])
+        del argv[k:k + 2]
+    counts = [int(x) for x in argv[0].split(",")] if len(argv) > 0 else [200, 2000, 20000]
+    names = argv[1].split(",") if len(argv) > 1 else ["m1"]
+    cols, rows, n_frames = 640, 480, 30
+    fns = {"m1": synth.mesh_m1, "m2": synth.mesh_m2, "m3": synth.mesh_m3, "m4": synth.mesh_m4}
+    meshes = [fns[k]() for k in names]
+    nb = len(meshes)
+    om = ObjectModel([v for v, _ in meshes], [t for _, t in meshes], center=True)
+    cam = CameraData(synth.camera_matrix(cols, rows), rows, cols)
+    init = np.zeros(12 * nb)
+    for b in range(nb):
+        Rt = synth.truth_pose(nb, frame=0)[b]
+        init[12 * b + 3:12 * b + 6] = pose.matrix_to_rotvec(Rt[:9].reshape(3, 3))
+        init[12 * b:12 * b + 3] = Rt[9:] - Rt[:9].reshape(3, 3) @ om.centers[b]
+    for n in counts:
+        P = RbSensorBuilder.Parameters(sample_count=n)
+        with RbSensor(om, cam, P, max_particles=max(1, n // nb)) as s:
+            rng = np.random.default_rng(0)
+            frames = [synth.make_frame(s.render_depth(synth.truth_pose(nb, frame=k)), rows, cols, rng, occluder=False)
+                      for k in range(n_frames + 1)]
+            trans = ObjectTransitionBuilder(ObjectTransitionBuilder.Parameters(part_count=nb)).build()
+            tr = DeviceParticleTracker(trans, s, om, ParticleTrackerBuilder.Parameters(evaluation_count=n), device_rng=True, seed=1)
+
+            def block(on, look_ahead, collect_ms=None):
+                """The 30 frames from a fresh initialize -> frames/s (the same sequence every time: device RNG, same seed)."""
+                tr.initialize([init])
+                tr.set_posterior(on)
+                tr.track(frames[0])
+                t0 = time.perf_counter()
+                if look_ahead:
+                    tr.submit(frames[1])
+                    for k in range(2, n_frames + 1):
+                        tr.submit(frames[k])
+                        tr.result()
+                    tr.result()
+                else:
+                    for k in range(1, n_frames + 1):
+                        tr.track(frames[k])
+                        if collect_ms is not None:
+                            collect_ms.append(tr.posterior_ms())
+                dt = time.perf_counter() - t0
+                if on:
+                    assert tr.posterior().frame == n_frames + 1
+                return n_frames / dt
+
+            for on in (False, True):      # warm-up: every kernel of both settings has run
+                block(on, False), block(on, True)
+            ms = []
+            block(True, False, collect_ms=ms)                 # (a pass of its own: the query is not inside the timed loops)
+            fps = {(on, la): [] for on in (False, True) for la in (False, True)}
+            for _ in range(repeats):
+                for la in (False, True):
+                    for on in (False, True):                  # alternating
+                        fps[(on, la)].append(block(on, la))
+            out = {"metric": "tracker FPS, posterior report off / on", "evaluation_count": n, "objects": nb, "particles": max(1, n // nb),
+                   "repeats": repeats, "unit": "frames/s", "resolution": [cols, rows],
+                   "posterior_kernels_device_ms": {"median": float(np.median(ms)), "min": float(np.min(ms)), "max": float(np.max(ms))}}
+            for (on, la), v in fps.items():
+                out[("on" if on else "off") + ("_look_ahead" if la else "_frame_by_frame")] = {
+                    "median": float(np.median(v)), "min": float(np.min(v)), "max": float(np.max(v))}
+            for la, name in ((False, "frame_by_frame"), (True, "look_ahead")):
+                out["on_over_off_" + name] = float(np.median(fps[(True, la)]) / np.median(fps[(False, la)]))
+            tr.close()
+            print(json.dumps(out), flush=True)
+
+
 def main():
+    if "--posterior" in sys.argv:
+        argv = [a for a in sys.argv[1:] if a != "--posterior"]
+        return posterior_main(argv)
     counts = [int(x) for x in sys.argv[1].split(",")] if len(sys.argv) > 1 else [200, 2000, 20000]
     names = sys.argv[2].split(",") if len(sys.argv) > 2 else ["m1"]     # e.g. m1,m2,m3 = BASELINE config C2
     cols, rows, n_frames = 640, 480, 30
