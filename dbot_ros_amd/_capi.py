@@ -57,6 +57,8 @@ EXPORTS = (
     "rbs_find_scene_body_finder", "rbs_find_scene_get_polish", "rbs_find_scene_stage_ms", "rbs_find_scene_last_error",
     "rbs_assess_default_params", "rbs_assess_poses", "rbs_assess_verdict", "rbs_assess_get_plane", "rbs_assess_kernel_ms",
     "rbs_contour_default_params", "rbs_contour_poses", "rbs_contour_verdict", "rbs_contour_kernel_ms",
+    "rbs_occlusion_mean", "rbs_occlusion_mean_ms", "rbs_occlusion_bodies",
+    "rbs_tracker_set_occlusion_map", "rbs_tracker_occlusion_map", "rbs_tracker_occlusion_map_ms",
 )
 RBS_ASSESS_OUT_OF_VIEW, RBS_ASSESS_OCCLUDED, RBS_ASSESS_SUPPORTED, RBS_ASSESS_LOST = range(4)
 RBS_CONTOUR_NO_RIM, RBS_CONTOUR_UNDECIDED, RBS_CONTOUR_PRESENT, RBS_CONTOUR_ABSENT = range(4)
@@ -212,6 +214,15 @@ class RbsContourBody(C.Structure):
         ("beyond", C.c_int32),
         ("verdict", C.c_int32),
         ("reserved", C.c_int32 * 2),
+    ]
+
+
+class RbsOcclusionBody(C.Structure):
+    _fields_ = [
+        ("rendered", C.c_int32),
+        ("occluded", C.c_int32),
+        ("sum_q32", C.c_int64),
+        ("reserved", C.c_int32 * 4),
     ]
 
 
@@ -499,5 +510,17 @@ def load():
     lib.rbs_contour_verdict.argtypes = [C.POINTER(RbsContourParams), C.POINTER(RbsContourBody), ip]
     lib.rbs_contour_kernel_ms.restype = C.c_int32
     lib.rbs_contour_kernel_ms.argtypes = [H, fp]
+    lib.rbs_occlusion_mean.restype = C.c_int32
+    lib.rbs_occlusion_mean.argtypes = [H, ip, dp, C.c_int32, fp]
+    lib.rbs_occlusion_mean_ms.restype = C.c_int32
+    lib.rbs_occlusion_mean_ms.argtypes = [H, fp]
+    lib.rbs_occlusion_bodies.restype = C.c_int32
+    lib.rbs_occlusion_bodies.argtypes = [H, fp, dp, C.c_int32, C.c_double, C.POINTER(RbsOcclusionBody)]
+    lib.rbs_tracker_set_occlusion_map.restype = C.c_int32
+    lib.rbs_tracker_set_occlusion_map.argtypes = [H, C.c_int32]
+    lib.rbs_tracker_occlusion_map.restype = C.c_int32
+    lib.rbs_tracker_occlusion_map.argtypes = [H, ip, fp]
+    lib.rbs_tracker_occlusion_map_ms.restype = C.c_int32
+    lib.rbs_tracker_occlusion_map_ms.argtypes = [H, fp]
     _lib = lib
     return lib

@@ -240,6 +240,9 @@ struct rbs_handle {
                                 // (it is only ever called with update = 0 and every index 0)
     // ---- the pose assessor (rbsensor_assess.hip): its planes, records and staging, allocated by the first rbs_assess_poses
     struct rbs_assess_state* assess = nullptr;
+    // ---- the occlusion map (rbsensor_occmap.hip): its buffers, allocated by the first rbs_occlusion_mean / rbs_occlusion_bodies /
+    // rbs_tracker_set_occlusion_map
+    struct rbs_occmap_state* occmap = nullptr;
 };
 
 // RCCL, bound at run time (dlopen): a single-device handle never needs it, and a process that

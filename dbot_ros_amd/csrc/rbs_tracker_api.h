@@ -44,6 +44,17 @@ struct rbs_tracker {
     float post_ms = 0.f;
     std::vector<double> post;
     int32_t post_i[4] = {0, 0, 0, 0};
+    // the occlusion map (rbs_tracker_set_occlusion_map, rbsensor_occmap.hip): off by default.  Per in-flight frame a pinned
+    // image the frame's last kernel writes and the event recorded behind it; rbs_tracker_result copies it into `map`.
+    bool map_on = false, map_valid = false, map_ready = false;   // map_ready: every buffer and event below exists
+    float* h_map[2] = {nullptr, nullptr};
+    float* h_map_dev[2] = {nullptr, nullptr};
+    hipEvent_t ev_map[2] = {nullptr, nullptr};
+    hipEvent_t ev_map0[2] = {nullptr, nullptr};   // in front of the map's first launch: its device time (rbs_tracker_occlusion_map_ms)
+    int map_seq[2] = {0, 0};                      // the frame number of the map in image k
+    float map_ms = 0.f;
+    int32_t map_frame = 0;
+    std::vector<float> map;
 };
 
 namespace {
@@ -265,6 +276,9 @@ void rbs_tracker_destroy(rbs_tracker* t)
         if (t->h_post[k]) (void)hipHostFree(t->h_post[k]);
         if (t->ev_post[k]) (void)hipEventDestroy(t->ev_post[k]);
         if (t->ev_post0[k]) (void)hipEventDestroy(t->ev_post0[k]);
+        if (t->h_map[k]) (void)hipHostFree(t->h_map[k]);
+        if (t->ev_map[k]) (void)hipEventDestroy(t->ev_map[k]);
+        if (t->ev_map0[k]) (void)hipEventDestroy(t->ev_map0[k]);
     }
     delete t;
 }
@@ -277,6 +291,7 @@ int32_t rbs_tracker_initialize(rbs_tracker* t, const double* default_state)
     t->recentre_pending = false;
     t->poisoned = false;
     t->post_valid = false;
+    t->map_valid = false;
     if (!t->reps.empty()) {
         for (rbs_tracker* r : t->reps)
             if (int32_t rc = rbs_tracker_initialize(r, default_state)) { t->s->err = r->s->err; return rc; }
@@ -543,6 +558,14 @@ static int32_t tracker_submit_impl(rbs_tracker* t, const float* frame, const dou
         RBT_HIP(t, hipGetLastError());
         RBT_HIP(t, hipEventRecord(t->ev_post[slot], s));
     }
+    if (t->map_on) {
+        // the occlusion map of the population this frame leaves behind (T.logw, T.idx: what rbs_tracker_get returns) over the
+        // planes the frame's last updating call wrote, behind everything else of the frame and with an event of its own
+        RBT_HIP(t, hipEventRecord(t->ev_map0[slot], s));
+        if (int32_t rc = occmap::enqueue(h, T.idx, T.logw, T.n, t->h_map_dev[slot])) { t->err = h->err; return rc; }
+        RBT_HIP(t, hipEventRecord(t->ev_map[slot], s));
+        t->map_seq[slot] = (int)(T.frame + 1);
+    }
     std::swap(T.part_old, T.part_new);   // this frame's particles are the next frame's old ones
     // (the estimate and the flags were stored into h_state[slot] / h_flags[slot] by the kernel that
     // finished them: no copies behind the last kernel)
@@ -610,6 +633,13 @@ int32_t rbs_tracker_result(rbs_tracker* t, double* out_state, int32_t* out_resam
             std::memcpy(t->post_i, t->h_post[slot] + nd, sizeof(t->post_i));
             if (hipEventElapsedTime(&t->post_ms, t->ev_post0[slot], t->ev_post[slot]) != hipSuccess) { (void)hipGetLastError(); t->post_ms = 0.f; }
             t->post_valid = true;
+        }
+        if (t->map_on) {   // likewise the map, finished last
+            RBT_HIP(t, hipEventSynchronize(t->ev_map[slot]));
+            std::memcpy(t->map.data(), t->h_map[slot], sizeof(float) * t->map.size());
+            t->map_frame = t->map_seq[slot];
+            if (hipEventElapsedTime(&t->map_ms, t->ev_map0[slot], t->ev_map[slot]) != hipSuccess) { (void)hipGetLastError(); t->map_ms = 0.f; }
+            t->map_valid = true;
         }
     }
     std::memcpy(out_state, r->h_state[slot], sizeof(double) * D);
@@ -749,6 +779,56 @@ int32_t rbs_tracker_posterior_ms(rbs_tracker* t, float* ms)
     if (!ms) return tfail(t, RBS_ERR_INVALID_ARGUMENT, "tracker_posterior_ms: null output");
     if (!t->post_on || !t->post_valid) return tfail(t, RBS_ERR_INVALID_ARGUMENT, "tracker_posterior_ms: no report has been handed out");
     *ms = t->post_ms;
+    return RBS_OK;
+}
+
+int32_t rbs_tracker_set_occlusion_map(rbs_tracker* t, int32_t enable)
+{
+    if (!t) return RBS_ERR_INVALID_ARGUMENT;
+    if (!t->reps.empty() || !t->s->shards.empty())
+        return tfail(t, RBS_ERR_UNSUPPORTED, "tracker_set_occlusion_map: single-device trackers only");
+    if (t->submitted != t->collected)
+        return tfail(t, RBS_ERR_INVALID_ARGUMENT, "tracker_set_occlusion_map: frames are in flight (call rbs_tracker_result)");
+    if (enable && !t->map_ready) {
+        // every buffer is made once, each only where an earlier attempt that failed half-way has not left it; the map is
+        // switched on only when all of them exist
+        rbs_handle* h = t->s;
+        if (h->group || h->peer_world > 1) return tfail(t, RBS_ERR_UNSUPPORTED, "tracker_set_occlusion_map: single-device trackers only");
+        RBT_HIP(t, hipSetDevice(h->device));
+        if (int32_t rc = occmap::ensure(h, t->T.n)) { t->err = h->err; return rc; }
+        t->map.assign((size_t)h->npx, 0.f);
+        for (int k = 0; k < 2; ++k) {
+            if (!t->h_map[k]) RBT_HIP(t, hipHostMalloc(&t->h_map[k], sizeof(float) * (size_t)h->npx, hipHostMallocDefault));
+            if (!t->h_map_dev[k]) RBT_HIP(t, hipHostGetDevicePointer(reinterpret_cast<void**>(&t->h_map_dev[k]), t->h_map[k], 0));
+            if (!t->ev_map[k]) RBT_HIP(t, hipEventCreate(&t->ev_map[k]));
+            if (!t->ev_map0[k]) RBT_HIP(t, hipEventCreate(&t->ev_map0[k]));
+        }
+        t->map_ready = true;
+    }
+    t->map_on = enable != 0;
+    t->map_valid = false;
+    return RBS_OK;
+}
+
+int32_t rbs_tracker_occlusion_map(rbs_tracker* t, int32_t* frame, float* out)
+{
+    if (!t) return RBS_ERR_INVALID_ARGUMENT;
+    if (t->poisoned || t->s->poisoned)
+        return tfail(t, RBS_ERR_HIP, "tracker_occlusion_map: an earlier frame failed half-way (" + (t->s->poisoned ? t->s->poison_msg : t->err) +
+                                         "): call rbs_tracker_initialize");
+    if (!t->map_on) return tfail(t, RBS_ERR_INVALID_ARGUMENT, "tracker_occlusion_map: the map is off (rbs_tracker_set_occlusion_map)");
+    if (!t->map_valid) return tfail(t, RBS_ERR_INVALID_ARGUMENT, "tracker_occlusion_map: no frame has been handed out since rbs_tracker_initialize");
+    if (frame) *frame = t->map_frame;
+    if (out) std::memcpy(out, t->map.data(), sizeof(float) * t->map.size());
+    return RBS_OK;
+}
+
+int32_t rbs_tracker_occlusion_map_ms(rbs_tracker* t, float* ms)
+{
+    if (!t) return RBS_ERR_INVALID_ARGUMENT;
+    if (!ms) return tfail(t, RBS_ERR_INVALID_ARGUMENT, "tracker_occlusion_map_ms: null output");
+    if (!t->map_on || !t->map_valid) return tfail(t, RBS_ERR_INVALID_ARGUMENT, "tracker_occlusion_map_ms: no map has been handed out");
+    *ms = t->map_ms;
     return RBS_OK;
 }
 

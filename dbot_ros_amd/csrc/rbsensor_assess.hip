@@ -58,6 +58,33 @@ struct AssessArgs {
     int* rec;                 // [n x B][kAssessFields], zeroed: rendered, valid, support, in_front, behind
 };
 
+// The union of a pose's B body rectangles (x1 <= x0: none of them holds a pixel).
+__device__ inline int4 assess_union_rect(const int4* s_rect, int B, int cols, int npx)
+{
+    int x0 = cols, y0 = npx, x1 = 0, y1 = 0;
+    for (int b = 0; b < B; ++b) {
+        const int4 r = s_rect[b];
+        if (r.z <= r.x) continue;
+        x0 = min(x0, r.x); y0 = min(y0, r.y); x1 = max(x1, r.z); y1 = max(y1, r.w);
+    }
+    return make_int4(x0, y0, x1, y1);
+}
+// The owner rule: the body whose plane is nearest at pixel (x, y) = i among those whose rectangle holds it, a tie with the
+// lowest body; -1 where no plane has a surface.  planes: the pose's B planes; best: the owner's depth.
+// (rbs_occmap_bodies_kernel, rbsensor_occmap.hip, decides owners with it too.)
+__device__ inline int assess_owner(const float* __restrict__ planes, const int4* s_rect, int B, int npx, int x, int y, int i, float& best)
+{
+    best = INFINITY;
+    int owner = -1;
+    for (int b = 0; b < B; ++b) {       // ascending: a tie stays with the lowest body
+        const int4 r = s_rect[b];
+        if (x < r.x || x >= r.z || y < r.y || y >= r.w) continue;
+        const float d = planes[(size_t)b * npx + i];
+        if (d < best) { best = d; owner = b; }
+    }
+    return owner;
+}
+
 // Owner and class of every pixel of pose blockIdx.y's rectangle (the union of its bodies').
 __global__ __launch_bounds__(256) void rbs_assess_count_kernel(const AssessArgs A)
 {
@@ -67,26 +94,16 @@ __global__ __launch_bounds__(256) void rbs_assess_count_kernel(const AssessArgs 
     for (int e = tid; e < B * 5; e += 256) s_cnt[e] = 0;
     if (tid < B) s_rect[tid] = A.rects[k * B + tid];
     __syncthreads();
-    int x0 = A.cols, y0 = A.npx, x1 = 0, y1 = 0;
-    for (int b = 0; b < B; ++b) {
-        const int4 r = s_rect[b];
-        if (r.z <= r.x) continue;
-        x0 = min(x0, r.x); y0 = min(y0, r.y); x1 = max(x1, r.z); y1 = max(y1, r.w);
-    }
+    const int4 u = assess_union_rect(s_rect, B, A.cols, A.npx);
+    const int x0 = u.x, y0 = u.y, x1 = u.z, y1 = u.w;
     if (x1 > x0) {
         const int w = x1 - x0, total = w * (y1 - y0);
         const float* planes = A.planes + (size_t)k * B * A.npx;
         for (int p = blockIdx.x * 256 + tid; p < total; p += gridDim.x * 256) {
             const int ly = p / w, x = x0 + (p - ly * w), y = y0 + ly;
             const int i = y * A.cols + x;
-            float best = INFINITY;
-            int owner = -1;
-            for (int b = 0; b < B; ++b) {       // ascending: a tie stays with the lowest body
-                const int4 r = s_rect[b];
-                if (x < r.x || x >= r.z || y < r.y || y >= r.w) continue;
-                const float d = planes[(size_t)b * A.npx + i];
-                if (d < best) { best = d; owner = b; }
-            }
+            float best;
+            const int owner = assess_owner(planes, s_rect, B, A.npx, x, y, i, best);
             if (owner < 0) continue;
             const float yv = A.frame[i];
             int* c = s_cnt + owner * 5;

@@ -58,6 +58,8 @@
 #include "rbsensor_assess.hip"
 // The contour rule beside it (rbs_contour_*): one more kernel on the assessor's planes.
 #include "rbsensor_contour.hip"
+// The occlusion map (rbs_occlusion_*): the population's mean plane read from the planes as stored, and its per-body summary.
+#include "rbsensor_occmap.hip"
 
 namespace {
 
@@ -133,6 +135,7 @@ void release(rbs_handle* h)
     (void)hipFree(h->d_vtx);
     (void)hipFree(h->d_render);
     assess_release(h);
+    occmap_release(h);
     if (h->up_stream) (void)hipStreamSynchronize(h->up_stream);
     for (int k = 0; k < 2; ++k) {
         if (h->h_frames[k]) (void)hipHostFree(h->h_frames[k]);

@@ -384,6 +384,41 @@ class RbSensor:
         self._check(self._lib.rbs_get_window(self._h, int(slot), w))
         return tuple(int(x) for x in w)
 
+    def occlusion_mean(self, slots, log_weights=None):
+        """The occlusion map of a population (rbs_occlusion_mean; include/rbsensor_mi355x.h, "Occlusion map"): the weighted
+        mean of the planes of `slots` [n] (repeats allowed) under softmax(log_weights) [n] (None: uniform), float32
+        [rows*cols], reduced on the device from the planes as stored -- no slot is made dense, nothing of the sensor changes."""
+        idx = np.ascontiguousarray(slots, dtype=np.int32).ravel()
+        lw = None if log_weights is None else np.ascontiguousarray(log_weights, dtype=np.float64).ravel()
+        if lw is not None and lw.size != idx.size:
+            raise RbSensorError(_capi.RBS_ERR_INVALID_ARGUMENT, "log_weights must have one entry per slot")
+        out = np.empty(self.rows * self.cols, dtype=np.float32)
+        self._check(self._lib.rbs_occlusion_mean(
+            self._h, idx.ctypes.data_as(C.POINTER(C.c_int32)), None if lw is None else lw.ctypes.data_as(C.POINTER(C.c_double)),
+            int(idx.size), out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def occlusion_mean_ms(self):
+        """Device time of the last occlusion_mean's kernels in milliseconds (rbs_occlusion_mean_ms)."""
+        ms = C.c_float()
+        self._check(self._lib.rbs_occlusion_mean_ms(self._h, C.byref(ms)))
+        return float(ms.value)
+
+    def occlusion_bodies(self, map, poses, threshold=0.5):
+        """A map summarised per body at `poses` [n, n_bodies, 12] (rbs_occlusion_bodies): int64 [n, n_bodies, 3] of
+        (rendered, occluded, sum_q32) over the pixels each body owns under the assessor's owner rule --
+        occluded counts map > threshold, sum_q32 / 2**32 / rendered is the body's mean occlusion."""
+        m = np.ascontiguousarray(map, dtype=np.float32).ravel()
+        if m.size != self.rows * self.cols:
+            raise RbSensorError(_capi.RBS_ERR_INVALID_ARGUMENT, "map has the wrong size")
+        p = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, self.n_bodies * 12)
+        n = p.shape[0]
+        rec = (_capi.RbsOcclusionBody * (max(n, 1) * self.n_bodies))()
+        self._check(self._lib.rbs_occlusion_bodies(self._h, m.ctypes.data_as(C.POINTER(C.c_float)), p.ctypes.data_as(C.POINTER(C.c_double)),
+                                                   n, float(threshold), rec))
+        out = np.array([[r.rendered, r.occluded, r.sum_q32] for r in rec[:n * self.n_bodies]], dtype=np.int64)
+        return out.reshape(n, self.n_bodies, 3)
+
     def shared_trail_state(self):
         """(active, rebases): has the handle switched to a shared background plane, how often has it re-based (rbsensor_mi355x.h)."""
         a, r = C.c_int32(0), C.c_int32(0)

@@ -56,6 +56,46 @@ def posterior_of(particles, log_weights, indices, resampled=False, frame=0):
                      resampled=bool(resampled), n=int(x.shape[0]), frame=int(frame))
 
 
+@dataclass
+class OcclusionMap:
+    """What a particle tracker believes is occluded after a frame (include/rbsensor_mi355x.h, "Occlusion map"): plane
+    [rows, cols] float32, the weighted mean of the particles' occlusion planes; frame: frames tracked since initialize."""
+    plane: np.ndarray
+    frame: int = 0
+
+
+@dataclass
+class BodyOcclusion:
+    """One body's share of an occlusion map at a pose: pixels the body owns, those of them above the threshold, and the
+    mean of the map over them (nan when the body owns no pixel)."""
+    rendered: int
+    occluded: int
+    mean: float
+
+
+def occlusion_map_of(planes_by_slot, log_weights, indices):
+    """The rule of the occlusion map in numpy -- the restatement the device kernels (csrc/rbsensor_occmap.hip) are tested
+    against, in np.longdouble (binary64 where the platform has nothing wider).  planes_by_slot: {slot: plane} or an array
+    [slots, npx] of the planes rbs_get_occlusion hands out; log_weights [n] (None: uniform; -inf: no contribution);
+    indices [n].  Returns M [npx] as longdouble, not rounded to float."""
+    idx = np.asarray(indices).astype(np.int64).ravel()
+    LD = np.longdouble
+    if log_weights is None:
+        e = np.ones(idx.size, dtype=LD)
+    else:
+        lw = np.asarray(log_weights, dtype=np.float64).ravel()
+        e = np.exp((lw - lw.max()).astype(LD))
+    S = e.sum()
+    acc = None
+    for s in np.unique(idx):
+        W = e[idx == s].sum()
+        if not W > 0:
+            continue
+        term = W * np.asarray(planes_by_slot[int(s)], dtype=np.float32).ravel().astype(LD)
+        acc = term if acc is None else acc + term
+    return acc / S
+
+
 def object_frame_jacobian(R, c):
     """d(published pose) / d(model pose), 6 x 6, to first order.  With center_object_frame the published position is
     p = t - R c (R: the body's absolute rotation, c: its centring offset); a model perturbation (dt, dtheta) -- dtheta
@@ -267,6 +307,25 @@ class ParticleTracker:
             out[b] = C
         return out
 
+    # -- what the filter believes is occluded ---------------------------------------------------
+    def occlusion_map(self):
+        """OcclusionMap of the population the last frame left behind: sensor.occlusion_mean with this tracker's own
+        weights and slot map."""
+        if self._frames == 0:
+            raise ValueError("occlusion_map: no frame has been tracked since initialize")
+        plane = self.sensor.occlusion_mean(self.indices, self.log_weights)
+        return OcclusionMap(plane=plane.reshape(self.sensor.rows, self.sensor.cols), frame=self._frames)
+
+    def occlusion_of_estimate(self, threshold=0.5):
+        """Per body a BodyOcclusion: the last frame's occlusion map summarised over the pixels each body owns at the
+        published estimate (sensor.occlusion_bodies; center_object_frame undone as assess() undoes it)."""
+        from .assess import state_poses
+        if self.moving_average is None:
+            raise ValueError("occlusion_of_estimate: no frame tracked yet")
+        rec = self.sensor.occlusion_bodies(self.occlusion_map().plane, state_poses(self, self.moving_average), threshold)[0]
+        return [BodyOcclusion(rendered=int(r), occluded=int(o), mean=float(q) / 2.0 ** 32 / int(r) if r else float("nan"))
+                for r, o, q in rec]
+
     # -- the last estimate judged against its frame (dbot_ros_amd/assess.py) -------------------
     _in_flight = 0   # frames submitted and not yet collected (the device trackers' submit / result)
 
@@ -302,7 +361,8 @@ class DeviceParticleTracker(ParticleTracker):
     device_rng=True the normals/uniforms are drawn on the device (Philox), otherwise they come
     from this object's numpy Generator exactly as in the host tracker."""
 
-    def __init__(self, transition, sensor, object_model, params, rng=None, device_rng=False, seed=0, posterior=False):
+    def __init__(self, transition, sensor, object_model, params, rng=None, device_rng=False, seed=0, posterior=False,
+                 occlusion_map=False):
         import ctypes as C
         from . import _capi
         super().__init__(transition, sensor, object_model, params, rng)
@@ -322,6 +382,8 @@ class DeviceParticleTracker(ParticleTracker):
         sensor._register_dependent(self)   # the C tracker borrows the sensor handle
         if posterior:
             self.set_posterior(True)
+        if occlusion_map:
+            self.set_occlusion_map(True)
 
     def set_posterior(self, enable):
         """Switch the device's posterior report on or off (rbs_tracker_set_posterior; refused with frames in flight)."""
@@ -343,6 +405,25 @@ class DeviceParticleTracker(ParticleTracker):
         """Device time of the last report's kernels in milliseconds (rbs_tracker_posterior_ms)."""
         ms = self._C.c_float()
         self.sensor._check(self._lib.rbs_tracker_posterior_ms(self._t, self._C.byref(ms)))
+        return float(ms.value)
+
+    def set_occlusion_map(self, enable):
+        """Switch the device's occlusion map on or off (rbs_tracker_set_occlusion_map; refused with frames in flight)."""
+        self.sensor._check(self._lib.rbs_tracker_set_occlusion_map(self._t, 1 if enable else 0))
+
+    def occlusion_map(self):
+        """The map of the frame most recently handed out by track() / result() (rbs_tracker_occlusion_map), reduced on
+        the device; needs occlusion_map=True (or set_occlusion_map(True)) -- an RbSensorError otherwise."""
+        C = self._C
+        frame = C.c_int32()
+        plane = np.empty((self.sensor.rows, self.sensor.cols), dtype=np.float32)
+        self.sensor._check(self._lib.rbs_tracker_occlusion_map(self._t, C.byref(frame), plane.ctypes.data_as(C.POINTER(C.c_float))))
+        return OcclusionMap(plane=plane, frame=int(frame.value))
+
+    def occlusion_map_ms(self):
+        """Device time of the last map's kernels in milliseconds (rbs_tracker_occlusion_map_ms)."""
+        ms = self._C.c_float()
+        self.sensor._check(self._lib.rbs_tracker_occlusion_map_ms(self._t, self._C.byref(ms)))
         return float(ms.value)
 
     def close(self):

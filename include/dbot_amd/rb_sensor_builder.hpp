@@ -241,12 +241,14 @@ public:
         const int32_t rc = rbs_create(&cfg, &handle_);
         if (rc != RBS_OK)
             throw std::runtime_error(std::string("RbSensor: ") + rbs_last_error(nullptr));
+        pixels_ = static_cast<size_t>(cfg.rows) * static_cast<size_t>(cfg.cols);
     }
     ~RbSensor() { rbs_destroy(handle_); }
     RbSensor(const RbSensor&) = delete;
     RbSensor& operator=(const RbSensor&) = delete;
 
     void reset() { check(rbs_reset(handle_)); }
+    size_t pixels() const { return pixels_; }   ///< rows * cols of a frame
 
     /// borrow_observations(true): set_observation(image) does not copy -- `image` must stay alive and unchanged until the
     /// next loglikes() has returned, as it does inside dbot's tracker_->track(image) -- and that loglikes() converts and sends
@@ -273,6 +275,19 @@ public:
     void set_observation_device(const float* d_depth, void* stream = nullptr)
     {
         check(rbs_set_observation_device(handle_, d_depth, stream));
+    }
+
+    /// The occlusion map of a population (rbs_occlusion_mean): the weighted mean, rows*cols floats, of the occlusion planes of
+    /// `slots` (repeats allowed) under softmax(log_weights) -- empty: uniform weights --, reduced on the device from the planes
+    /// as they are stored; nothing of the sensor changes.
+    std::vector<float> occlusion_mean(const IntArray& slots, const RealArray& log_weights = RealArray())
+    {
+        if (!log_weights.empty() && log_weights.size() != slots.size())
+            throw std::runtime_error("RbSensor::occlusion_mean: log_weights.size() != slots.size()");
+        std::vector<float> out(pixels_);
+        check(rbs_occlusion_mean(handle_, slots.data(), log_weights.empty() ? nullptr : log_weights.data(), static_cast<int32_t>(slots.size()),
+                                 out.data()));
+        return out;
     }
 
     /// deltas: state deltas around integrated_poses(); indices: occlusion slot each particle
@@ -355,6 +370,7 @@ private:
     int n_bodies_;
     State integrated_poses_;
     size_t max_particles_ = 0;
+    size_t pixels_ = 0;
     bool borrow_ = false;
     std::vector<Real> poses_, deltas_, defaults_;
 };
@@ -434,6 +450,7 @@ public:
         return averaged(model, nres);
     }
     int resamplings() const { return resamplings_; }
+    RbSensor<State>& sensor() { return *sensor_; }   ///< the sensor the tracker was built over (its occlusion_mean, its planes)
 
     /// The posterior report of the frame most recently handed out by track() / result() (rbs_tracker_posterior): weighted
     /// mean [D] and covariance [D][D] (row-major) of the re-centred particle deltas, D = 12 per body -- position, rotation
@@ -464,6 +481,25 @@ public:
         p.frame = info.frame;
         return p;
     }
+    /// The occlusion map of the frame most recently handed out by track() / result() (rbs_tracker_occlusion_map): what the
+    /// filter believes is occluded, the weighted mean of the particles' occlusion planes, rows*cols floats, and the number
+    /// of frames tracked since initialize().
+    struct OcclusionMap {
+        std::vector<float> plane;
+        int frame = 0;
+    };
+    /// Switch the map on or off (off by default; refused while frames are in flight).
+    void enable_occlusion_map(bool on = true) { check(rbs_tracker_set_occlusion_map(t_, on ? 1 : 0)); }
+    OcclusionMap occlusion_map() const
+    {
+        OcclusionMap m;
+        m.plane.resize(sensor_->pixels());
+        int32_t frame = 0;
+        check(rbs_tracker_occlusion_map(t_, &frame, m.plane.data()));
+        m.frame = frame;
+        return m;
+    }
+
     /// Per body the 6 x 6 covariance (row-major, [parts][36]) of the PUBLISHED pose -- position, rotation; camera frame,
     /// left perturbation.  With center_object_frame the published position is t - R c, to first order
     /// dp = dt + [R c]x dtheta: J C J^T with J = [[I, [R c]x], [0, I]], R the body's rotation in the last estimate and c

@@ -1129,6 +1129,75 @@ int32_t rbs_contour_verdict(const rbs_contour_params* params, const rbs_contour_
  * handle's last assessment was not an rbs_contour_poses: RBS_ERR_INVALID_ARGUMENT. */
 int32_t rbs_contour_kernel_ms(rbs_handle* h, float* out3);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Occlusion map (csrc/rbsensor_occmap.hip): what a particle population believes is occluded -- the
+ * weighted mean of the occlusion planes its members point at, reduced on the device from the planes as they are stored.
+ * It is the quantity the assessor's blind spot (above, "The blind spot") asks for: a single frame cannot tell an occluder
+ * from the object, the filter's belief, integrated over the frames, can.
+ *
+ * The rule.  Population: n members; member i has an occlusion slot idx_i and a log-weight lw_i.  At least one lw_i is
+ * finite; lw_i = -inf contributes nothing.  With m = max lw:
+ *   e_i = exp(lw_i - m)   (the device library's exp, as in the posterior report),    S = sum e_i,
+ *   W_s = sum over { i : idx_i = s } of e_i.
+ * Value of a slot at a pixel: v_s(p) is exactly the float rbs_get_occlusion(h, s, .) hands out at p, in every layout --
+ *   inside the slot's window the stored float (slabs: addressed through the stored region); occlusion_mode REFERENCE: the
+ *   effective value exact_prior(value, age) as of the slot's epoch, an age beyond age_max being the background;
+ *   outside the window the scalar background, or the shared trail's plane pixel while the trail is active (REFERENCE: its
+ *   effective value);  dense planes: the stored float.
+ * Map:  M(p) = (float)((sum over s of W_s (double)v_s(p)) / S) -- the sum in binary64, one rounding to float; no contraction
+ * into fused operations.  Every sum (W_s, S, the per-pixel sum) is taken in an order fixed by n, idx and the windows alone:
+ * W_s over ascending i; S per thread t of 1 024 over i = t, t + 1 024, ..., then a fixed tree; per pixel the slots with
+ * W_s > 0 in ascending s, cut into four contiguous parts that are summed one by one and folded in part order.  No
+ * floating-point atomics: two runs give the same bits, and so do a tracker frame by frame and with look-ahead.  Outside every
+ * live window M(p) is the background value bit for bit.
+ * Nothing of the sensor is touched: values, windows, regions, the shared plane, clocks, staged poses, rbs_render_depth's
+ * image and the observation stay as they were.  In particular no slot is made dense, as rbs_get_occlusion makes it on float
+ * windowed planes: the planes are read in place.
+ *
+ * rbs_occlusion_mean: host pointers, synchronous.  slots [n] in [0, max_particles), repeats allowed; log_weights [n], NULL =
+ * uniform weights; out [rows*cols].  RBS_ERR_INVALID_ARGUMENT: a null pointer, n < 1, a slot out of range, a log-weight that
+ * is NaN or +inf, every log-weight -inf.  A handle over several devices or attached to other ranks: RBS_ERR_UNSUPPORTED.  A
+ * poisoned handle: its own error.  The call's buffers are allocated at first use, grow only, and are freed by rbs_destroy. */
+int32_t rbs_occlusion_mean(rbs_handle* h, const int32_t* slots, const double* log_weights, int32_t n, float* out);
+/* Device time of the last rbs_occlusion_mean's kernels, first launch to last (HIP events), in milliseconds.
+ * RBS_ERR_INVALID_ARGUMENT before the first map. */
+int32_t rbs_occlusion_mean_ms(rbs_handle* h, float* ms);
+
+/* The device tracker's occlusion map (opt-in), on the pattern of the posterior report: with it on, every frame ends with the
+ * map of the population rbs_tracker_get returns after that frame (log_weights, indices), its kernels launched last in the
+ * frame's chain -- behind the posterior report's when that is on too; the two are independent -- into a pinned buffer per
+ * frame in flight.
+ * rbs_tracker_set_occlusion_map: enable != 0 switches the map on (allocating its buffers the first time), 0 off.  Off -- the
+ * default -- a frame enqueues exactly what it did before the map existed.  Frames in flight: RBS_ERR_INVALID_ARGUMENT; a
+ * tracker over several devices: RBS_ERR_UNSUPPORTED.  The filter is not touched: estimates and particles are bit for bit those
+ * of a tracker with the map off.
+ * rbs_tracker_occlusion_map: the map of the frame most recently handed out by rbs_tracker_result / rbs_tracker_track* (with
+ * look-ahead: of frame k after result(k), while k + 1 is in flight).  frame: frames tracked since rbs_tracker_initialize
+ * (1, 2, ...); out [rows*cols]; either may be NULL.  RBS_ERR_INVALID_ARGUMENT while the map is off, before the first frame,
+ * and after rbs_tracker_initialize until the next result; a poisoned tracker's error comes first.
+ * rbs_tracker_occlusion_map_ms: device time of that map's kernels; RBS_ERR_INVALID_ARGUMENT wherever there is no map. */
+int32_t rbs_tracker_set_occlusion_map(rbs_tracker* t, int32_t enable);
+int32_t rbs_tracker_occlusion_map(rbs_tracker* t, int32_t* frame, float* out);
+int32_t rbs_tracker_occlusion_map_ms(rbs_tracker* t, float* ms);
+
+/* A map summarised per body at given poses: which share of each body the map calls occluded.  poses [n][n_objects][12] as
+ * for rbs_assess_poses, n x n_objects <= 64; planes and the owner of a pixel are exactly the assessor's (Pose assessment
+ * above: the nearest of the bodies' own depth planes, a tie with the lowest body).  Per pixel p owned by body b:
+ *   rendered += 1;   occluded += ((double)M(p) > threshold);   sum_q32 += (uint64)((double)M(p) 2^32), truncated.
+ * Integer sums: order-free.  The mean occlusion of a body is sum_q32 / 2^32 / rendered.
+ * map [rows*cols] host floats, each finite and in [0, 1]; threshold in [0, 1]; out [n][n_objects].  Checked on the host
+ * before any launch: RBS_ERR_INVALID_ARGUMENT.  Single-device handles only (RBS_ERR_UNSUPPORTED).  The sensor's state is not
+ * touched; the assessor's last-call inspection state (rbs_assess_get_plane) is what an rbs_assess_poses at these poses
+ * leaves, except that rbs_assess_kernel_ms keeps the times of the assessor's own last call (zeros when there was none).  On a
+ * handle over several devices RBS_ERR_UNSUPPORTED comes before a poisoned handle's error, here and in rbs_occlusion_mean. */
+typedef struct rbs_occlusion_body {   /* 32 bytes */
+    int32_t rendered;       /* pixels the body owns */
+    int32_t occluded;       /* ... of them with M > threshold */
+    int64_t sum_q32;        /* sum over them of floor(M 2^32) */
+    int32_t reserved[4];    /* 0 */
+} rbs_occlusion_body;
+int32_t rbs_occlusion_bodies(rbs_handle* h, const float* map, const double* poses, int32_t n, double threshold, rbs_occlusion_body* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,11 @@ resampling, mean on the GPU, one host sync per frame) and filter='host' (numpy m
     tracker_fps.py [COUNTS [MESHES]] --posterior [--repeats R]
 the device tracker's posterior report (rbs_tracker_set_posterior) off and on, alternating in ONE process after a warm-up, frame
 by frame and with look-ahead (two frames in flight): frames/s of each (median and range over the repeats -- the range is the
-run-to-run spread a difference has to exceed) and the report's kernels' device time from events.  One JSON line per count."""
+run-to-run spread a difference has to exceed) and the report's kernels' device time from events.  One JSON line per count.
+
+    tracker_fps.py [COUNTS [MESHES]] --occlusion-map [--never-resample] [--repeats R]
+the same measurement for the device tracker's occlusion map (rbs_tracker_set_occlusion_map); MESHES m1,m2,m3 is the
+three-body scene; --never-resample sets max_kl_divergence so large that nothing resamples and every slot stays live."""
 import json
 import os
 import sys
@@ -24,9 +28,11 @@ from dbot_ros_amd.tracker import (DeviceParticleTracker, ObjectTransitionBuilder
                                   ParticleTrackerBuilder)
 
 
-def posterior_main(argv):
-    """--posterior: see the module's docstring."""
+def posterior_main(argv, product="posterior"):
+    """--posterior, --occlusion-map: see the module's docstring."""
     repeats = 5
+    never = product == "occlusion_map" and "--never-resample" in argv
+    argv = [a for a in argv if a != "--never-resample"]
     if "--repeats" in argv:
         k = argv.index("--repeats")
         repeats = int(argv[k + 1])
@@ -51,12 +57,17 @@ def posterior_main(argv):
             frames = [synth.make_frame(s.render_depth(synth.truth_pose(nb, frame=k)), rows, cols, rng, occluder=False)
                       for k in range(n_frames + 1)]
             trans = ObjectTransitionBuilder(ObjectTransitionBuilder.Parameters(part_count=nb)).build()
-            tr = DeviceParticleTracker(trans, s, om, ParticleTrackerBuilder.Parameters(evaluation_count=n), device_rng=True, seed=1)
+            tp = ParticleTrackerBuilder.Parameters(evaluation_count=n)
+            if never:
+                tp.max_kl_divergence = 1e30
+            tr = DeviceParticleTracker(trans, s, om, tp, device_rng=True, seed=1)
+            switch, ms_of, last = ((tr.set_posterior, tr.posterior_ms, tr.posterior) if product == "posterior" else
+                                   (tr.set_occlusion_map, tr.occlusion_map_ms, tr.occlusion_map))
 
             def block(on, look_ahead, collect_ms=None):
                 """The 30 frames from a fresh initialize -> frames/s (the same sequence every time: device RNG, same seed)."""
                 tr.initialize([init])
-                tr.set_posterior(on)
+                switch(on)
                 tr.track(frames[0])
                 t0 = time.perf_counter()
                 if look_ahead:
@@ -69,10 +80,10 @@ def posterior_main(argv):
                     for k in range(1, n_frames + 1):
                         tr.track(frames[k])
                         if collect_ms is not None:
-                            collect_ms.append(tr.posterior_ms())
+                            collect_ms.append(ms_of())
                 dt = time.perf_counter() - t0
                 if on:
-                    assert tr.posterior().frame == n_frames + 1
+                    assert last().frame == n_frames + 1
                 return n_frames / dt
 
             for on in (False, True):      # warm-up: every kernel of both settings has run
@@ -84,9 +95,12 @@ def posterior_main(argv):
                 for la in (False, True):
                     for on in (False, True):                  # alternating
                         fps[(on, la)].append(block(on, la))
-            out = {"metric": "tracker FPS, posterior report off / on", "evaluation_count": n, "objects": nb, "particles": max(1, n // nb),
+            what = "posterior report" if product == "posterior" else "occlusion map"
+            out = {"metric": "tracker FPS, %s off / on" % what, "evaluation_count": n, "objects": nb, "particles": max(1, n // nb),
                    "repeats": repeats, "unit": "frames/s", "resolution": [cols, rows],
-                   "posterior_kernels_device_ms": {"median": float(np.median(ms)), "min": float(np.min(ms)), "max": float(np.max(ms))}}
+                   product + "_kernels_device_ms": {"median": float(np.median(ms)), "min": float(np.min(ms)), "max": float(np.max(ms))}}
+            if product == "occlusion_map":
+                out["resamplings"] = tr.n_resamplings
             for (on, la), v in fps.items():
                 out[("on" if on else "off") + ("_look_ahead" if la else "_frame_by_frame")] = {
                     "median": float(np.median(v)), "min": float(np.min(v)), "max": float(np.max(v))}
@@ -100,6 +114,9 @@ def main():
     if "--posterior" in sys.argv:
         argv = [a for a in sys.argv[1:] if a != "--posterior"]
         return posterior_main(argv)
+    if "--occlusion-map" in sys.argv:
+        argv = [a for a in sys.argv[1:] if a != "--occlusion-map"]
+        return posterior_main(argv, product="occlusion_map")
     counts = [int(x) for x in sys.argv[1].split(",")] if len(sys.argv) > 1 else [200, 2000, 20000]
     names = sys.argv[2].split(",") if len(sys.argv) > 2 else ["m1"]     # e.g. m1,m2,m3 = BASELINE config C2
     cols, rows, n_frames = 640, 480, 30
