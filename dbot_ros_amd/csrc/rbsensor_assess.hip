@@ -1,14 +1,13 @@
 // rbsensor_assess.hip -- poses judged against one depth frame (rbs_assess_*, include/rbsensor_mi355x.h; the rule:
-// DESIGN.md Appendix J).  Included by rbsensor_capi.hip ahead of create_impl: it uses the handle, its observation and the
-// rasterizer of rbsensor_kernels.hip, and sensor creation and release call assess_configure / assess_release.
+// DESIGN.md Appendix J).  Included by rbsensor_capi.hip ahead of create_impl, behind rbs_pose_planes.h: it uses the handle,
+// its observation and the shared planes, and sensor release calls assess_release.
 //
 // Per call, on the sensor's stream:
-//   rbs_assess_render_kernel  one block row per (pose, body): the body's own screen rectangle cut into 64 x 64 tiles
-//                             dealt to the row's blocks; every tile goes through raster_window with the body's bit as
-//                             the body mask, culled as rbs_render_kernel's (the minimum over the bodies is bit-identical
-//                             to rbs_render_depth).  Plane (k, b) is valid inside rect (k, b) only.
-//   rbs_assess_count_kernel   a fixed grid per pose over the union of its bodies' rectangles: owner and class per pixel,
-//                             integer counts in LDS, one integer global add per block and counter.
+//   rbs_planes_render_kernel<true>  (rbs_pose_planes.h) one plane per (pose, body): body b alone in its own screen
+//                             rectangle, so the minimum over the bodies is bit-identical to rbs_render_depth.
+//   rbs_assess_count_kernel   a fixed grid per pose over the union of its bodies' rectangles: owner and class per pixel
+//                             (planes_owner, planes_class), integer counts in LDS, one integer global add per block and
+//                             counter.
 // Integer sums do not depend on their order: the same inputs give the same counts, run after run.  The verdict is
 // taken on the host from the counts (assess::verdict_of, also rbs_assess_verdict).
 // rbs_contour_poses (rbsensor_contour.hip) is the same call with one more kernel behind the count kernel, on the same
@@ -16,104 +15,43 @@
 namespace rbs {
 
 constexpr int kAssessMaxPlanes = 64;      // n x n_objects of one call
-constexpr int kAssessRenderSplit = 32;    // blocks per (pose, body) (tiles beyond it: strided)
 constexpr int kAssessCountBlocks = 32;    // blocks per pose of the count kernel
-constexpr int kAssessTileW = 64, kAssessTilePx = 4096;
 constexpr int kAssessFields = 8;          // int32 per record (rbs_assess_body)
 
-__global__ __launch_bounds__(kBlock) void rbs_assess_render_kernel(const DevParams P, float* __restrict__ planes, int4* __restrict__ rects)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const Smem m = carve(smem, P.tile_px, false);
-    const int kb = blockIdx.x;                // (pose, body)
-    const int k = kb / P.n_bodies, b = kb - k * P.n_bodies;
-    const double* pose = P.poses + (size_t)k * 12 * P.n_bodies;
-    const Rect r = bodies_rect(P, pose, b, b + 1);
-    if (blockIdx.y == 0 && threadIdx.x == 0) rects[kb] = make_int4(r.x0, r.y0, r.x1, r.y1);
-    if (r.x1 <= r.x0) return;
-    const TileGrid tg = tile_grid(r.x1 - r.x0, r.y1 - r.y0, P.tile_w, min(P.tile_w * P.tile_h, P.tile_px));
-    const int nx = (r.x1 - r.x0 + tg.tw - 1) / tg.tw, ny = (r.y1 - r.y0 + tg.th - 1) / tg.th;
-    float* out = planes + (size_t)kb * P.npx;
-    for (int t = blockIdx.y; t < nx * ny; t += gridDim.y) {
-        const int ty = t / nx;
-        const int wx0 = r.x0 + (t - ty * nx) * tg.tw, wy0 = r.y0 + ty * tg.th;
-        const int wx1 = min(r.x1, wx0 + tg.tw), wy1 = min(r.y1, wy0 + tg.th);
-        const int tw = wx1 - wx0, npx = tw * (wy1 - wy0);
-        raster_window(P, pose, wx0, wy0, wx1, wy1, true, m.tile, m.big, m.nbig,
-                      m.evalq + (threadIdx.x >> 6) * kQPlanes * kEvalQueue, 1u << b);
-        for (int p = threadIdx.x; p < npx; p += kBlock) {
-            const int lr = p / tw;
-            out[(size_t)(wy0 + lr) * P.cols + wx0 + (p - lr * tw)] = __uint_as_float(m.tile[p]);
-        }
-        __syncthreads();
-    }
-}
-
 struct AssessArgs {
-    const float* planes;      // [n x B][npx], plane (k, b) valid inside rects[k B + b]
-    const int4* rects;        // [n x B]
+    PlaneSet S;               // the n x B planes of the call
     const float* frame;
-    int cols, npx, B;
     double sigmas, ms, sf;    // tau = sigmas (ms + sf d d)
     int* rec;                 // [n x B][kAssessFields], zeroed: rendered, valid, support, in_front, behind
 };
-
-// The union of a pose's B body rectangles (x1 <= x0: none of them holds a pixel).
-__device__ inline int4 assess_union_rect(const int4* s_rect, int B, int cols, int npx)
-{
-    int x0 = cols, y0 = npx, x1 = 0, y1 = 0;
-    for (int b = 0; b < B; ++b) {
-        const int4 r = s_rect[b];
-        if (r.z <= r.x) continue;
-        x0 = min(x0, r.x); y0 = min(y0, r.y); x1 = max(x1, r.z); y1 = max(y1, r.w);
-    }
-    return make_int4(x0, y0, x1, y1);
-}
-// The owner rule: the body whose plane is nearest at pixel (x, y) = i among those whose rectangle holds it, a tie with the
-// lowest body; -1 where no plane has a surface.  planes: the pose's B planes; best: the owner's depth.
-// (rbs_occmap_bodies_kernel, rbsensor_occmap.hip, decides owners with it too.)
-__device__ inline int assess_owner(const float* __restrict__ planes, const int4* s_rect, int B, int npx, int x, int y, int i, float& best)
-{
-    best = INFINITY;
-    int owner = -1;
-    for (int b = 0; b < B; ++b) {       // ascending: a tie stays with the lowest body
-        const int4 r = s_rect[b];
-        if (x < r.x || x >= r.z || y < r.y || y >= r.w) continue;
-        const float d = planes[(size_t)b * npx + i];
-        if (d < best) { best = d; owner = b; }
-    }
-    return owner;
-}
 
 // Owner and class of every pixel of pose blockIdx.y's rectangle (the union of its bodies').
 __global__ __launch_bounds__(256) void rbs_assess_count_kernel(const AssessArgs A)
 {
     __shared__ int s_cnt[kMaxBodies * 5];
     __shared__ int4 s_rect[kMaxBodies];
-    const int tid = threadIdx.x, k = blockIdx.y, B = A.B;
+    const PlaneSet& S = A.S;
+    const int tid = threadIdx.x, k = blockIdx.y, B = S.B;
     for (int e = tid; e < B * 5; e += 256) s_cnt[e] = 0;
-    if (tid < B) s_rect[tid] = A.rects[k * B + tid];
+    if (tid < B) s_rect[tid] = S.rects[k * B + tid];
     __syncthreads();
-    const int4 u = assess_union_rect(s_rect, B, A.cols, A.npx);
+    const int4 u = planes_union_rect(S, s_rect, 0xffffffffu);
     const int x0 = u.x, y0 = u.y, x1 = u.z, y1 = u.w;
     if (x1 > x0) {
         const int w = x1 - x0, total = w * (y1 - y0);
-        const float* planes = A.planes + (size_t)k * B * A.npx;
+        const float* planes = S.planes + (size_t)k * B * S.npx;
         for (int p = blockIdx.x * 256 + tid; p < total; p += gridDim.x * 256) {
             const int ly = p / w, x = x0 + (p - ly * w), y = y0 + ly;
-            const int i = y * A.cols + x;
+            const int i = y * S.cols + x;
             float best;
-            const int owner = assess_owner(planes, s_rect, B, A.npx, x, y, i, best);
+            const int owner = planes_owner(S, planes, s_rect, 0xffffffffu, x, y, i, best);
             if (owner < 0) continue;
             const float yv = A.frame[i];
             int* c = s_cnt + owner * 5;
             atomicAdd(c + 0, 1);
             if (!(fabsf(yv) < INFINITY)) continue;   // no reading (NaN fails the comparison too)
-            const double d = (double)best;
-            const double r = (double)yv - d;
-            const double tau = A.sigmas * (A.ms + A.sf * (d * d));
             atomicAdd(c + 1, 1);
-            atomicAdd(c + (r < -tau ? 3 : r > tau ? 4 : 2), 1);
+            atomicAdd(c + 2 + planes_class(yv, best, A.sigmas, A.ms, A.sf), 1);   // support, in_front, behind
         }
     }
     __syncthreads();
@@ -203,6 +141,14 @@ int32_t ensure(rbs_handle* h, int planes)
     return RBS_OK;
 }
 
+// The assessor's planes are now those of n poses (0: of none, while they are being drawn), what rbs_assess_get_plane and
+// the *_kernel_ms calls answer from; contour: an rbs_contour_poses drew them.  rbs_occlusion_bodies draws into them too.
+void planes_hold(rbs_assess_state* a, int n, bool contour)
+{
+    a->n = n;
+    a->contour = contour;
+}
+
 // rbs_assess_poses (contour == nullptr: its two kernels and nothing else) and rbs_contour_poses (contour: checked by the
 // caller; one more kernel and one more copy; out_contour gets the counts, its caller takes the verdicts).  `who` names
 // the entry point in the messages.  out may be NULL.
@@ -244,26 +190,14 @@ int32_t run(rbs_handle* h, const char* who, const rbs_assess_params* params, con
     RBS_HIP(h, hipMemcpyAsync(a->d_poses, h_poses, sizeof(double) * 12 * (size_t)planes, hipMemcpyHostToDevice, s));
     RBS_HIP(h, hipMemsetAsync(a->d_rec, 0, sizeof(int) * rbs::kAssessFields * (size_t)planes, s));
     if (contour) RBS_HIP(h, hipMemsetAsync(a->d_crec, 0, sizeof(int) * rbs::kAssessFields * (size_t)planes, s));
-    DevParams P = h->base;
-    P.poses = a->d_poses;
-    P.n = n;
-    P.tile_w = rbs::kAssessTileW;
-    P.tile_px = rbs::kAssessTilePx;
-    P.tile_h = rbs::kAssessTilePx / rbs::kAssessTileW;
-    a->n = 0;
-    a->contour = false;
+    planes_hold(a, 0, false);
     RBS_HIP(h, hipEventRecord(a->ev[0], s));
-    hipLaunchKernelGGL(rbs::rbs_assess_render_kernel, dim3((unsigned)planes, rbs::kAssessRenderSplit), dim3(rbs::kBlock),
-                       rbs::smem_bytes(rbs::kAssessTilePx, false), s, P, a->d_planes, a->d_rects);
+    rbs::launch_pose_planes(s, h->base, a->d_poses, n, true, a->d_planes, a->d_rects, nullptr);
     RBS_HIP(h, hipGetLastError());
     RBS_HIP(h, hipEventRecord(a->ev[1], s));
     rbs::AssessArgs A{};
-    A.planes = a->d_planes;
-    A.rects = a->d_rects;
+    A.S = rbs::PlaneSet{a->d_planes, a->d_rects, h->cols, h->npx, B};
     A.frame = d_frame;
-    A.cols = h->cols;
-    A.npx = h->npx;
-    A.B = B;
     A.sigmas = p.sigmas;
     A.ms = h->base.ms;
     A.sf = h->base.sf;
@@ -285,20 +219,11 @@ int32_t run(rbs_handle* h, const char* who, const rbs_assess_params* params, con
         out[i].reserved[0] = out[i].reserved[1] = 0;
     }
     for (int i = 0; out_contour && i < planes; ++i) out_contour[i] = h_crec[i];
-    a->n = n;
-    a->contour = contour != nullptr;
+    planes_hold(a, n, contour != nullptr);
     return RBS_OK;
 }
 
 }  // namespace assess
-
-// rbs_create: the render kernel's dynamic LDS, beside rbs_render_kernel's.
-int32_t assess_configure(rbs_handle* h)
-{
-    RBS_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&rbs::rbs_assess_render_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)rbs::smem_bytes(rbs::kAssessTilePx, false)));
-    return RBS_OK;
-}
 
 // rbs_destroy (the handle's device is current and its streams are idle).
 void assess_release(rbs_handle* h)

@@ -13,6 +13,8 @@
 //   rbs_handle.h       struct rbs_handle, Rccl, fmt / fail / upload, RBS_HIP, RBS_REFUSE_POISONED, with_flags
 //   rbs_frames.h       frame ingest: obs_frame, convert_f64_f32*, BorrowedFrameGuard, upload_frame, hand_over_*, make_current, frame_abandon
 //   rbs_call.h         the likelihood call: occlusion_coeffs, launch_prep, launch_raster, launch_bgp_step, stp_decide, enqueue_loglikes
+//   rbs_device.h       (through rbsensor_kernels.hip) generic device helpers: rotations, Philox, block_sum / block_max
+//   rbs_pose_planes.h  poses drawn as depth planes: rbs_planes_render_kernel, launch_pose_planes, PlaneSet and its owner rule
 //   rbs_planes.h       the occlusion planes' storage: materialize, slab_expand / exact_expand, store_plane, fit_or_grow, grow_slabs, drain
 //   rbs_planes_api.h   the slot entry points: rbs_get_occlusion .. rbs_import_window, rbs_stream_join, rbs_get_window
 //   rbs_ipc.h          IpcBlob, rbs_ipc_export, rbs_ipc_attach, rbs_stage_windows, rbs_peer_resample
@@ -54,7 +56,10 @@
 // The occlusion planes' storage: materialize, slabs, stamped planes, grow_slabs, drain.
 #include "rbs_planes.h"
 
-// The pose assessor (rbs_assess_*): its kernels and host side (release and create_impl call into it).
+// Poses drawn as depth planes and the rule for reading them back: the render kernel, its launch, PlaneSet (create_impl sets its LDS limit).
+#include "rbs_pose_planes.h"
+
+// The pose assessor (rbs_assess_*): its kernels and host side (release calls into it).
 #include "rbsensor_assess.hip"
 // The contour rule beside it (rbs_contour_*): one more kernel on the assessor's planes.
 #include "rbsensor_contour.hip"
@@ -481,9 +486,7 @@ int32_t create_impl(const rbs_config* cfg, rbs_handle* h)
         for (int k = 0; k < n_kernels; ++k)
             RBS_HIP(h, hipFuncSetAttribute(kernels[k], hipFuncAttributeMaxDynamicSharedMemorySize, (int)rbs::smem_bytes(rbs::kTilePxBig, false, true)));
     }
-    RBS_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&rbs::rbs_render_kernel),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)rbs::smem_bytes(rbs::kTilePxBig, false)));
-    if (int32_t rc = assess_configure(h)) return rc;
+    RBS_HIP(h, rbs::pose_planes_configure());
 
     {   // per-item partial sums: sized for the default tiling so no call ever allocates
         const size_t gmul = h->d_groups[0] ? rbs::kMaxGroups : 1;   // every group of bodies tiles its own rectangle
@@ -1493,8 +1496,9 @@ int32_t rbs_render_depth(rbs_handle* h, const double* pose, float* out)
     P.tile_w = 256;
     P.tile_px = rbs::kTilePxBig;
     P.tile_h = P.tile_px / 256;
-    hipLaunchKernelGGL(rbs::rbs_render_kernel, dim3(1), dim3(rbs::kBlock), rbs::smem_bytes(P.tile_px, false),
-                       h->stream, P, h->d_render);
+    // (one block, the raster kernel's big tile: not launch_pose_planes' geometry)
+    hipLaunchKernelGGL(rbs::rbs_planes_render_kernel<false>, dim3(1), dim3(rbs::kBlock), rbs::smem_bytes(P.tile_px, false),
+                       h->stream, P, h->d_render, (int4*)nullptr, (const int*)nullptr);
     RBS_HIP(h, hipGetLastError());
     RBS_HIP(h, hipMemcpyAsync(out, h->d_render, sizeof(float) * h->npx, hipMemcpyDeviceToHost,
                               h->stream));

@@ -1,10 +1,10 @@
 // rbsensor_contour.hip -- the silhouette of a pose judged against the frame (rbs_contour_*, include/rbsensor_mi355x.h;
 // the rule: DESIGN.md Appendix J, "The contour rule").  Included by rbsensor_capi.hip behind rbsensor_assess.hip: the
-// planes, rectangles, frame and buffers are the assessor's (rbs_assess_state), and rbs_contour_poses is assess::run with
-// one more kernel behind the count kernel:
+// planes (rbs_planes_render_kernel<true>, rbs_pose_planes.h), rectangles, frame and buffers are the assessor's
+// (rbs_assess_state), and rbs_contour_poses is assess::run with one more kernel behind the count kernel:
 //   rbs_contour_count_kernel  a fixed grid per pose over the union of its bodies' rectangles grown by `radius`, in tiles
 //                             of 32 x 32 pixels.  A tile and its halo are staged in LDS once as (owner, depth), composed
-//                             from the B planes as the count kernel composes them; per body present in the staged tile a
+//                             from the B planes by the owner rule the count kernel uses (planes_owner); per body present in the staged tile a
 //                             horizontal and then a vertical running maximum over (owner == b ? depth : -inf) gives the
 //                             anchor of every interior pixel (a window maximum is separable); uncovered interior pixels
 //                             with an anchor are the body's rim and are classed against the frame.  Integer counts in
@@ -33,21 +33,18 @@ __global__ __launch_bounds__(256) void rbs_contour_count_kernel(const ContourArg
     __shared__ int4 s_rect[kMaxBodies];
     __shared__ unsigned s_present;                                  // bodies that own a staged pixel of this tile
     const AssessArgs& A = C.A;
-    const int tid = threadIdx.x, k = blockIdx.y, B = A.B, r = C.radius, cols = A.cols, rows = C.rows;
+    const PlaneSet& PS = A.S;
+    const int tid = threadIdx.x, k = blockIdx.y, B = PS.B, r = C.radius, cols = PS.cols, rows = C.rows;
     const int S = kContourTile + 2 * r;                             // staged side
     for (int e = tid; e < B * 5; e += 256) s_cnt[e] = 0;
-    if (tid < B) s_rect[tid] = A.rects[k * B + tid];
+    if (tid < B) s_rect[tid] = PS.rects[k * B + tid];
     __syncthreads();
-    int x0 = cols, y0 = rows, x1 = 0, y1 = 0;
-    for (int b = 0; b < B; ++b) {
-        const int4 q = s_rect[b];
-        if (q.z <= q.x) continue;
-        x0 = min(x0, q.x); y0 = min(y0, q.y); x1 = max(x1, q.z); y1 = max(y1, q.w);
-    }
+    const int4 u = planes_union_rect(PS, s_rect, 0xffffffffu);
+    int x0 = u.x, y0 = u.y, x1 = u.z, y1 = u.w;
     if (x1 > x0) {                                                  // (block-uniform)
         x0 = max(x0 - r, 0); y0 = max(y0 - r, 0); x1 = min(x1 + r, cols); y1 = min(y1 + r, rows);
         const int nx = (x1 - x0 + kContourTile - 1) / kContourTile, ny = (y1 - y0 + kContourTile - 1) / kContourTile;
-        const float* planes = A.planes + (size_t)k * B * A.npx;
+        const float* planes = PS.planes + (size_t)k * B * PS.npx;
         for (int t = blockIdx.x; t < nx * ny; t += gridDim.x) {
             const int ty = t / nx;
             const int tx0 = x0 + (t - ty * nx) * kContourTile, ty0 = y0 + ty * kContourTile;
@@ -59,15 +56,7 @@ __global__ __launch_bounds__(256) void rbs_contour_count_kernel(const ContourArg
                 const int sy = p / S, x = tx0 - r + (p - sy * S), y = ty0 - r + sy;
                 float best = INFINITY;
                 int owner = -1;
-                if (x >= 0 && x < cols && y >= 0 && y < rows) {
-                    const int i = y * cols + x;
-                    for (int b = 0; b < B; ++b) {                   // ascending: a tie stays with the lowest body
-                        const int4 q = s_rect[b];                   // a plane is valid inside its rectangle only
-                        if (x < q.x || x >= q.z || y < q.y || y >= q.w) continue;
-                        const float d = planes[(size_t)b * A.npx + i];
-                        if (d < best) { best = d; owner = b; }
-                    }
-                }
+                if (x >= 0 && x < cols && y >= 0 && y < rows) owner = planes_owner(PS, planes, s_rect, 0xffffffffu, x, y, y * cols + x, best);
                 s_owner[p] = (signed char)owner;
                 s_depth[p] = best;
                 if (owner >= 0) mine |= 1u << owner;
@@ -111,10 +100,8 @@ __global__ __launch_bounds__(256) void rbs_contour_count_kernel(const ContourArg
                     if (!(a > -INFINITY)) continue;                 // no pixel of b in the window
                     ++rim;
                     if (!(fabsf(yv[q]) < INFINITY)) continue;       // no reading (NaN fails the comparison too)
-                    const double d = (double)a;
-                    const double g = (double)yv[q] - d;
-                    const double tau = A.sigmas * (A.ms + A.sf * (d * d));
-                    if (g < -tau) ++front; else if (g > tau) ++beyond; else ++flush;
+                    const int cls = planes_class(yv[q], a, A.sigmas, A.ms, A.sf);
+                    if (cls == kPlaneInFront) ++front; else if (cls == kPlaneBehind) ++beyond; else ++flush;
                 }
                 int* c = s_cnt + b * 5;
                 if (rim) atomicAdd(c + 0, rim);

@@ -219,30 +219,13 @@ __global__ __launch_bounds__(64) void rbs_find_nms_kernel(const double* __restri
     if (lane == 0) *count = nk;
 }
 
-__device__ inline uint4 philox(unsigned long long seed, unsigned long long ctr_hi, unsigned long long ctr_lo)
-{
-    return rbt::philox(seed, ctr_hi, ctr_lo);
-}
-
-// rotation by the vector v (angle-axis via the unit quaternion, as dbot_ros_amd.pose.rotvec_to_matrix)
-__device__ inline void rotvec_matrix(const double* v, double* R)
-{
-    const double angle = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-    const double half = 0.5 * angle;
-    const double k = angle < 1e-9 ? 0.5 - angle * angle / 48.0 : sin(half) / angle;
-    const double w = cos(half), x = v[0] * k, y = v[1] * k, z = v[2] * k;
-    R[0] = 1.0 - 2.0 * (y * y + z * z); R[1] = 2.0 * (x * y - w * z);       R[2] = 2.0 * (x * z + w * y);
-    R[3] = 2.0 * (x * y + w * z);       R[4] = 1.0 - 2.0 * (x * x + z * z); R[5] = 2.0 * (y * z - w * x);
-    R[6] = 2.0 * (x * z - w * y);       R[7] = 2.0 * (y * z + w * x);       R[8] = 1.0 - 2.0 * (x * x + y * y);
-}
-
 // the six standard normals of child j of survivor k in round `round`: Box-Muller pairs of three Philox blocks
 __device__ inline void child_normals(unsigned long long seed, int round, int k, int j, double* nz)
 {
 #pragma unroll
     for (int pr = 0; pr < 3; ++pr) {
-        const uint4 r = philox(seed, ((unsigned long long)(unsigned)round << 32) | (unsigned)k, ((unsigned long long)(unsigned)j << 2) | pr);
-        const double u1 = 1.0 - rbt::u01(r.x, r.y), u2 = rbt::u01(r.z, r.w);
+        const uint4 r = rbd::philox(seed, ((unsigned long long)(unsigned)round << 32) | (unsigned)k, ((unsigned long long)(unsigned)j << 2) | pr);
+        const double u1 = 1.0 - rbd::u01(r.x, r.y), u2 = rbd::u01(r.z, r.w);
         const double rad = sqrt(-2.0 * log(u1));
         nz[2 * pr] = rad * cos(kTwoPi * u2);
         nz[2 * pr + 1] = rad * sin(kTwoPi * u2);
@@ -254,12 +237,8 @@ __device__ inline void perturb_pose(const double* __restrict__ P, const double* 
 {
     const double v[3] = {sa * nz[0], sa * nz[1], sa * nz[2]};
     double A[9];
-    rotvec_matrix(v, A);
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-            o[3 * r + c] = A[3 * r] * P[c] + A[3 * r + 1] * P[3 + c] + A[3 * r + 2] * P[6 + c];
+    rbd::rotvec_to_matrix(v, A);
+    rbd::matmul3(A, P, o);
     o[9] = P[9] + st * nz[3];
     o[10] = P[10] + st * nz[4];
     o[11] = P[11] + st * nz[5];
@@ -356,7 +335,7 @@ __global__ __launch_bounds__(kFgThreads) void rbs_findfg_trials_kernel(const flo
 {
     const int t = blockIdx.x * kFgThreads + threadIdx.x;
     if (t >= trials) return;
-    const uint4 r = philox(seed, 0xFFFFFFFF00000000ull, (unsigned long long)(unsigned)t);
+    const uint4 r = rbd::philox(seed, 0xFFFFFFFF00000000ull, (unsigned long long)(unsigned)t);
     const unsigned word[3] = {r.x, r.y, r.z};
     double u[3], v[3], d[3];
     bool ok = true;
@@ -578,7 +557,7 @@ __global__ __launch_bounds__(256) void rbs_findr_children_kernel(const double* _
         od[a] = s;
     }
     double A[9];
-    rotvec_matrix(d, A);
+    rbd::rotvec_to_matrix(d, A);
 #pragma unroll
     for (int r = 0; r < 3; ++r)
 #pragma unroll

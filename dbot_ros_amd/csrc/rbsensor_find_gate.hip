@@ -102,7 +102,7 @@ __global__ __launch_bounds__(rbs::kBlock) void rbs_findc_evidence_kernel(const r
                 sx0 = max(ix0 - rad, 0); sy0 = max(iy0 - rad, 0); sx1 = min(ix1 + rad, cols); sy1 = min(iy1 + rad, rows);
             };
             tile_geo();
-            // the tile and its halo, culled as rbs_render_kernel's; on return the tile is complete and synchronised
+            // the tile and its halo, culled as rbs_planes_render_kernel's; on return the tile is complete and synchronised
             rbs::raster_window<false, true>(P, pose, sx0, sy0, sx1, sy1, true, m.tile, m.big, m.nbig,
                                             m.evalq + (tid >> 6) * rbs::kQPlanes * rbs::kEvalQueue, 1u);
             tile_geo();

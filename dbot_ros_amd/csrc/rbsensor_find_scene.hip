@@ -3,7 +3,8 @@
 // per-part finder (find_create_part) per body and a B-body scoring handle (make_scorer), so every score is the sensor's.
 //
 // Per scene find, on the B-body scoring handle's stream, for each searched body in S1's order:
-//   rbs_assess_render_kernel   (the assessor's) the B bodies' planes at the poses so far, into the scene finder's own buffers
+//   rbs_planes_render_kernel<true>  (rbs_pose_planes.h, as the assessor's) the B bodies' planes at the poses so far, into the
+//                              scene finder's own buffers
 //   rbs_finds_residual_kernel  the residual frame: the union of the placed bodies' rectangles grown by the radius, in tiles of
 //                              32 x 32 pixels; a tile and its halo are staged in LDS once as (support, depth) and every thread
 //                              tests its pixels against the (2r + 1)^2 staged neighbours; pixels outside the grown union are
@@ -28,22 +29,18 @@ constexpr unsigned kResNaN = 0x7FC00000u;                       // an explained 
 constexpr int kSceneMaxSweeps = 8, kSceneMaxChildren = 1024;
 
 struct ResidualArgs {
-    const float* planes;      // [B][npx], plane b valid inside rects[b]
-    const int4* rects;        // [B]
+    rbs::PlaneSet S;          // [B] planes of one pose
     const unsigned* frame;    // the frame's bits
     unsigned* out;            // the residual frame's bits
-    int rows, cols, npx, B, radius;
+    int rows, radius;
     unsigned placed;          // bit b: body b is placed
     double sigmas, ms, sf;    // tau = sigmas (ms + sf d d)
 };
 
-// neither r < -tau nor r > tau, r = y - d: the assess rule's support test
+// neither in front nor behind: the assess rule's support test
 __device__ inline bool res_agrees(const ResidualArgs& A, float y, float depth)
 {
-    const double d = (double)depth;
-    const double r = (double)y - d;
-    const double tau = A.sigmas * (A.ms + A.sf * (d * d));
-    return !(r < -tau) && !(r > tau);
+    return rbs::planes_class(y, depth, A.sigmas, A.ms, A.sf) == rbs::kPlaneSupport;
 }
 
 __global__ __launch_bounds__(256) void rbs_finds_residual_kernel(const ResidualArgs A)
@@ -51,20 +48,17 @@ __global__ __launch_bounds__(256) void rbs_finds_residual_kernel(const ResidualA
     __shared__ float s_depth[kResStage * kResStage];            // depth(j) of a staged pixel (its owner's plane)
     __shared__ unsigned char s_support[kResStage * kResStage];  // 1: j is a support pixel
     __shared__ int4 s_rect[rbs::kMaxBodies];
-    const int tid = threadIdx.x, B = A.B, r = A.radius, cols = A.cols, rows = A.rows;
+    const rbs::PlaneSet& PS = A.S;
+    const int tid = threadIdx.x, B = PS.B, r = A.radius, cols = PS.cols, rows = A.rows;
     const int S = kResTile + 2 * r;                             // staged side
-    if (tid < B) s_rect[tid] = A.rects[tid];
+    if (tid < B) s_rect[tid] = PS.rects[tid];
     __syncthreads();
-    int x0 = cols, y0 = rows, x1 = 0, y1 = 0;
-    for (int b = 0; b < B; ++b) {
-        const int4 q = s_rect[b];
-        if (!(A.placed >> b & 1u) || q.z <= q.x) continue;
-        x0 = min(x0, q.x); y0 = min(y0, q.y); x1 = max(x1, q.z); y1 = max(y1, q.w);
-    }
+    const int4 u = rbs::planes_union_rect(PS, s_rect, A.placed);
+    int x0 = u.x, y0 = u.y, x1 = u.z, y1 = u.w;
     const bool any = x1 > x0;                                   // (block-uniform)
     if (any) { x0 = max(x0 - r, 0); y0 = max(y0 - r, 0); x1 = min(x1 + r, cols); y1 = min(y1 + r, rows); }
     // outside the grown union: the frame's bits
-    for (int p = blockIdx.x * 256 + tid; p < A.npx; p += gridDim.x * 256) {
+    for (int p = blockIdx.x * 256 + tid; p < PS.npx; p += gridDim.x * 256) {
         const int y = p / cols, x = p - y * cols;
         if (any && x >= x0 && x < x1 && y >= y0 && y < y1) continue;
         A.out[p] = A.frame[p];
@@ -81,12 +75,7 @@ __global__ __launch_bounds__(256) void rbs_finds_residual_kernel(const ResidualA
             bool support = false;
             if (x >= 0 && x < cols && y >= 0 && y < rows) {
                 const int i = y * cols + x;
-                for (int b = 0; b < B; ++b) {                   // ascending: a tie stays with the lowest body
-                    const int4 q = s_rect[b];                   // a plane is valid inside its rectangle only
-                    if (!(A.placed >> b & 1u) || x < q.x || x >= q.z || y < q.y || y >= q.w) continue;
-                    const float d = A.planes[(size_t)b * A.npx + i];
-                    if (d < best) best = d;
-                }
+                (void)rbs::planes_owner(PS, PS.planes, s_rect, A.placed, x, y, i, best);   // the placed bodies' nearest depth
                 if (best < INFINITY) {
                     const float yv = __uint_as_float(A.frame[i]);
                     support = fabsf(yv) < INFINITY && res_agrees(A, yv, best);   // (NaN fails the first comparison)
@@ -215,26 +204,15 @@ int32_t scene_residual(rbs_find_scene* f, uint32_t placed, float* out)
 {
     rbs_handle* j = f->joint;
     hipStream_t st = f->st;
-    DevParams P = j->base;
-    P.poses = f->d_X;
-    P.n = 1;
-    P.tile_w = rbs::kAssessTileW;
-    P.tile_px = rbs::kAssessTilePx;
-    P.tile_h = rbs::kAssessTilePx / rbs::kAssessTileW;
     RBF_HIP(f, hipEventRecord(f->ev[0], st));
-    hipLaunchKernelGGL(rbs::rbs_assess_render_kernel, dim3((unsigned)f->B, rbs::kAssessRenderSplit), dim3(rbs::kBlock),
-                       rbs::smem_bytes(rbs::kAssessTilePx, false), st, P, f->d_planes, f->d_rects);
+    rbs::launch_pose_planes(st, j->base, f->d_X, 1, true, f->d_planes, f->d_rects, nullptr);   // (j->base.n_bodies == f->B)
     RBF_HIP(f, hipGetLastError());
     RBF_HIP(f, hipEventRecord(f->ev[1], st));
     rbf::ResidualArgs A{};
-    A.planes = f->d_planes;
-    A.rects = f->d_rects;
+    A.S = rbs::PlaneSet{f->d_planes, f->d_rects, j->cols, j->npx, f->B};
     A.frame = reinterpret_cast<const unsigned*>(f->d_frame);
     A.out = reinterpret_cast<unsigned*>(out);
     A.rows = j->rows;
-    A.cols = j->cols;
-    A.npx = j->npx;
-    A.B = f->B;
     A.radius = f->sp.explain_radius;
     A.placed = placed;
     A.sigmas = f->sp.explain_sigmas;

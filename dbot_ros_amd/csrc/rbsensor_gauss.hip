@@ -3,10 +3,9 @@
 // and the rasterizer of rbsensor_kernels.hip.
 //
 // Per frame, on the sensor's stream:
-//   rbs_gauss_render_kernel   one block row per distinct sigma pose (1 + 12 B of them), the pose's screen
-//                             rectangle cut into 64 x 64 tiles dealt to the row's blocks; every tile goes
-//                             through raster_window exactly as rbs_render_kernel's (depths bit-identical to
-//                             the oracle's orc_render).  Plane k is valid inside rect k only.
+//   rbs_planes_render_kernel<false>  (rbs_pose_planes.h) one plane per distinct sigma pose (1 + 12 B of them):
+//                             all bodies, z-min, in the pose's screen rectangle; depths bit-identical to the
+//                             oracle's orc_render.  Plane k is valid inside rect k only.
 //   rbs_gauss_moments_kernel  per pixel of the union rectangle with a finite observation: y_hat, P, h, R, the
 //                             robust body weight b and pi = b / R; a block stages 256 pixels' (pi, residual, h)
 //                             in LDS and thread e accumulates entry e of {Lambda - I (upper triangle), eta} over
@@ -20,37 +19,6 @@ namespace rbs {
 
 constexpr int kGaussMaxBodies = 3;        // 6B(6B+1)/2 + 6B <= 256 entries: one per thread of the moments block
 constexpr int kGaussBlocks = 256;         // moments grid: fixed, so the reduction order is too
-constexpr int kGaussTileW = 64, kGaussTilePx = 4096;   // render tiles: small, so that a pose's rectangle spreads over blocks
-constexpr int kGaussRenderSplit = 32;     // blocks per sigma pose (tiles beyond it: strided)
-
-__global__ __launch_bounds__(kBlock) void rbs_gauss_render_kernel(const DevParams P, float* __restrict__ planes, int4* __restrict__ rects,
-                                                                  const int* __restrict__ err)
-{
-    if (err && *err) return;                  // (rbs_gauss_submit: the frame's prior failed -- its poses are not to be drawn)
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const Smem m = carve(smem, P.tile_px, false);
-    const int k = blockIdx.x;
-    const double* pose = P.poses + (size_t)k * 12 * P.n_bodies;
-    const Rect r = particle_rect(P, pose);
-    if (blockIdx.y == 0 && threadIdx.x == 0) rects[k] = make_int4(r.x0, r.y0, r.x1, r.y1);
-    if (r.x1 <= r.x0) return;
-    const TileGrid tg = tile_grid(r.x1 - r.x0, r.y1 - r.y0, P.tile_w, min(P.tile_w * P.tile_h, P.tile_px));
-    const int nx = (r.x1 - r.x0 + tg.tw - 1) / tg.tw, ny = (r.y1 - r.y0 + tg.th - 1) / tg.th;
-    float* out = planes + (size_t)k * P.npx;
-    for (int t = blockIdx.y; t < nx * ny; t += gridDim.y) {
-        const int ty = t / nx;
-        const int wx0 = r.x0 + (t - ty * nx) * tg.tw, wy0 = r.y0 + ty * tg.th;
-        const int wx1 = min(r.x1, wx0 + tg.tw), wy1 = min(r.y1, wy0 + tg.th);
-        const int tw = wx1 - wx0, npx = tw * (wy1 - wy0);
-        raster_window(P, pose, wx0, wy0, wx1, wy1, true, m.tile, m.big, m.nbig,
-                      m.evalq + (threadIdx.x >> 6) * kQPlanes * kEvalQueue, 0xffffffffu);
-        for (int p = threadIdx.x; p < npx; p += kBlock) {
-            const int lr = p / tw;
-            out[(size_t)(wy0 + lr) * P.cols + wx0 + (p - lr * tw)] = __uint_as_float(m.tile[p]);
-        }
-        __syncthreads();
-    }
-}
 
 struct GaussArgs {
     const float* planes;      // [nd][npx], plane k valid inside rects[k]
@@ -296,7 +264,7 @@ __global__ __launch_bounds__(64) void rbs_gauss_predict_kernel(const GaussDev G)
         s_W[gauss_perm(i, NP) * D + gauss_perm(j, NP)] = s_S[e];
     }
     for (int i = t; i < D; i += 64) G.mpf[gauss_perm(i, NP)] = s_m[i];
-    if (t < B) rbt::rotvec_to_matrix(z + 12 * t + 3, s_Rz[t]);
+    if (t < B) rbd::rotvec_to_matrix(z + 12 * t + 3, s_Rz[t]);
     __syncthreads();
     if (!gauss_cholesky(s_W, s_L, D, s_col)) {
         if (t == 0) *G.err = kGaussNotPD;
@@ -314,9 +282,9 @@ __global__ __launch_bounds__(64) void rbs_gauss_predict_kernel(const GaussDev G)
         double x[6], Rd[9];
 #pragma unroll
         for (int d = 0; d < 6; ++d) x[d] = s_col[6 * b + d] + (k == 0 ? 0.0 : sc * s_L[(6 * b + d) * D + j]);
-        rbt::rotvec_to_matrix(x + 3, Rd);
+        rbd::rotvec_to_matrix(x + 3, Rd);
         double o[12];
-        rbt::matmul3(Rd, s_Rz[b], o);
+        rbd::matmul3(Rd, s_Rz[b], o);
 #pragma unroll
         for (int d = 0; d < 3; ++d) o[9 + d] = z[12 * b + d] + x[d];
         double* out = G.poses + (size_t)q * 12;
@@ -449,11 +417,11 @@ __global__ __launch_bounds__(256) void rbs_gauss_reduce_update_kernel(const Gaus
         double* zb = z + 12 * t;
         double* mb = s_mu + 12 * t;
         double Rz[9], Rm[9], Rn[9], zn[12];
-        rbt::rotvec_to_matrix(zb + 3, Rz);
-        rbt::rotvec_to_matrix(mb + 3, Rm);
-        rbt::matmul3(Rm, Rz, Rn);
+        rbd::rotvec_to_matrix(zb + 3, Rz);
+        rbd::rotvec_to_matrix(mb + 3, Rm);
+        rbd::matmul3(Rm, Rz, Rn);
         for (int d = 0; d < 3; ++d) zn[d] = zb[d] + mb[d];
-        rbt::matrix_to_rotvec(Rn, zn + 3);
+        rbd::matrix_to_rotvec(Rn, zn + 3);
         for (int d = 6; d < 12; ++d) zn[d] = mb[d];
         for (int d = 0; d < 6; ++d) mb[d] = 0.0;
         for (int d = 0; d < 12; ++d) {
@@ -712,15 +680,8 @@ int32_t track_impl(rbs_gauss* g, const float* f32, const double* f64, double* ou
     // ---- device: render, moments, reduction
     hipStream_t s = h->stream;
     RBS_HIP(h, hipMemcpyAsync(g->d_poses, g->h_poses, sizeof(double) * g->sigma.size(), hipMemcpyHostToDevice, s));
-    DevParams P = h->base;
-    P.poses = g->d_poses;
-    P.n = nd;
-    P.tile_w = rbs::kGaussTileW;
-    P.tile_px = rbs::kGaussTilePx;
-    P.tile_h = rbs::kGaussTilePx / rbs::kGaussTileW;
     RBS_HIP(h, hipEventRecord(g->ev[0], s));
-    hipLaunchKernelGGL(rbs::rbs_gauss_render_kernel, dim3((unsigned)nd, rbs::kGaussRenderSplit), dim3(rbs::kBlock),
-                       rbs::smem_bytes(rbs::kGaussTilePx, false), s, P, g->d_planes, g->d_rects, (const int*)nullptr);
+    rbs::launch_pose_planes(s, h->base, g->d_poses, nd, false, g->d_planes, g->d_rects, nullptr);
     RBS_HIP(h, hipGetLastError());
     RBS_HIP(h, hipEventRecord(g->ev[1], s));
     const rbs::GaussArgs G = moments_args(g);
@@ -852,15 +813,8 @@ int32_t submit_impl(rbs_gauss* g, const float* f32, const double* f64, bool* enq
     G.seq = g->seq + 1;
     hipLaunchKernelGGL(rbs::rbs_gauss_predict_kernel, dim3(1), dim3(64), 0, s, G);
     RBS_HIP(h, hipGetLastError());
-    DevParams P = h->base;
-    P.poses = g->d_poses;
-    P.n = g->nd;
-    P.tile_w = rbs::kGaussTileW;
-    P.tile_px = rbs::kGaussTilePx;
-    P.tile_h = rbs::kGaussTilePx / rbs::kGaussTileW;
     RBS_HIP(h, hipEventRecord(g->ev[0], s));
-    hipLaunchKernelGGL(rbs::rbs_gauss_render_kernel, dim3((unsigned)g->nd, rbs::kGaussRenderSplit), dim3(rbs::kBlock),
-                       rbs::smem_bytes(rbs::kGaussTilePx, false), s, P, g->d_planes, g->d_rects, (const int*)g->d_err);
+    rbs::launch_pose_planes(s, h->base, g->d_poses, g->nd, false, g->d_planes, g->d_rects, g->d_err);
     RBS_HIP(h, hipGetLastError());
     RBS_HIP(h, hipEventRecord(g->ev[1], s));
     rbs::GaussArgs A = moments_args(g);

@@ -41,6 +41,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "rbs_device.h"
 #include "rbs_math.h"
 
 namespace rbs {
@@ -1499,28 +1500,14 @@ constexpr int kPrepPerBlock = 8;   // particles (= waves) per block of the recta
 
 // Absolute pose of one body from a state delta and the body's default pose:
 //   R = R(delta rotation vector) R(default rotation vector),  t = t(delta) + t(default),
-// rotation vector -> matrix through the unit quaternion.  The operations and their order are those of
+// rotation vector -> matrix through the unit quaternion (rbs_device.h).  The operations and their order are those of
 // oracle/tracker_oracle.c orc_compose_poses (and of rbsensor_tracker.hip propagate_body); sin / cos / sqrt are the device library's.
-__device__ inline void rotvec_to_matrix_(const double* rv, double* R)
-{
-    const double angle = sqrt(rv[0] * rv[0] + rv[1] * rv[1] + rv[2] * rv[2]);
-    const double half = 0.5 * angle;
-    const double k = angle < 1e-9 ? 0.5 - angle * angle / 48.0 : sin(half) / angle;
-    const double w = cos(half), x = rv[0] * k, y = rv[1] * k, z = rv[2] * k;
-    R[0] = 1.0 - 2.0 * (y * y + z * z); R[1] = 2.0 * (x * y - w * z); R[2] = 2.0 * (x * z + w * y);
-    R[3] = 2.0 * (x * y + w * z); R[4] = 1.0 - 2.0 * (x * x + z * z); R[5] = 2.0 * (y * z - w * x);
-    R[6] = 2.0 * (x * z - w * y); R[7] = 2.0 * (y * z + w * x); R[8] = 1.0 - 2.0 * (x * x + y * y);
-}
 __device__ inline void compose_pose(const double* __restrict__ d, const double* __restrict__ d0, double* __restrict__ out)
 {
     double Rd[9], R0[9];
-    rotvec_to_matrix_(d + 3, Rd);
-    rotvec_to_matrix_(d0 + 3, R0);
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-            out[3 * r + c] = Rd[3 * r] * R0[c] + Rd[3 * r + 1] * R0[3 + c] + Rd[3 * r + 2] * R0[6 + c];
+    rbd::rotvec_to_matrix(d + 3, Rd);
+    rbd::rotvec_to_matrix(d0 + 3, R0);
+    rbd::matmul3(Rd, R0, out);
 #pragma unroll
     for (int k = 0; k < 3; ++k) out[9 + k] = d[k] + d0[k];
 }
@@ -2803,28 +2790,7 @@ __global__ void rbs_set_window_kernel(int4* __restrict__ win, int n, int4 value)
     if (i < n) win[i] = value;
 }
 
-// Inspection hook: depth image of one pose through the same raster_window path.
-__global__ __launch_bounds__(kBlock) void rbs_render_kernel(const DevParams P, float* out)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const Smem m = carve(smem, P.tile_px, false);
-    const Rect r = particle_rect(P, P.poses);
-    if (r.x1 <= r.x0) return;
-    const TileGrid tg = tile_grid(r.x1 - r.x0, r.y1 - r.y0, P.tile_w, min(P.tile_w * P.tile_h, P.tile_px));
-    for (int wy0 = r.y0; wy0 < r.y1; wy0 += tg.th)
-        for (int wx0 = r.x0; wx0 < r.x1; wx0 += tg.tw) {
-            const int wx1 = min(r.x1, wx0 + tg.tw), wy1 = min(r.y1, wy0 + tg.th);
-            const int tw = wx1 - wx0, npx = tw * (wy1 - wy0);
-            raster_window(P, P.poses, wx0, wy0, wx1, wy1, true, m.tile, m.big, m.nbig,
-                          m.evalq + (threadIdx.x >> 6) * kQPlanes * kEvalQueue, 0xffffffffu);
-            for (int p = threadIdx.x; p < npx; p += kBlock) {
-                const int lr = p / tw;
-                out[(wy0 + lr) * P.cols + wx0 + (p - lr * tw)] = __uint_as_float(m.tile[p]);
-            }
-            __syncthreads();
-        }
-}
-
+// (The inspection hook's depth image of one pose is rbs_planes_render_kernel<false>, rbs_pose_planes.h.)
 __global__ void rbs_fill_kernel(float* __restrict__ p, size_t n, float v)
 {
     const size_t stride = (size_t)gridDim.x * blockDim.x;

@@ -31,8 +31,8 @@
 // Every order above is fixed by n, idx and the windows; there is no floating-point atomic: two runs give the same bits.
 // A population that never resampled has n live slots: the same kernels, only longer lists.
 //
-// rbs_occmap_bodies_kernel: the assessor's planes and owner rule (rbs_assess_render_kernel, rbs_assess_count_kernel) over a
-// map instead of a depth frame: integer counts and a 32.32 fixed-point sum, order-free.
+// rbs_occmap_bodies_kernel: the assessor's planes and owner rule (rbs_planes_render_kernel<true>, planes_owner:
+// rbs_pose_planes.h) over a map instead of a depth frame: integer counts and a 32.32 fixed-point sum, order-free.
 #pragma once
 
 namespace rbs {
@@ -87,14 +87,14 @@ __global__ __launch_bounds__(1024) void rbs_occmap_weights_kernel(const double* 
     const int tid = threadIdx.x;
     double m = lw ? -INFINITY : 0.0;
     if (lw) for (int i = tid; i < n; i += 1024) m = fmax(m, lw[i]);
-    m = rbt::block_max(m, sh);
+    m = rbd::block_max(m, sh);
     double s = 0.0;
     for (int i = tid; i < n; i += 1024) {
         const double ei = lw ? exp(lw[i] - m) : 1.0;
         e[i] = ei;
         s += ei;
     }
-    const double S = rbt::block_sum(s, sh);
+    const double S = rbd::block_sum(s, sh);
     if (tid == 0) { head_d[0] = m; head_d[1] = S; }
 }
 
@@ -227,35 +227,34 @@ __global__ __launch_bounds__(64 * kOccParts) void rbs_occmap_kernel(const OccVie
 
 // ---- per-body summary of a map -------------------------------------------------------------------------------------------------
 struct OccBodiesArgs {
-    const float* planes;      // [n x B][npx], plane (k, b) valid inside rects[k B + b] (rbs_assess_render_kernel)
-    const int4* rects;        // [n x B]
+    PlaneSet S;               // the assessor's n x B planes
     const float* map;         // [npx]
-    int cols, npx, B;
     double threshold;
     rbs_occlusion_body* rec;  // [n x B], zeroed
 };
 
-// Every pixel of pose blockIdx.y's rectangle with rbs_assess_count_kernel's walk and owner rule (assess_union_rect,
-// assess_owner: rbsensor_assess.hip).
+// Every pixel of pose blockIdx.y's rectangle with rbs_assess_count_kernel's walk and owner rule (planes_union_rect,
+// planes_owner: rbs_pose_planes.h).
 __global__ __launch_bounds__(256) void rbs_occmap_bodies_kernel(const OccBodiesArgs A)
 {
     __shared__ int s_cnt[kMaxBodies * 2];
     __shared__ unsigned long long s_sum[kMaxBodies];
     __shared__ int4 s_rect[kMaxBodies];
-    const int tid = threadIdx.x, k = blockIdx.y, B = A.B;
+    const PlaneSet& S = A.S;
+    const int tid = threadIdx.x, k = blockIdx.y, B = S.B;
     for (int e = tid; e < B * 2; e += 256) s_cnt[e] = 0;
-    if (tid < B) { s_sum[tid] = 0ull; s_rect[tid] = A.rects[k * B + tid]; }
+    if (tid < B) { s_sum[tid] = 0ull; s_rect[tid] = S.rects[k * B + tid]; }
     __syncthreads();
-    const int4 u = assess_union_rect(s_rect, B, A.cols, A.npx);
+    const int4 u = planes_union_rect(S, s_rect, 0xffffffffu);
     const int x0 = u.x, y0 = u.y, x1 = u.z, y1 = u.w;
     if (x1 > x0) {
         const int w = x1 - x0, total = w * (y1 - y0);
-        const float* planes = A.planes + (size_t)k * B * A.npx;
+        const float* planes = S.planes + (size_t)k * B * S.npx;
         for (int p = blockIdx.x * 256 + tid; p < total; p += gridDim.x * 256) {
             const int ly = p / w, x = x0 + (p - ly * w), y = y0 + ly;
-            const int i = y * A.cols + x;
+            const int i = y * S.cols + x;
             float best;
-            const int owner = assess_owner(planes, s_rect, B, A.npx, x, y, i, best);
+            const int owner = planes_owner(S, planes, s_rect, 0xffffffffu, x, y, i, best);
             if (owner < 0) continue;
             const double mv = (double)A.map[i];
             atomicAdd(s_cnt + owner * 2, 1);
@@ -463,29 +462,17 @@ int32_t rbs_occlusion_bodies(rbs_handle* h, const float* map, const double* pose
     rbs_assess_state* a = h->assess;
     rbs_occmap_state* o = h->occmap;
     hipStream_t s = h->stream;
-    // the assessor's planes and rectangles at these poses: its own render launch, as assess::run makes it
+    // the assessor's planes and rectangles at these poses
     RBS_HIP(h, hipStreamSynchronize(s));   // (the two buffers written next have no reader left)
     RBS_HIP(h, hipMemcpy(a->d_poses, poses, sizeof(double) * 12 * (size_t)planes, hipMemcpyHostToDevice));
     RBS_HIP(h, hipMemcpy(o->d_out, map, sizeof(float) * (size_t)h->npx, hipMemcpyHostToDevice));
     RBS_HIP(h, hipMemsetAsync(o->d_brec, 0, sizeof(rbs_occlusion_body) * (size_t)planes, s));
-    DevParams P = h->base;
-    P.poses = a->d_poses;
-    P.n = n;
-    P.tile_w = rbs::kAssessTileW;
-    P.tile_px = rbs::kAssessTilePx;
-    P.tile_h = rbs::kAssessTilePx / rbs::kAssessTileW;
-    a->n = 0;
-    a->contour = false;
-    hipLaunchKernelGGL(rbs::rbs_assess_render_kernel, dim3((unsigned)planes, rbs::kAssessRenderSplit), dim3(rbs::kBlock),
-                       rbs::smem_bytes(rbs::kAssessTilePx, false), s, P, a->d_planes, a->d_rects);
+    assess::planes_hold(a, 0, false);
+    rbs::launch_pose_planes(s, h->base, a->d_poses, n, true, a->d_planes, a->d_rects, nullptr);
     RBS_HIP(h, hipGetLastError());
     rbs::OccBodiesArgs A{};
-    A.planes = a->d_planes;
-    A.rects = a->d_rects;
+    A.S = rbs::PlaneSet{a->d_planes, a->d_rects, h->cols, h->npx, B};
     A.map = o->d_out;
-    A.cols = h->cols;
-    A.npx = h->npx;
-    A.B = B;
     A.threshold = threshold;
     A.rec = o->d_brec;
     hipLaunchKernelGGL(rbs::rbs_occmap_bodies_kernel, dim3(rbs::kAssessCountBlocks, (unsigned)n), dim3(256), 0, s, A);
@@ -494,7 +481,7 @@ int32_t rbs_occlusion_bodies(rbs_handle* h, const float* map, const double* pose
     RBS_HIP(h, hipMemcpy(out, o->d_brec, sizeof(rbs_occlusion_body) * (size_t)planes, hipMemcpyDeviceToHost));
     // (the planes of these poses are what rbs_assess_get_plane hands out now, as after an rbs_assess_poses; the assessor's kernel
     // times -- rbs_assess_kernel_ms -- stay those of its own last call: no event of its is recorded here)
-    a->n = n;
+    assess::planes_hold(a, n, false);
     return RBS_OK;
 }
 

@@ -180,7 +180,7 @@ __global__ __launch_bounds__(1024) void rbs_post_kernel(const TrackerDev T, cons
     const int first = tid < stride ? tid : n;
     double m = -INFINITY;
     for (int i = first; i < n; i += stride) m = fmax(m, T.logw[i]);
-    m = block_max(m, sh);
+    m = rbd::block_max(m, sh);
     double s = 0.0, q = 0.0;
     for (int i = first; i < n; i += stride) {   // (a thread reads back below only the e_i it stored here)
         const double e = exp(T.logw[i] - m);
@@ -188,8 +188,8 @@ __global__ __launch_bounds__(1024) void rbs_post_kernel(const TrackerDev T, cons
         s += e;
         q += e * e;
     }
-    const double S = block_sum(s, sh);
-    const double Q = block_sum(q, sh);
+    const double S = rbd::block_sum(s, sh);
+    const double Q = rbd::block_sum(q, sh);
     // survivors: a bitmap of n bits in LDS (slot values are < n; anything else is not a slot and is not counted)
     for (int w = tid; w < kMultiBlockFrom / 32; w += 1024) bm[w] = 0u;
     if (tid == 0) sh_cnt = 0;
@@ -260,7 +260,7 @@ __global__ __launch_bounds__(1024) void rbs_post_max_kernel(const TrackerDev T, 
         const int i = blockIdx.x * kChunk + k * 1024 + (int)threadIdx.x;
         if (i < T.n) m = fmax(m, T.logw[i]);
     }
-    m = block_max(m, sh);
+    m = rbd::block_max(m, sh);
     if (threadIdx.x == 0) L.mx[blockIdx.x] = m;
     const int words = (T.n + 31) / 32, w = blockIdx.x * (kChunk / 32) + (int)threadIdx.x;
     if ((int)threadIdx.x < kChunk / 32 && w < words) P.bitmap[w] = 0u;
@@ -275,7 +275,7 @@ __global__ __launch_bounds__(1024) void rbs_post_sums_kernel(const TrackerDev T,
     const bool pending = recentred == 0;
     double m = -INFINITY;
     for (int b = threadIdx.x; b < (int)gridDim.x; b += 1024) m = fmax(m, L.mx[b]);
-    m = block_max(m, sh);
+    m = rbd::block_max(m, sh);
     double e[4], se = 0.0, sq = 0.0;
     for (int k = 0; k < 4; ++k) {
         const int i = blockIdx.x * kChunk + k * 1024 + (int)threadIdx.x;
@@ -292,8 +292,8 @@ __global__ __launch_bounds__(1024) void rbs_post_sums_kernel(const TrackerDev T,
                 atomicOr(P.bitmap + (v >> 5), 1u << (v & 31));
         }
     }
-    se = block_sum(se, sh);
-    sq = block_sum(sq, sh);
+    se = rbd::block_sum(se, sh);
+    sq = rbd::block_sum(sq, sh);
     if (threadIdx.x == 0) { L.se[blockIdx.x] = se; L.sq[blockIdx.x] = sq; }
     for (int g = 0; g < T.D / 6; ++g) {
         double a[6];

@@ -47,73 +47,6 @@ struct TrackerDev {
     int* host_flags;
 };
 
-// ------------------------------------------------------------------ rotations
-// rotation vector -> row-major matrix through the unit quaternion; same formula as
-// dbot_ros_amd/pose.py rotvec_to_matrix.
-__device__ inline void rotvec_to_matrix(const double* rv, double* R)
-{
-    const double angle = sqrt(rv[0] * rv[0] + rv[1] * rv[1] + rv[2] * rv[2]);
-    const double half = 0.5 * angle;
-    const double k = angle < 1e-9 ? 0.5 - angle * angle / 48.0 : sin(half) / angle;
-    const double w = cos(half), x = rv[0] * k, y = rv[1] * k, z = rv[2] * k;
-    R[0] = 1.0 - 2.0 * (y * y + z * z); R[1] = 2.0 * (x * y - w * z); R[2] = 2.0 * (x * z + w * y);
-    R[3] = 2.0 * (x * y + w * z); R[4] = 1.0 - 2.0 * (x * x + z * z); R[5] = 2.0 * (y * z - w * x);
-    R[6] = 2.0 * (x * z - w * y); R[7] = 2.0 * (y * z + w * x); R[8] = 1.0 - 2.0 * (x * x + y * y);
-}
-
-// matrix -> rotation vector, atan2 form (dbot_ros_amd/tracker.py _rotvecs / pose.py matrix_to_rotvec)
-__device__ inline void matrix_to_rotvec(const double* R, double* rv)
-{
-    const double sx = 0.5 * (R[7] - R[5]), sy = 0.5 * (R[2] - R[6]), sz = 0.5 * (R[3] - R[1]);
-    const double sn = sqrt(sx * sx + sy * sy + sz * sz);
-    const double cs = 0.5 * ((R[0] + R[4] + R[8]) - 1.0);
-    const double ang = atan2(sn, cs);
-    if (sn > 1e-8 || cs > 0.0) {
-        const double k = sn > 1e-8 ? ang / sn : 1.0;
-        rv[0] = sx * k; rv[1] = sy * k; rv[2] = sz * k;
-        return;
-    }
-    // angle ~ pi: the antisymmetric part vanishes, the axis comes from the symmetric part
-    // (column i of R + e_i is parallel to the axis; i = the largest diagonal entry), as in
-    // dbot_ros_amd/pose.py matrix_to_rotvec
-    double d[3];
-    for (int k = 0; k < 3; ++k) d[k] = sqrt(fmax((R[4 * k] + 1.0) * 0.5, 0.0));
-    const int i = d[0] >= d[1] ? (d[0] >= d[2] ? 0 : 2) : (d[1] >= d[2] ? 1 : 2);
-    double a[3];
-    for (int k = 0; k < 3; ++k) a[k] = (R[3 * k + i] + (k == i ? 1.0 : 0.0)) / (2.0 * d[i]);
-    const double an = sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
-    for (int k = 0; k < 3; ++k) rv[k] = a[k] / an * ang;
-}
-
-__device__ inline void matmul3(const double* A, const double* B, double* C)
-{
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-            C[3 * r + c] = A[3 * r] * B[c] + A[3 * r + 1] * B[3 + c] + A[3 * r + 2] * B[6 + c];
-}
-
-// ------------------------------------------------------------------ random numbers
-// Philox4x32-10 counter-based generator: (seed, frame, stream, index) -> 4 x 32 random bits.
-__device__ inline uint4 philox(unsigned long long seed, unsigned long long ctr_hi, unsigned long long ctr_lo)
-{
-    unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
-    unsigned c0 = (unsigned)ctr_lo, c1 = (unsigned)(ctr_lo >> 32), c2 = (unsigned)ctr_hi, c3 = (unsigned)(ctr_hi >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
-        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
-        c1 = (unsigned)p1; c3 = (unsigned)p0; c0 = n0; c2 = n2;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return make_uint4(c0, c1, c2, c3);
-}
-__device__ inline double u01(unsigned hi, unsigned lo)   // 53-bit uniform in [0,1)
-{
-    return (double)((((unsigned long long)hi << 32) | lo) >> 11) * (1.0 / 9007199254740992.0);
-}
-
 // ------------------------------------------------------------------ f2: transition + pose composition
 // One thread per particle, sampling block b: restart from the OLD particle, apply the
 // transition of bodies 0..b with their accumulated noise (vel' = vf vel + sigma o n,
@@ -136,8 +69,8 @@ __device__ inline void propagate_body(const TrackerDev& T, int b, int i, int bb,
             } else {  // Box-Muller on Philox uniforms: 3 pairs
 #pragma unroll
                 for (int pr = 0; pr < 3; ++pr) {
-                    const uint4 r = philox(T.seed, (T.frame << 8) | (unsigned)b, ((unsigned long long)i << 2) | pr);
-                    const double u1 = 1.0 - u01(r.x, r.y), u2 = u01(r.z, r.w);
+                    const uint4 r = rbd::philox(T.seed, (T.frame << 8) | (unsigned)b, ((unsigned long long)i << 2) | pr);
+                    const double u1 = 1.0 - rbd::u01(r.x, r.y), u2 = rbd::u01(r.z, r.w);
                     const double rad = sqrt(-2.0 * log(u1));
                     nz[2 * pr] = rad * cos(6.283185307179586 * u2);
                     nz[2 * pr + 1] = rad * sin(6.283185307179586 * u2);
@@ -158,9 +91,9 @@ __device__ inline void propagate_body(const TrackerDev& T, int b, int i, int bb,
 #pragma unroll
     for (int k = 0; k < kBody; ++k) T.part_new[(size_t)i * T.D + bb * kBody + k] = s[k];
     double Rd[9], R0[9], R[9];
-    rotvec_to_matrix(s + 3, Rd);
-    rotvec_to_matrix(T.deflt + bb * kBody + 3, R0);
-    matmul3(Rd, R0, R);
+    rbd::rotvec_to_matrix(s + 3, Rd);
+    rbd::rotvec_to_matrix(T.deflt + bb * kBody + 3, R0);
+    rbd::matmul3(Rd, R0, R);
     double* out = T.poses + ((size_t)i * T.parts + bb) * 12;
 #pragma unroll
     for (int k = 0; k < 9; ++k) out[k] = R[k];
@@ -180,29 +113,6 @@ __global__ __launch_bounds__(256) void propagate_kernel(const TrackerDev T, int 
 }
 
 // ------------------------------------------------------------------ f1: weights, KL, resampling
-__device__ inline double block_sum(double v, double* sh)
-{
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    const int w = threadIdx.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[w] = v;
-    __syncthreads();
-    double s = 0.0;
-    for (int k = 0; k < (int)(blockDim.x >> 6); ++k) s += sh[k];
-    return s;
-}
-__device__ inline double block_max(double v, double* sh)
-{
-    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_down(v, off, 64));
-    const int w = threadIdx.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[w] = v;
-    __syncthreads();
-    double s = -INFINITY;
-    for (int k = 0; k < (int)(blockDim.x >> 6); ++k) s = fmax(s, sh[k]);
-    return s;
-}
-
 // Single block (1024 threads): log_w += new_ll - ll; ll = new_ll; w = softmax(log_w);
 // KL(w || uniform) = log n + sum w log w; if KL > max_kl: cdf = cumsum(w)/sum, flag = 1.
 // `updated`: the sensor call wrote slot i for particle i, so the slot map becomes identity.
@@ -220,17 +130,17 @@ __device__ inline void weights_body(const TrackerDev& T, int updated, double* sh
         if (updated) T.idx[i] = i;
         m = fmax(m, lw);
     }
-    m = block_max(m, sh);
+    m = rbd::block_max(m, sh);
     double s = 0.0;
     for (int i = lo; i < hi; ++i) s += exp(T.logw[i] - m);
     const double local = s;
-    const double S = block_sum(s, sh);
+    const double S = rbd::block_sum(s, sh);
     double e = 0.0;
     for (int i = lo; i < hi; ++i) {
         const double w = exp(T.logw[i] - m) / S;
         if (w > 0.0) e += w * log(w);
     }
-    const double kl = log((double)n) + block_sum(e, sh);
+    const double kl = log((double)n) + rbd::block_sum(e, sh);
     const bool resample = kl > T.max_kl;
     if (threadIdx.x == 0) {
         T.flag[0] = resample ? 1 : 0;
@@ -308,7 +218,7 @@ __global__ __launch_bounds__(1024) void weights_w1_kernel(const TrackerDev T, in
             m = fmax(m, lw);
         }
     }
-    m = block_max(m, sh);
+    m = rbd::block_max(m, sh);
     if (threadIdx.x == 0) T.red[blockIdx.x] = m;
 }
 
@@ -317,7 +227,7 @@ __global__ __launch_bounds__(1024) void weights_w2_kernel(const TrackerDev T)
     __shared__ double sh[16];
     double m = -INFINITY;
     for (int b = threadIdx.x; b < (int)gridDim.x; b += 1024) m = fmax(m, T.red[b]);
-    m = block_max(m, sh);
+    m = rbd::block_max(m, sh);
     const int base = blockIdx.x * kChunk;
     double se = 0.0, sl = 0.0;
     for (int k = 0; k < 4; ++k) {
@@ -330,8 +240,8 @@ __global__ __launch_bounds__(1024) void weights_w2_kernel(const TrackerDev T)
             if (e > 0.0) sl += e * d;
         }
     }
-    se = block_sum(se, sh);
-    sl = block_sum(sl, sh);
+    se = rbd::block_sum(se, sh);
+    sl = rbd::block_sum(sl, sh);
     if (threadIdx.x == 0) {
         T.red[kRedBlocks + blockIdx.x] = se;
         T.red[2 * kRedBlocks + blockIdx.x] = sl;
@@ -417,7 +327,7 @@ __global__ __launch_bounds__(1024) void mean_m1_kernel(const TrackerDev T)
         const int i = blockIdx.x * kChunk + k * 1024 + (int)threadIdx.x;
         if (i < T.n) m = fmax(m, T.logw[i]);
     }
-    m = block_max(m, sh);
+    m = rbd::block_max(m, sh);
     if (threadIdx.x == 0) T.red[blockIdx.x] = m;
 }
 
@@ -427,7 +337,7 @@ __global__ __launch_bounds__(1024) void mean_m2_kernel(const TrackerDev T)
     __shared__ double shb[16][kBody];
     double m = -INFINITY;
     for (int b = threadIdx.x; b < (int)gridDim.x; b += 1024) m = fmax(m, T.red[b]);
-    m = block_max(m, sh);
+    m = rbd::block_max(m, sh);
     double se = 0.0;
     double e[4];
     for (int k = 0; k < 4; ++k) {
@@ -435,7 +345,7 @@ __global__ __launch_bounds__(1024) void mean_m2_kernel(const TrackerDev T)
         e[k] = i < T.n ? exp(T.logw[i] - m) : 0.0;
         se += e[k];
     }
-    se = block_sum(se, sh);
+    se = rbd::block_sum(se, sh);
     double* out = T.red + 3 * kRedBlocks + (size_t)blockIdx.x * T.D;
     if (threadIdx.x == 0) T.red[kRedBlocks + blockIdx.x] = se;
     for (int b = 0; b < T.parts; ++b) {
@@ -482,11 +392,11 @@ __global__ __launch_bounds__(64) void mean_m3_kernel(const TrackerDev T, int blo
         double* z = T.deflt + b * kBody;
         const double* mu = T.mean + b * kBody;
         double Rm[9], Rz[9], R[9];
-        rotvec_to_matrix(mu + 3, Rm);
-        rotvec_to_matrix(z + 3, Rz);
-        matmul3(Rm, Rz, R);
+        rbd::rotvec_to_matrix(mu + 3, Rm);
+        rbd::rotvec_to_matrix(z + 3, Rz);
+        rbd::matmul3(Rm, Rz, R);
         for (int k = 0; k < 3; ++k) z[k] += mu[k];
-        matrix_to_rotvec(R, z + 3);
+        rbd::matrix_to_rotvec(R, z + 3);
         for (int k = 6; k < 12; ++k) z[k] = mu[k];
         double* RmT = T.mean + T.D + b * 9;
         for (int r = 0; r < 3; ++r)
@@ -503,8 +413,8 @@ __device__ inline void resample_one(const TrackerDev& T, int b, int j)
         double u;
         if (T.uniforms) u = T.uniforms[(size_t)b * T.n + j];
         else {
-            const uint4 r = philox(T.seed ^ 0x5bd1e995ull, (T.frame << 8) | (unsigned)b, (unsigned long long)j);
-            u = u01(r.x, r.y);
+            const uint4 r = rbd::philox(T.seed ^ 0x5bd1e995ull, (T.frame << 8) | (unsigned)b, (unsigned long long)j);
+            u = rbd::u01(r.x, r.y);
         }
         int lo = 0, hi = T.n;   // first index with cdf > u
         while (lo < hi) {
@@ -568,10 +478,10 @@ __device__ inline void mean_body(const TrackerDev& T, const double* __restrict__
     if (!uniform) {
         m = -INFINITY;
         for (int i = threadIdx.x; i < n; i += 1024) m = fmax(m, T.logw[i]);
-        m = block_max(m, sh);
+        m = rbd::block_max(m, sh);
         double s = 0.0;
         for (int i = threadIdx.x; i < n; i += 1024) s += exp(T.logw[i] - m);
-        S = block_sum(s, sh);
+        S = rbd::block_sum(s, sh);
     }
     // the twelve components of a body are reduced together: each one's additions are exactly
     // those of block_sum (same per-thread order, same shuffle tree, same order over the waves),
@@ -606,11 +516,11 @@ __device__ inline void mean_body(const TrackerDev& T, const double* __restrict__
         double* z = T.deflt + b * kBody;
         const double* mu = T.mean + b * kBody;
         double Rm[9], Rz[9], R[9];
-        rotvec_to_matrix(mu + 3, Rm);
-        rotvec_to_matrix(z + 3, Rz);
-        matmul3(Rm, Rz, R);
+        rbd::rotvec_to_matrix(mu + 3, Rm);
+        rbd::rotvec_to_matrix(z + 3, Rz);
+        rbd::matmul3(Rm, Rz, R);
         for (int k = 0; k < 3; ++k) z[k] += mu[k];
-        matrix_to_rotvec(R, z + 3);
+        rbd::matrix_to_rotvec(R, z + 3);
         for (int k = 6; k < 12; ++k) z[k] = mu[k];
         double* RmT = T.mean + T.D + b * 9;
         for (int r = 0; r < 3; ++r)
@@ -631,9 +541,9 @@ __device__ inline void recentre_body(const TrackerDev& T, double* __restrict__ p
 {
     for (int k = 0; k < 3; ++k) p[k] -= T.mean[b * kBody + k];
     double Rd[9], R[9];
-    rotvec_to_matrix(p + 3, Rd);
-    matmul3(Rd, T.mean + T.D + b * 9, R);
-    matrix_to_rotvec(R, p + 3);
+    rbd::rotvec_to_matrix(p + 3, Rd);
+    rbd::matmul3(Rd, T.mean + T.D + b * 9, R);
+    rbd::matrix_to_rotvec(R, p + 3);
 }
 __device__ inline void recentre_one(const TrackerDev& T, double* __restrict__ part_new, int i)
 {
@@ -782,7 +692,7 @@ __global__ void default_pose_kernel(const TrackerDev T)
     const int bb = threadIdx.x;
     if (bb >= T.parts) return;
     double R0[9];
-    rotvec_to_matrix(T.deflt + bb * kBody + 3, R0);
+    rbd::rotvec_to_matrix(T.deflt + bb * kBody + 3, R0);
     double* out = T.poses + (size_t)bb * 12;
     for (int k = 0; k < 9; ++k) out[k] = R0[k];
     for (int k = 0; k < 3; ++k) out[9 + k] = T.deflt[bb * kBody + k];

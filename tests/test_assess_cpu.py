@@ -137,7 +137,9 @@ def test_symbols_are_declared_and_exported():
     assert b"rbs_test_assess" not in release
     src = open(os.path.join(ROOT, "dbot_ros_amd", "csrc", "rbsensor_assess.hip")).read()
     kernels = re.findall(r"__global__[^\n]*?void\s+(\w+)\s*\(", src)
-    assert kernels == ["rbs_assess_render_kernel", "rbs_assess_count_kernel"]
+    assert kernels == ["rbs_assess_count_kernel"]          # (the planes: rbs_planes_render_kernel, shared, rbs_pose_planes.h)
+    shared = open(os.path.join(ROOT, "dbot_ros_amd", "csrc", "rbs_pose_planes.h")).read()
+    assert re.findall(r"__global__[^\n]*?void\s+(\w+)\s*\(", shared) == ["rbs_planes_render_kernel"]
     assert not any(re.fullmatch(r"rbs_find_\w*_kernel", k) for k in kernels)
 
 
