@@ -59,6 +59,8 @@ EXPORTS = (
     "rbs_contour_default_params", "rbs_contour_poses", "rbs_contour_verdict", "rbs_contour_kernel_ms",
     "rbs_occlusion_mean", "rbs_occlusion_mean_ms", "rbs_occlusion_bodies",
     "rbs_tracker_set_occlusion_map", "rbs_tracker_occlusion_map", "rbs_tracker_occlusion_map_ms",
+    "rbs_object_map", "rbs_object_map_ms", "rbs_object_map_info", "rbs_object_segment_default_params", "rbs_object_segment",
+    "rbs_tracker_set_object_map", "rbs_tracker_object_map", "rbs_tracker_object_map_ms", "rbs_tracker_poses",
 )
 RBS_ASSESS_OUT_OF_VIEW, RBS_ASSESS_OCCLUDED, RBS_ASSESS_SUPPORTED, RBS_ASSESS_LOST = range(4)
 RBS_CONTOUR_NO_RIM, RBS_CONTOUR_UNDECIDED, RBS_CONTOUR_PRESENT, RBS_CONTOUR_ABSENT = range(4)
@@ -223,6 +225,15 @@ class RbsOcclusionBody(C.Structure):
         ("occluded", C.c_int32),
         ("sum_q32", C.c_int64),
         ("reserved", C.c_int32 * 4),
+    ]
+
+
+class RbsObjectSegmentParams(C.Structure):
+    _fields_ = [
+        ("min_cover", C.c_double),
+        ("sigmas", C.c_double),
+        ("depth_sigmas", C.c_double),
+        ("reserved", C.c_double),
     ]
 
 
@@ -522,5 +533,23 @@ def load():
     lib.rbs_tracker_occlusion_map.argtypes = [H, ip, fp]
     lib.rbs_tracker_occlusion_map_ms.restype = C.c_int32
     lib.rbs_tracker_occlusion_map_ms.argtypes = [H, fp]
+    lib.rbs_object_map.restype = C.c_int32
+    lib.rbs_object_map.argtypes = [H, dp, C.c_int32, ip, dp, C.c_int32, fp, fp, fp]
+    lib.rbs_object_map_ms.restype = C.c_int32
+    lib.rbs_object_map_ms.argtypes = [H, fp]
+    lib.rbs_object_map_info.restype = C.c_int32
+    lib.rbs_object_map_info.argtypes = [H, ip]
+    lib.rbs_object_segment_default_params.restype = None
+    lib.rbs_object_segment_default_params.argtypes = [C.POINTER(RbsObjectSegmentParams)]
+    lib.rbs_object_segment.restype = C.c_int32
+    lib.rbs_object_segment.argtypes = [H, C.POINTER(RbsObjectSegmentParams), fp, fp, fp, ip, ip, ip, fp, C.c_int32, ip]
+    lib.rbs_tracker_set_object_map.restype = C.c_int32
+    lib.rbs_tracker_set_object_map.argtypes = [H, C.c_int32]
+    lib.rbs_tracker_object_map.restype = C.c_int32
+    lib.rbs_tracker_object_map.argtypes = [H, ip, fp, fp, fp]
+    lib.rbs_tracker_object_map_ms.restype = C.c_int32
+    lib.rbs_tracker_object_map_ms.argtypes = [H, fp]
+    lib.rbs_tracker_poses.restype = C.c_int32
+    lib.rbs_tracker_poses.argtypes = [H, dp]
     _lib = lib
     return lib

@@ -291,6 +291,7 @@ int32_t hand_over_host(rbs_handle* h, const float* f32, const double* f64)
     if (int32_t rc = next_frame_staging(h)) return rc;
     if (int32_t rc = upload_frame(h, staging(h), f32, f64)) return rc;   // (staged and sent piece by piece)
     h->pending_frames += 1;
+    h->frames_handed += 1;
     return RBS_OK;
 }
 // ... a frame in pinned memory: the committed buffer (a group's: shard 0's, sent to every shard)
@@ -298,6 +299,7 @@ int32_t hand_over_pinned(rbs_handle* h, const float* src)
 {
     if (int32_t rc = upload_frame(h, src)) return rc;
     h->pending_frames += 1;
+    h->frames_handed += 1;
     return RBS_OK;
 }
 // ... the driver's full-resolution frame, sub-sampled by f.
@@ -320,6 +322,7 @@ void hand_over_borrowed(rbs_handle* h, const float* f32, const double* f64)
 {
     h->fr.next = f64 ? NextFrame{NextFrame::BORROWED_F64, f64} : NextFrame{NextFrame::BORROWED_F32, f32};
     h->pending_frames += 1;
+    h->frames_handed += 1;
 }
 // ... a frame in device memory, ingested on stream s by whatever needs it first
 int32_t hand_over_device(rbs_handle* h, const float* d_depth, hipStream_t s)
@@ -327,6 +330,7 @@ int32_t hand_over_device(rbs_handle* h, const float* d_depth, hipStream_t s)
     if (int32_t rc = release_frame_slot(h)) return rc;
     h->fr.next = {NextFrame::DEVICE, d_depth, s};
     h->pending_frames += 1;
+    h->frames_handed += 1;
     return RBS_OK;
 }
 // ... the frame uploaded ahead (fr.next is AHEAD)
@@ -337,6 +341,7 @@ int32_t hand_over_ahead(rbs_handle* h)
     if (int32_t rc = release_frame_slot(h)) return rc;   // the readers of the frame it replaces are on the launch stream by now
     h->fr.cur = k;
     h->pending_frames += 1;
+    h->frames_handed += 1;
     return RBS_OK;
 }
 

@@ -243,6 +243,10 @@ struct rbs_handle {
     // ---- the occlusion map (rbsensor_occmap.hip): its buffers, allocated by the first rbs_occlusion_mean / rbs_occlusion_bodies /
     // rbs_tracker_set_occlusion_map
     struct rbs_occmap_state* occmap = nullptr;
+    // ---- the object map (rbsensor_objmap.hip): its buffers, allocated by the first rbs_object_map / rbs_object_segment /
+    // rbs_tracker_set_object_map
+    struct rbs_objmap_state* objmap = nullptr;
+    long frames_handed = 0;     // frames handed over since rbs_create (rbs_object_segment refuses a handle that never saw one)
 };
 
 // RCCL, bound at run time (dlopen): a single-device handle never needs it, and a process that

@@ -55,6 +55,17 @@ struct rbs_tracker {
     float map_ms = 0.f;
     int32_t map_frame = 0;
     std::vector<float> map;
+    // the object map (rbs_tracker_set_object_map, rbsensor_objmap.hip): off by default, on the occlusion map's pattern.  An image
+    // is [n_objects + 2][npx] floats: cover, depth, var.
+    bool obj_on = false, obj_valid = false, obj_ready = false;
+    float* h_obj[2] = {nullptr, nullptr};
+    float* h_obj_dev[2] = {nullptr, nullptr};
+    hipEvent_t ev_obj[2] = {nullptr, nullptr};
+    hipEvent_t ev_obj0[2] = {nullptr, nullptr};
+    int obj_seq[2] = {0, 0};
+    float obj_ms = 0.f;
+    int32_t obj_frame = 0;
+    std::vector<float> obj;
 };
 
 namespace {
@@ -279,6 +290,9 @@ void rbs_tracker_destroy(rbs_tracker* t)
         if (t->h_map[k]) (void)hipHostFree(t->h_map[k]);
         if (t->ev_map[k]) (void)hipEventDestroy(t->ev_map[k]);
         if (t->ev_map0[k]) (void)hipEventDestroy(t->ev_map0[k]);
+        if (t->h_obj[k]) (void)hipHostFree(t->h_obj[k]);
+        if (t->ev_obj[k]) (void)hipEventDestroy(t->ev_obj[k]);
+        if (t->ev_obj0[k]) (void)hipEventDestroy(t->ev_obj0[k]);
     }
     delete t;
 }
@@ -292,6 +306,7 @@ int32_t rbs_tracker_initialize(rbs_tracker* t, const double* default_state)
     t->poisoned = false;
     t->post_valid = false;
     t->map_valid = false;
+    t->obj_valid = false;
     if (!t->reps.empty()) {
         for (rbs_tracker* r : t->reps)
             if (int32_t rc = rbs_tracker_initialize(r, default_state)) { t->s->err = r->s->err; return rc; }
@@ -566,6 +581,16 @@ static int32_t tracker_submit_impl(rbs_tracker* t, const float* frame, const dou
         RBT_HIP(t, hipEventRecord(t->ev_map[slot], s));
         t->map_seq[slot] = (int)(T.frame + 1);
     }
+    if (t->obj_on) {
+        // the object map of the same population over the poses the frame's last sampling block evaluated: member i is a copy of
+        // particle T.idx[i] of that block (gather_one: idx2[j] = idx[parent], idx being the identity behind the last block's
+        // weights), and row s of T.poses holds every body's pose slot s was evaluated with (propagate_body writes all of them
+        // in every block).  The next frame's transition overwrites T.poses behind these launches in stream order.
+        RBT_HIP(t, hipEventRecord(t->ev_obj0[slot], s));
+        if (int32_t rc = objmap::enqueue(h, T.poses, T.n, T.idx, T.logw, T.n, t->h_obj_dev[slot])) { t->err = h->err; return rc; }
+        RBT_HIP(t, hipEventRecord(t->ev_obj[slot], s));
+        t->obj_seq[slot] = (int)(T.frame + 1);
+    }
     std::swap(T.part_old, T.part_new);   // this frame's particles are the next frame's old ones
     // (the estimate and the flags were stored into h_state[slot] / h_flags[slot] by the kernel that
     // finished them: no copies behind the last kernel)
@@ -640,6 +665,13 @@ int32_t rbs_tracker_result(rbs_tracker* t, double* out_state, int32_t* out_resam
             t->map_frame = t->map_seq[slot];
             if (hipEventElapsedTime(&t->map_ms, t->ev_map0[slot], t->ev_map[slot]) != hipSuccess) { (void)hipGetLastError(); t->map_ms = 0.f; }
             t->map_valid = true;
+        }
+        if (t->obj_on) {   // ... and the object map behind it
+            RBT_HIP(t, hipEventSynchronize(t->ev_obj[slot]));
+            std::memcpy(t->obj.data(), t->h_obj[slot], sizeof(float) * t->obj.size());
+            t->obj_frame = t->obj_seq[slot];
+            if (hipEventElapsedTime(&t->obj_ms, t->ev_obj0[slot], t->ev_obj[slot]) != hipSuccess) { (void)hipGetLastError(); t->obj_ms = 0.f; }
+            t->obj_valid = true;
         }
     }
     std::memcpy(out_state, r->h_state[slot], sizeof(double) * D);
@@ -829,6 +861,85 @@ int32_t rbs_tracker_occlusion_map_ms(rbs_tracker* t, float* ms)
     if (!ms) return tfail(t, RBS_ERR_INVALID_ARGUMENT, "tracker_occlusion_map_ms: null output");
     if (!t->map_on || !t->map_valid) return tfail(t, RBS_ERR_INVALID_ARGUMENT, "tracker_occlusion_map_ms: no map has been handed out");
     *ms = t->map_ms;
+    return RBS_OK;
+}
+
+int32_t rbs_tracker_set_object_map(rbs_tracker* t, int32_t enable)
+{
+    if (!t) return RBS_ERR_INVALID_ARGUMENT;
+    if (!t->reps.empty() || !t->s->shards.empty())
+        return tfail(t, RBS_ERR_UNSUPPORTED, "tracker_set_object_map: single-device trackers only");
+    if (t->submitted != t->collected)
+        return tfail(t, RBS_ERR_INVALID_ARGUMENT, "tracker_set_object_map: frames are in flight (call rbs_tracker_result)");
+    if (enable && !t->obj_ready) {
+        // every buffer is made once, each only where an earlier attempt that failed half-way has not left it; the map is
+        // switched on only when all of them exist
+        rbs_handle* h = t->s;
+        if (const char* why = objmap::refuse_handle(h)) return tfail(t, RBS_ERR_UNSUPPORTED, fmt("tracker_set_object_map: %s", why));
+        RBT_HIP(t, hipSetDevice(h->device));
+        if (int32_t rc = objmap::ensure(h, t->T.n, t->T.n)) { t->err = h->err; return rc; }
+        const size_t floats = (size_t)(h->n_bodies + 2) * (size_t)h->npx;
+        t->obj.assign(floats, 0.f);
+        for (int k = 0; k < 2; ++k) {
+            if (!t->h_obj[k]) RBT_HIP(t, hipHostMalloc(&t->h_obj[k], sizeof(float) * floats, hipHostMallocDefault));
+            if (!t->h_obj_dev[k]) RBT_HIP(t, hipHostGetDevicePointer(reinterpret_cast<void**>(&t->h_obj_dev[k]), t->h_obj[k], 0));
+            if (!t->ev_obj[k]) RBT_HIP(t, hipEventCreate(&t->ev_obj[k]));
+            if (!t->ev_obj0[k]) RBT_HIP(t, hipEventCreate(&t->ev_obj0[k]));
+        }
+        t->obj_ready = true;
+    }
+    t->obj_on = enable != 0;
+    t->obj_valid = false;
+    return RBS_OK;
+}
+
+int32_t rbs_tracker_object_map(rbs_tracker* t, int32_t* frame, float* cover, float* depth, float* var)
+{
+    if (!t) return RBS_ERR_INVALID_ARGUMENT;
+    if (t->poisoned || t->s->poisoned)
+        return tfail(t, RBS_ERR_HIP, "tracker_object_map: an earlier frame failed half-way (" + (t->s->poisoned ? t->s->poison_msg : t->err) +
+                                         "): call rbs_tracker_initialize");
+    if (!t->obj_on) return tfail(t, RBS_ERR_INVALID_ARGUMENT, "tracker_object_map: the map is off (rbs_tracker_set_object_map)");
+    if (!t->obj_valid) return tfail(t, RBS_ERR_INVALID_ARGUMENT, "tracker_object_map: no frame has been handed out since rbs_tracker_initialize");
+    const size_t npx = (size_t)t->s->npx, B = (size_t)t->s->n_bodies;
+    if (frame) *frame = t->obj_frame;
+    if (cover) std::memcpy(cover, t->obj.data(), sizeof(float) * B * npx);
+    if (depth) std::memcpy(depth, t->obj.data() + B * npx, sizeof(float) * npx);
+    if (var) std::memcpy(var, t->obj.data() + (B + 1) * npx, sizeof(float) * npx);
+    return RBS_OK;
+}
+
+int32_t rbs_tracker_object_map_ms(rbs_tracker* t, float* ms)
+{
+    if (!t) return RBS_ERR_INVALID_ARGUMENT;
+    if (!ms) return tfail(t, RBS_ERR_INVALID_ARGUMENT, "tracker_object_map_ms: null output");
+    if (!t->obj_on || !t->obj_valid) return tfail(t, RBS_ERR_INVALID_ARGUMENT, "tracker_object_map_ms: no map has been handed out");
+    *ms = t->obj_ms;
+    return RBS_OK;
+}
+
+int32_t rbs_tracker_poses(rbs_tracker* t, double* out)
+{
+    if (!t) return RBS_ERR_INVALID_ARGUMENT;
+    if (!out) return tfail(t, RBS_ERR_INVALID_ARGUMENT, "tracker_poses: null output");
+    if (!t->reps.empty() || !t->s->shards.empty())
+        return tfail(t, RBS_ERR_UNSUPPORTED, "tracker_poses: single-device trackers only");
+    if (t->poisoned || t->s->poisoned)
+        return tfail(t, RBS_ERR_HIP, "tracker_poses: an earlier frame failed half-way (" + (t->s->poisoned ? t->s->poison_msg : t->err) +
+                                         "): call rbs_tracker_initialize");
+    // (no snapshot is kept: a frame in flight has overwritten, or is overwriting, the rows the last result's population points at)
+    if (t->submitted != t->collected)
+        return tfail(t, RBS_ERR_INVALID_ARGUMENT, "tracker_poses: frames are in flight (call rbs_tracker_result)");
+    rbt::TrackerDev& T = t->T;
+    if (T.frame < 1) return tfail(t, RBS_ERR_INVALID_ARGUMENT, "tracker_poses: no frame has been tracked since rbs_tracker_initialize");
+    RBT_HIP(t, hipSetDevice(t->s->device));
+    RBT_HIP(t, hipStreamSynchronize(t->s->stream));
+    const size_t w = (size_t)T.parts * 12;
+    std::vector<double> rows((size_t)T.n * w);
+    std::vector<int> idx((size_t)T.n);
+    RBT_HIP(t, hipMemcpy(rows.data(), T.poses, sizeof(double) * rows.size(), hipMemcpyDeviceToHost));
+    RBT_HIP(t, hipMemcpy(idx.data(), T.idx, sizeof(int) * idx.size(), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < (size_t)T.n; ++i) std::memcpy(out + i * w, rows.data() + (size_t)idx[i] * w, sizeof(double) * w);
     return RBS_OK;
 }
 

@@ -65,6 +65,8 @@
 #include "rbsensor_contour.hip"
 // The occlusion map (rbs_occlusion_*): the population's mean plane read from the planes as stored, and its per-body summary.
 #include "rbsensor_occmap.hip"
+// The object map (rbs_object_*): per pixel and body what a population sees, the mean and variance of its depth, the segmentation.
+#include "rbsensor_objmap.hip"
 
 namespace {
 
@@ -141,6 +143,7 @@ void release(rbs_handle* h)
     (void)hipFree(h->d_render);
     assess_release(h);
     occmap_release(h);
+    objmap_release(h);
     if (h->up_stream) (void)hipStreamSynchronize(h->up_stream);
     for (int k = 0; k < 2; ++k) {
         if (h->h_frames[k]) (void)hipHostFree(h->h_frames[k]);
@@ -487,6 +490,7 @@ int32_t create_impl(const rbs_config* cfg, rbs_handle* h)
             RBS_HIP(h, hipFuncSetAttribute(kernels[k], hipFuncAttributeMaxDynamicSharedMemorySize, (int)rbs::smem_bytes(rbs::kTilePxBig, false, true)));
     }
     RBS_HIP(h, rbs::pose_planes_configure());
+    RBS_HIP(h, rbs::objmap_configure());
 
     {   // per-item partial sums: sized for the default tiling so no call ever allocates
         const size_t gmul = h->d_groups[0] ? rbs::kMaxGroups : 1;   // every group of bodies tiles its own rectangle

@@ -419,6 +419,81 @@ class RbSensor:
         out = np.array([[r.rendered, r.occluded, r.sum_q32] for r in rec[:n * self.n_bodies]], dtype=np.int64)
         return out.reshape(n, self.n_bodies, 3)
 
+    def object_map(self, poses, members=None, log_weights=None):
+        """The object map of a population (rbs_object_map; include/rbsensor_mi355x.h, "Object map"): poses
+        [m, n_bodies, 12], members [n] pose indices (None: the identity), log_weights [n] (None: uniform).  Returns
+        (cover [n_bodies, rows*cols], depth [rows*cols], var [rows*cols]) float32: per pixel and body the probability that
+        the body is what the camera sees there, the posterior mean (+inf: no surface) and variance of the rendered depth."""
+        p = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, self.n_bodies * 12)
+        idx = None if members is None else np.ascontiguousarray(members, dtype=np.int32).ravel()
+        n = p.shape[0] if idx is None else idx.size
+        lw = None if log_weights is None else np.ascontiguousarray(log_weights, dtype=np.float64).ravel()
+        if lw is not None and lw.size != n:
+            raise RbSensorError(_capi.RBS_ERR_INVALID_ARGUMENT, "log_weights must have one entry per member")
+        npx = self.rows * self.cols
+        cover = np.empty((self.n_bodies, npx), dtype=np.float32)
+        depth, var = np.empty(npx, dtype=np.float32), np.empty(npx, dtype=np.float32)
+        fp = C.POINTER(C.c_float)
+        self._check(self._lib.rbs_object_map(
+            self._h, p.ctypes.data_as(C.POINTER(C.c_double)), int(p.shape[0]),
+            None if idx is None else idx.ctypes.data_as(C.POINTER(C.c_int32)),
+            None if lw is None else lw.ctypes.data_as(C.POINTER(C.c_double)), int(n),
+            cover.ctypes.data_as(fp), depth.ctypes.data_as(fp), var.ctypes.data_as(fp)))
+        return cover, depth, var
+
+    def object_map_ms(self):
+        """Device time of the last object_map's kernels in milliseconds (rbs_object_map_ms)."""
+        ms = C.c_float()
+        self._check(self._lib.rbs_object_map_ms(self._h, C.byref(ms)))
+        return float(ms.value)
+
+    def object_map_info(self):
+        """Of the last object_map: dict(live, rect (x0, y0, x1, y1), tiles, groups, tile_px) (rbs_object_map_info)."""
+        v = (C.c_int32 * 8)()
+        self._check(self._lib.rbs_object_map_info(self._h, v))
+        return dict(live=int(v[0]), rect=tuple(int(x) for x in v[1:5]), tiles=int(v[5]), groups=int(v[6]), tile_px=int(v[7]))
+
+    @staticmethod
+    def object_segment_default_params():
+        """dict(min_cover, sigmas, depth_sigmas): rbs_object_segment_default_params."""
+        p = _capi.RbsObjectSegmentParams()
+        _capi.load().rbs_object_segment_default_params(C.byref(p))
+        return dict(min_cover=float(p.min_cover), sigmas=float(p.sigmas), depth_sigmas=float(p.depth_sigmas))
+
+    def object_segment(self, maps=None, params=None, capacity=None):
+        """The staged observation segmented against an object map (rbs_object_segment).  maps: (cover, depth, var) as
+        object_map returns them, None: the maps of the last object_map on this sensor, still on the device.  params: a dict
+        with any of min_cover, sigmas, depth_sigmas (None: the defaults).  capacity: points handed out at most (None: every
+        pixel).  Returns (labels int32 [rows*cols] -- the body or -1 --, counts int32 [n_bodies], pixel int32 [c],
+        xyz float32 [c, 3] camera coordinates, n_points): the labelled pixels in ascending pixel index, c =
+        min(n_points, capacity)."""
+        npx = self.rows * self.cols
+        q = _capi.RbsObjectSegmentParams()
+        self._lib.rbs_object_segment_default_params(C.byref(q))
+        for k, v in (params or {}).items():
+            if k not in ("min_cover", "sigmas", "depth_sigmas"):
+                raise RbSensorError(_capi.RBS_ERR_INVALID_ARGUMENT, "object_segment: unknown parameter %r" % (k,))
+            setattr(q, k, float(v))
+        cap = npx if capacity is None else int(capacity)
+        fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+        cp = dp_ = vp = None
+        if maps is not None:
+            cover = np.ascontiguousarray(maps[0], dtype=np.float32).ravel()
+            depth = np.ascontiguousarray(maps[1], dtype=np.float32).ravel()
+            var = np.ascontiguousarray(maps[2], dtype=np.float32).ravel()
+            if cover.size != self.n_bodies * npx or depth.size != npx or var.size != npx:
+                raise RbSensorError(_capi.RBS_ERR_INVALID_ARGUMENT, "object_segment: a map has the wrong size")
+            cp, dp_, vp = cover.ctypes.data_as(fp), depth.ctypes.data_as(fp), var.ctypes.data_as(fp)
+        labels = np.empty(npx, dtype=np.int32)
+        counts = np.empty(self.n_bodies, dtype=np.int32)
+        pixel = np.full(max(cap, 1), -1, dtype=np.int32)
+        xyz = np.full((max(cap, 1), 3), np.nan, dtype=np.float32)
+        n_points = C.c_int32()
+        self._check(self._lib.rbs_object_segment(self._h, C.byref(q), cp, dp_, vp, labels.ctypes.data_as(ip), counts.ctypes.data_as(ip),
+                                                 pixel.ctypes.data_as(ip), xyz.ctypes.data_as(fp), cap, C.byref(n_points)))
+        c = min(int(n_points.value), max(cap, 0))
+        return labels, counts, pixel[:c], xyz[:c], int(n_points.value)
+
     def shared_trail_state(self):
         """(active, rebases): has the handle switched to a shared background plane, how often has it re-based (rbsensor_mi355x.h)."""
         a, r = C.c_int32(0), C.c_int32(0)

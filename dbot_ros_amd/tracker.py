@@ -65,6 +65,28 @@ class OcclusionMap:
 
 
 @dataclass
+class ObjectMap:
+    """Where a particle tracker sees the object after a frame (include/rbsensor_mi355x.h, "Object map"): cover
+    [n_bodies, rows, cols] float32, the probability per body that it is what the camera sees at the pixel; depth
+    [rows, cols], the posterior mean of the rendered depth (+inf: no surface); var [rows, cols], its variance; frame:
+    frames tracked since initialize."""
+    cover: np.ndarray
+    depth: np.ndarray
+    var: np.ndarray
+    frame: int = 0
+
+
+@dataclass
+class Segmentation:
+    """A depth frame segmented against an ObjectMap (rbs_object_segment): labels [rows, cols] int32, the body or -1;
+    counts [n_bodies]; pixel [c] the labelled pixels in ascending index; xyz [c, 3] their points in camera coordinates."""
+    labels: np.ndarray
+    counts: np.ndarray
+    pixel: np.ndarray
+    xyz: np.ndarray
+
+
+@dataclass
 class BodyOcclusion:
     """One body's share of an occlusion map at a pose: pixels the body owns, those of them above the threshold, and the
     mean of the map over them (nan when the body owns no pixel)."""
@@ -94,6 +116,80 @@ def occlusion_map_of(planes_by_slot, log_weights, indices):
         term = W * np.asarray(planes_by_slot[int(s)], dtype=np.float32).ravel().astype(LD)
         acc = term if acc is None else acc + term
     return acc / S
+
+
+def object_map_of(planes, rects, members, log_weights):
+    """The rule of the object map in numpy -- the restatement the device kernels (csrc/rbsensor_objmap.hip) are tested
+    against, in np.longdouble.  planes [m, B, rows, cols] float32: body b of pose k alone (+inf: no surface), valid inside
+    rects [m, B, 4] (x0, y0, x1, y1); members [n] pose indices (None: the identity); log_weights [n] (None: uniform; -inf: no
+    contribution).  Returns (cover [B, npx], depth [npx], var [npx], a [npx], S) as longdouble, not rounded to float;
+    depth = +inf and var = 0 where a = 0."""
+    LD = np.longdouble
+    P = np.asarray(planes, dtype=np.float32)
+    if P.ndim != 4:
+        raise ValueError("object_map_of: planes must be [m, B, rows, cols]")
+    m, B, rows, cols = P.shape
+    npx = rows * cols
+    idx = np.arange(m) if members is None else np.asarray(members).astype(np.int64).ravel()
+    if log_weights is None:
+        e = np.ones(idx.size, dtype=LD)
+    else:
+        lw = np.asarray(log_weights, dtype=np.float64).ravel()
+        e = np.exp((lw - lw.max()).astype(LD))
+    S = e.sum()
+    R = np.asarray(rects).reshape(m, B, -1)
+    yy, xx = np.mgrid[0:rows, 0:cols]
+    c = np.zeros((B, rows, cols), dtype=LD)
+    s1 = np.zeros((rows, cols), dtype=LD)
+    s2 = np.zeros((rows, cols), dtype=LD)
+    for k in np.unique(idx):
+        W = e[idx == k].sum()
+        if not W > 0:
+            continue
+        best = np.full((rows, cols), np.inf, dtype=np.float32)
+        owner = np.full((rows, cols), -1, dtype=np.int64)
+        for b in range(B):   # ascending, strictly nearer: a tie stays with the lowest body
+            x0, y0, x1, y1 = (int(v) for v in R[k, b, :4])
+            inside = (xx >= x0) & (xx < x1) & (yy >= y0) & (yy < y1)
+            nearer = inside & (P[k, b] < best)
+            best = np.where(nearer, P[k, b], best)
+            owner = np.where(nearer, b, owner)
+        d = np.where(owner >= 0, best, np.float32(0)).astype(LD)
+        for b in range(B):
+            c[b] += np.where(owner == b, W, LD(0))
+        s1 += np.where(owner >= 0, W * d, LD(0))
+        s2 += np.where(owner >= 0, W * (d * d), LD(0))
+    a = c.sum(axis=0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mu = np.where(a > 0, s1 / np.where(a > 0, a, 1), LD(np.inf))
+        var = np.where(a > 0, np.maximum(s2 / np.where(a > 0, a, 1) - np.where(a > 0, mu, 0) ** 2, 0), LD(0))
+    return (c / S).reshape(B, npx), mu.reshape(npx), var.reshape(npx), a.reshape(npx), S
+
+
+def segment_of(cover, depth, var, y, K, model_sigma, sigma_factor, min_cover=0.5, sigmas=3.0, depth_sigmas=3.0):
+    """The segmentation rule in numpy (binary64, exactly the device's operations): cover [B, rows, cols], depth, var and the
+    observation y [rows, cols] float32; K the 3 x 3 camera matrix.  Returns (labels int32 [rows*cols], counts [B],
+    pixel int32 [c], xyz float32 [c, 3])."""
+    cov = np.asarray(cover, dtype=np.float32)
+    B, rows, cols = cov.shape
+    D = np.asarray(depth, dtype=np.float32).reshape(rows, cols).astype(np.float64)
+    v = np.asarray(var, dtype=np.float32).reshape(rows, cols).astype(np.float64)
+    yf = np.asarray(y, dtype=np.float32).reshape(rows, cols)
+    best = np.argmax(cov, axis=0)          # (the first maximum: a tie stays with the lowest body)
+    top = np.take_along_axis(cov, best[None], 0)[0].astype(np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        tau = float(sigmas) * (float(model_sigma) + float(sigma_factor) * (D * D))
+        ex = np.maximum(0.0, np.abs(yf.astype(np.float64) - D) - tau)
+        ok = (top >= float(min_cover)) & np.isfinite(yf) & np.isfinite(D) & (ex * ex <= (float(depth_sigmas) * float(depth_sigmas)) * v)
+    labels = np.where(ok, best, -1).astype(np.int32).ravel()
+    counts = np.array([(labels == b).sum() for b in range(B)], dtype=np.int32)
+    pixel = np.nonzero(labels >= 0)[0].astype(np.int32)
+    K = np.asarray(K, dtype=np.float64).reshape(3, 3)
+    z = yf.ravel()[pixel]
+    x, yy = (pixel % cols).astype(np.float64), (pixel // cols).astype(np.float64)
+    X = ((x - K[0, 2]) / K[0, 0] * z.astype(np.float64)).astype(np.float32)
+    Y = ((yy - K[1, 2]) / K[1, 1] * z.astype(np.float64)).astype(np.float32)
+    return labels, counts, pixel, np.stack([X, Y, z], axis=-1).astype(np.float32).reshape(-1, 3)
 
 
 def object_frame_jacobian(R, c):
@@ -326,6 +422,28 @@ class ParticleTracker:
         return [BodyOcclusion(rendered=int(r), occluded=int(o), mean=float(q) / 2.0 ** 32 / int(r) if r else float("nan"))
                 for r, o, q in rec]
 
+    # -- where the filter sees the object ---------------------------------------------------------
+    def poses(self):
+        """[n, parts, 12]: the absolute pose of every member of the population the last frame left behind."""
+        if self._frames == 0:
+            raise ValueError("poses: no frame has been tracked since initialize")
+        return self.absolute_poses(self.particles)
+
+    def object_map(self):
+        """ObjectMap of the population the last frame left behind: sensor.object_map over poses() with this tracker's own
+        weights."""
+        cover, depth, var = self.sensor.object_map(self.poses(), None, self.log_weights)
+        r, c = self.sensor.rows, self.sensor.cols
+        return ObjectMap(cover=cover.reshape(-1, r, c), depth=depth.reshape(r, c), var=var.reshape(r, c), frame=self._frames)
+
+    def segment(self, params=None, object_map=None):
+        """Segmentation of the sensor's current observation against `object_map` (None: self.object_map())
+        (sensor.object_segment; params: a dict with any of min_cover, sigmas, depth_sigmas).  The observation is the frame
+        handed over last: with frames in flight that is a later frame than the map's, so segment frame by frame."""
+        m = self.object_map() if object_map is None else object_map
+        labels, counts, pixel, xyz, _ = self.sensor.object_segment((m.cover, m.depth, m.var), params)
+        return Segmentation(labels=labels.reshape(self.sensor.rows, self.sensor.cols), counts=counts, pixel=pixel, xyz=xyz)
+
     # -- the last estimate judged against its frame (dbot_ros_amd/assess.py) -------------------
     _in_flight = 0   # frames submitted and not yet collected (the device trackers' submit / result)
 
@@ -362,7 +480,7 @@ class DeviceParticleTracker(ParticleTracker):
     from this object's numpy Generator exactly as in the host tracker."""
 
     def __init__(self, transition, sensor, object_model, params, rng=None, device_rng=False, seed=0, posterior=False,
-                 occlusion_map=False):
+                 occlusion_map=False, object_map=False):
         import ctypes as C
         from . import _capi
         super().__init__(transition, sensor, object_model, params, rng)
@@ -384,6 +502,8 @@ class DeviceParticleTracker(ParticleTracker):
             self.set_posterior(True)
         if occlusion_map:
             self.set_occlusion_map(True)
+        if object_map:
+            self.set_object_map(True)
 
     def set_posterior(self, enable):
         """Switch the device's posterior report on or off (rbs_tracker_set_posterior; refused with frames in flight)."""
@@ -425,6 +545,36 @@ class DeviceParticleTracker(ParticleTracker):
         ms = self._C.c_float()
         self.sensor._check(self._lib.rbs_tracker_occlusion_map_ms(self._t, self._C.byref(ms)))
         return float(ms.value)
+
+    def set_object_map(self, enable):
+        """Switch the device's object map on or off (rbs_tracker_set_object_map; refused with frames in flight)."""
+        self.sensor._check(self._lib.rbs_tracker_set_object_map(self._t, 1 if enable else 0))
+
+    def object_map(self):
+        """The ObjectMap of the frame most recently handed out by track() / result() (rbs_tracker_object_map), reduced on
+        the device; needs object_map=True (or set_object_map(True)) -- an RbSensorError otherwise."""
+        C = self._C
+        r, c = self.sensor.rows, self.sensor.cols
+        frame = C.c_int32()
+        cover = np.empty((self.parts, r, c), dtype=np.float32)
+        depth, var = np.empty((r, c), dtype=np.float32), np.empty((r, c), dtype=np.float32)
+        fp = C.POINTER(C.c_float)
+        self.sensor._check(self._lib.rbs_tracker_object_map(self._t, C.byref(frame), cover.ctypes.data_as(fp), depth.ctypes.data_as(fp),
+                                                            var.ctypes.data_as(fp)))
+        return ObjectMap(cover=cover, depth=depth, var=var, frame=int(frame.value))
+
+    def object_map_ms(self):
+        """Device time of the last object map's kernels in milliseconds (rbs_tracker_object_map_ms)."""
+        ms = self._C.c_float()
+        self.sensor._check(self._lib.rbs_tracker_object_map_ms(self._t, self._C.byref(ms)))
+        return float(ms.value)
+
+    def poses(self):
+        """[n, parts, 12]: the absolute pose of every member of the population get_state() returns (rbs_tracker_poses;
+        refused with frames in flight)."""
+        out = np.empty((self.n, self.parts, 12))
+        self.sensor._check(self._lib.rbs_tracker_poses(self._t, out.ctypes.data_as(self._C.POINTER(self._C.c_double))))
+        return out
 
     def close(self):
         if getattr(self, "_t", None) is not None and self._t.value:

@@ -290,6 +290,54 @@ public:
         return out;
     }
 
+    /// The object map of a population (rbs_object_map; rbsensor_mi355x.h, "Object map"): cover [n_bodies][rows*cols], the
+    /// probability per body that it is what the camera sees at the pixel; depth [rows*cols], the posterior mean of the rendered
+    /// depth (+inf: no surface); var, its variance.
+    struct ObjectMap {
+        std::vector<float> cover, depth, var;
+        int frame = 0;   ///< a tracker's map: frames tracked since initialize()
+    };
+    /// poses: [m][n_bodies][12] absolute poses (row-major R, then t), flat; members: pose index per member, empty: the
+    /// identity; log_weights: empty: uniform.  Reduced on the device; nothing of the sensor changes.
+    ObjectMap object_map(const RealArray& poses, const IntArray& members = IntArray(), const RealArray& log_weights = RealArray())
+    {
+        const size_t per = static_cast<size_t>(n_bodies_) * 12;
+        if (poses.empty() || poses.size() % per) throw std::runtime_error("RbSensor::object_map: poses must hold m x n_bodies x 12 values");
+        const size_t m = poses.size() / per, n = members.empty() ? m : members.size();
+        if (!log_weights.empty() && log_weights.size() != n)
+            throw std::runtime_error("RbSensor::object_map: log_weights.size() != the number of members");
+        ObjectMap out;
+        out.cover.resize(pixels_ * static_cast<size_t>(n_bodies_));
+        out.depth.resize(pixels_);
+        out.var.resize(pixels_);
+        check(rbs_object_map(handle_, poses.data(), static_cast<int32_t>(m), members.empty() ? nullptr : members.data(),
+                             log_weights.empty() ? nullptr : log_weights.data(), static_cast<int32_t>(n), out.cover.data(), out.depth.data(),
+                             out.var.data()));
+        return out;
+    }
+    /// The staged observation segmented against a map (rbs_object_segment): labels [rows*cols], the body or -1; counts
+    /// [n_bodies]; the labelled pixels in ascending index and their points (x, y, z per pixel) in camera coordinates.
+    struct Segmentation {
+        std::vector<int32_t> labels, counts, pixel;
+        std::vector<float> xyz;
+    };
+    /// map: nullptr = the maps of the last object_map() on this sensor, still on the device; params: nullptr = the defaults.
+    Segmentation object_segment(const ObjectMap* map = nullptr, const rbs_object_segment_params* params = nullptr)
+    {
+        Segmentation s;
+        s.labels.resize(pixels_);
+        s.counts.resize(static_cast<size_t>(n_bodies_));
+        s.pixel.resize(pixels_);
+        s.xyz.resize(pixels_ * 3);
+        int32_t n_points = 0;
+        check(rbs_object_segment(handle_, params, map ? map->cover.data() : nullptr, map ? map->depth.data() : nullptr,
+                                 map ? map->var.data() : nullptr, s.labels.data(), s.counts.data(), s.pixel.data(), s.xyz.data(),
+                                 static_cast<int32_t>(pixels_), &n_points));
+        s.pixel.resize(static_cast<size_t>(n_points));
+        s.xyz.resize(static_cast<size_t>(n_points) * 3);
+        return s;
+    }
+
     /// deltas: state deltas around integrated_poses(); indices: occlusion slot each particle
     /// inherits from, set to identity when update is true.  Returns log-likelihoods.
     RealArray loglikes(const StateArray& deltas, IntArray& indices, const bool& update = false)
@@ -406,7 +454,7 @@ public:
                     const rbs_tracker_params& tp, bool center_object_frame, Real moving_average_update_rate,
                     uint64_t seed)
         : sensor_(sensor), om_(om), center_(center_object_frame), rate_(moving_average_update_rate), seed_(seed),
-          parts_(om->count_parts())
+          parts_(om->count_parts()), n_particles_(tp.n_particles)
     {
         if (rbs_tracker_create(sensor_->handle(), &tp, &t_) != RBS_OK)
             throw std::runtime_error(std::string("ParticleTracker: ") + rbs_last_error(sensor_->handle()));
@@ -499,6 +547,28 @@ public:
         m.frame = frame;
         return m;
     }
+    /// The object map of the frame most recently handed out by track() / result() (rbs_tracker_object_map): which pixels the
+    /// filter sees the object at, and at what depth.  Off by default; refused while frames are in flight.
+    typedef typename RbSensor<State>::ObjectMap ObjectMap;
+    void enable_object_map(bool on = true) { check(rbs_tracker_set_object_map(t_, on ? 1 : 0)); }
+    ObjectMap object_map() const
+    {
+        ObjectMap m;
+        m.cover.resize(sensor_->pixels() * static_cast<size_t>(parts_));
+        m.depth.resize(sensor_->pixels());
+        m.var.resize(sensor_->pixels());
+        int32_t frame = 0;
+        check(rbs_tracker_object_map(t_, &frame, m.cover.data(), m.depth.data(), m.var.data()));
+        m.frame = frame;
+        return m;
+    }
+    /// The absolute pose [n][parts][12] of every particle of the last frame's population (rbs_tracker_poses).
+    std::vector<Real> poses() const
+    {
+        std::vector<Real> out(static_cast<size_t>(n_particles_) * static_cast<size_t>(parts_) * 12);
+        check(rbs_tracker_poses(t_, out.data()));
+        return out;
+    }
 
     /// Per body the 6 x 6 covariance (row-major, [parts][36]) of the PUBLISHED pose -- position, rotation; camera frame,
     /// left perturbation.  With center_object_frame the published position is t - R c, to first order
@@ -576,6 +646,7 @@ private:
     Real rate_;
     uint64_t seed_;
     int parts_;
+    int n_particles_;
     rbs_tracker* t_ = nullptr;
     State average_{1};
     State model_{1};   // the last estimate in model coordinates (pose_covariance's rotation)

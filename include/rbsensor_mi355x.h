@@ -1198,6 +1198,105 @@ typedef struct rbs_occlusion_body {   /* 32 bytes */
 } rbs_occlusion_body;
 int32_t rbs_occlusion_bodies(rbs_handle* h, const float* map, const double* poses, int32_t n, double threshold, rbs_occlusion_body* out);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Object map (csrc/rbsensor_objmap.hip): which pixels a weighted particle population sees the object
+ * at, and at what depth -- per pixel and body the probability that the body is what the camera sees there, and the
+ * posterior mean and variance of the rendered depth -- reduced on the device without a plane per member; and the
+ * segmentation of the staged observation against such a map.
+ *
+ * Population.  n members; member i has a pose index k_i into poses[m][n_objects][12] (row-major R, then t, as for
+ * rbs_assess_poses) and a log-weight lw_i.  e_i, S, m = max lw and the treatment of -inf are exactly the occlusion map's
+ * (above), and so is W_k = sum over { i : k_i = k } of e_i in ascending i (the same kernels).  A pose is live when W_k > 0.
+ * Planes and owner.  d_{k,b}(p): body b of pose k alone, the depth rbs_assess_get_plane hands out inside the body's
+ * rectangle, +inf where there is no surface.  o_k(p), d_k(p): the assessor's owner rule -- the nearest body, a tie with the
+ * lowest, -1: none.
+ * Outputs (binary64, no contraction into fused operations, every output float rounded once):
+ *   c_b(p) = sum_k W_k [o_k(p) = b]     a(p) = c_0(p) + c_1(p) + ...  (ascending b)   = sum_k W_k [o_k(p) >= 0]
+ *   s1(p) = sum_k W_k d_k(p)            s2(p) = sum_k W_k (d_k(p) d_k(p))               (over the k with o_k(p) >= 0)
+ *   cover[b][p] = (float)(c_b / S)   depth[p] = (float)(s1 / a)   var[p] = (float)max(0, s2 / a - (s1 / a)(s1 / a))
+ *   a = 0:  depth[p] = +inf (rbs_render_depth's "no surface"),  var[p] = 0.
+ * Order.  U = the union of the live poses' body rectangles, cut from its corner into tiles of 32 x 32 pixels (n_objects <= 4)
+ * or 32 x 16 (5 .. 8).  The live poses in ascending k are cut into G contiguous parts, part g = [L g / G, L (g + 1) / G) of
+ * the L live poses, with
+ *   G = max(1, min(32, ceil(L / 8), floor(C / (tiles(U) tile_px (n_objects + 2)))))
+ * C being the doubles of partial sums the handle keeps (below).  Every sum above is taken per part in ascending k and the
+ * parts are added in ascending g: the order is fixed by n, the indices and the poses' rectangles alone.  No floating-point
+ * atomics: two runs give the same bits, and so do a tracker frame by frame and with look-ahead.  A pixel no live pose covers
+ * reads 0, +inf, 0 bit for bit.
+ * Nothing of the sensor is written: planes, windows, clocks, staged poses, the observation and the assessor's inspection
+ * state stay as they were.
+ * Limits.  n_objects <= 8 (more: RBS_ERR_UNSUPPORTED).  Device memory, allocated at first use, grow-only, freed by
+ * rbs_destroy: per member 20 bytes, per pose 16 n_objects + 12 + 96 n_objects (its rectangles, list entry, weight and the
+ * caller's pose), the maps (n_objects + 2) x 4 bytes per pixel, the segmentation's 20 bytes per pixel, and the partial sums:
+ * C = max(one part over the whole frame, min(32 parts over the whole frame, 4 Mi doubles = 32 MiB)), one part over the whole
+ * frame being tiles(frame) tile_px (n_objects + 2) doubles -- 7.4 MB at 640 x 480 and one body.  Nothing grows with
+ * n x rows x cols.
+ *
+ * rbs_object_map: host pointers, synchronous.  poses [n_poses][n_objects][12]; members [n] in [0, n_poses), repeats allowed,
+ * NULL = the identity (then n must equal n_poses); log_weights [n], NULL = uniform; cover [n_objects][rows*cols], depth and
+ * var [rows*cols], each may be NULL.  Refusals, in this order: a null poses pointer, n or n_poses < 1 (or n != n_poses
+ * without members): RBS_ERR_INVALID_ARGUMENT; a handle over several devices or attached to other ranks, then
+ * n_objects > 8: RBS_ERR_UNSUPPORTED; a pose index out of range, a log-weight that is NaN or +inf, every log-weight -inf, a
+ * pose entry that is not finite: RBS_ERR_INVALID_ARGUMENT; a poisoned handle: its own error.
+ * rbs_object_map_ms: device time of the last rbs_object_map's kernels, first launch to last (HIP events), in ms.
+ * rbs_object_map_info: of the last rbs_object_map: [0] live poses L, [1..4] U (x0, y0, x1, y1), [5] tiles(U), [6] G,
+ * [7] tile_px.  Both: RBS_ERR_INVALID_ARGUMENT before the first map, and after an rbs_object_segment with host maps has
+ * replaced that map's images on the device. */
+int32_t rbs_object_map(rbs_handle* h, const double* poses, int32_t n_poses, const int32_t* members, const double* log_weights, int32_t n,
+                       float* cover, float* depth, float* var);
+int32_t rbs_object_map_ms(rbs_handle* h, float* ms);
+int32_t rbs_object_map_info(rbs_handle* h, int32_t* out8);
+
+/* Segmentation of the staged observation y against a map.  With D = depth[p], tau = sigmas (model_sigma + sigma_factor D D)
+ * (the assessor's tau, from the handle's Kinect parameters), all in binary64:
+ *   b* = argmax_b cover[b][p], a tie with the lowest b;
+ *   label[p] = b*  when  cover[b*][p] >= min_cover  and  y(p) is finite  and  D is finite (there is a surface)  and
+ *                        max(0, |y - D| - tau)^2 <= depth_sigmas^2 var[p];         -1 otherwise.
+ * No square root is taken: the labels are an exact function of the float maps.  counts[b] = pixels labelled b.  The
+ * labelled pixels in ascending pixel index c = 0, 1, ...: pixel[c] = y * cols + x, xyz[c] = (X, Y, Z) in camera
+ * coordinates on integer sample coordinates,  Z = y(p),  X = (float)(((double)x - cx) / fx * (double)Z),  Y likewise.
+ * An integer scan, no atomics: order and values are exact.
+ * cover / depth / var: host maps as rbs_object_map returns them; cover == NULL: the maps of the last rbs_object_map on this
+ * handle, still on the device (RBS_ERR_INVALID_ARGUMENT when there are none, or when a call with host maps has replaced
+ * them).  labels [rows*cols], counts [n_objects], pixel [capacity], xyz [capacity][3]; labels, counts and n_points may be
+ * NULL, pixel and xyz when capacity == 0.  *n_points is always the full count; when it exceeds capacity the first `capacity`
+ * points are written, nothing past them, and the call still returns RBS_OK -- compare *n_points with capacity.
+ * Refusals, in this order: bad parameters (min_cover outside [0, 1], sigmas not finite and > 0, depth_sigmas not finite
+ * and >= 0), capacity < 0 or > 0 without its outputs, cover without depth and var: RBS_ERR_INVALID_ARGUMENT; several devices,
+ * n_objects > 8: RBS_ERR_UNSUPPORTED; no observation handed to the handle since rbs_create, cover == NULL without maps on the
+ * device: RBS_ERR_INVALID_ARGUMENT; a poisoned handle: its own error. */
+typedef struct rbs_object_segment_params {   /* 32 bytes */
+    double min_cover;       /* 0.5 */
+    double sigmas;          /* rbs_assess_default_params' sigmas */
+    double depth_sigmas;    /* 3 */
+    double reserved;        /* 0 */
+} rbs_object_segment_params;
+void rbs_object_segment_default_params(rbs_object_segment_params* p);
+int32_t rbs_object_segment(rbs_handle* h, const rbs_object_segment_params* params, const float* cover, const float* depth, const float* var,
+                           int32_t* labels, int32_t* counts, int32_t* pixel, float* xyz, int32_t capacity, int32_t* n_points);
+
+/* The device tracker's object map (opt-in), point for point on the pattern of rbs_tracker_set_occlusion_map: with it on,
+ * every frame ends with the object map of the population rbs_tracker_get returns after that frame, over the poses
+ * rbs_tracker_poses returns, its kernels launched last in the frame's chain -- behind the posterior report's and the
+ * occlusion map's when those are on; the three are independent -- into a pinned buffer per frame in flight.
+ * rbs_tracker_set_object_map: enable != 0 switches it on (allocating its buffers the first time), 0 off.  Off -- the
+ * default -- a frame enqueues exactly what it did before.  Refusals in this order: a tracker over several devices:
+ * RBS_ERR_UNSUPPORTED; frames in flight: RBS_ERR_INVALID_ARGUMENT; n_objects > 8: RBS_ERR_UNSUPPORTED.  The filter is not
+ * touched: estimates and particles are bit for bit those of a tracker with the map off.
+ * rbs_tracker_object_map: the maps of the frame most recently handed out by rbs_tracker_result / rbs_tracker_track*; frame
+ * and every output may be NULL.  A poisoned tracker's error first; then RBS_ERR_INVALID_ARGUMENT while the map is off, before
+ * the first frame, and after rbs_tracker_initialize until the next result.
+ * rbs_tracker_object_map_ms: device time of that map's kernels; RBS_ERR_INVALID_ARGUMENT wherever there is no map.
+ * rbs_tracker_poses: out [n][n_objects][12], the absolute pose of every member of the population rbs_tracker_get returns:
+ * member i's pose is the one the frame's last sampling block evaluated for its parent.  No snapshot is kept -- the next
+ * frame's transition overwrites those rows -- so the call refuses where rbs_tracker_get would hand out another frame's
+ * population: RBS_ERR_INVALID_ARGUMENT with frames in flight, and before the first frame; several devices:
+ * RBS_ERR_UNSUPPORTED. */
+int32_t rbs_tracker_set_object_map(rbs_tracker* t, int32_t enable);
+int32_t rbs_tracker_object_map(rbs_tracker* t, int32_t* frame, float* cover, float* depth, float* var);
+int32_t rbs_tracker_object_map_ms(rbs_tracker* t, float* ms);
+int32_t rbs_tracker_poses(rbs_tracker* t, double* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,7 +12,11 @@ run-to-run spread a difference has to exceed) and the report's kernels' device t
 
     tracker_fps.py [COUNTS [MESHES]] --occlusion-map [--never-resample] [--repeats R]
 the same measurement for the device tracker's occlusion map (rbs_tracker_set_occlusion_map); MESHES m1,m2,m3 is the
-three-body scene; --never-resample sets max_kl_divergence so large that nothing resamples and every slot stays live."""
+three-body scene; --never-resample sets max_kl_divergence so large that nothing resamples and every slot stays live.
+
+    tracker_fps.py [COUNTS [MESHES]] --object-map [--never-resample] [--repeats R]
+the same for the device tracker's object map (rbs_tracker_set_object_map), with the sensor's raster kernel time of the
+frame's likelihood call beside the map's (rbs_raster_kernel_ms: the kernel that draws the same poses)."""
 import json
 import os
 import sys
@@ -29,9 +33,9 @@ from dbot_ros_amd.tracker import (DeviceParticleTracker, ObjectTransitionBuilder
 
 
 def posterior_main(argv, product="posterior"):
-    """--posterior, --occlusion-map: see the module's docstring."""
+    """--posterior, --occlusion-map, --object-map: see the module's docstring."""
     repeats = 5
-    never = product == "occlusion_map" and "--never-resample" in argv
+    never = product != "posterior" and "--never-resample" in argv
     argv = [a for a in argv if a != "--never-resample"]
     if "--repeats" in argv:
         k = argv.index("--repeats")
@@ -61,8 +65,9 @@ def posterior_main(argv, product="posterior"):
             if never:
                 tp.max_kl_divergence = 1e30
             tr = DeviceParticleTracker(trans, s, om, tp, device_rng=True, seed=1)
-            switch, ms_of, last = ((tr.set_posterior, tr.posterior_ms, tr.posterior) if product == "posterior" else
-                                   (tr.set_occlusion_map, tr.occlusion_map_ms, tr.occlusion_map))
+            switch, ms_of, last = {"posterior": (tr.set_posterior, tr.posterior_ms, tr.posterior),
+                                   "occlusion_map": (tr.set_occlusion_map, tr.occlusion_map_ms, tr.occlusion_map),
+                                   "object_map": (tr.set_object_map, tr.object_map_ms, tr.object_map)}[product]
 
             def block(on, look_ahead, collect_ms=None):
                 """The 30 frames from a fresh initialize -> frames/s (the same sequence every time: device RNG, same seed)."""
@@ -95,12 +100,14 @@ def posterior_main(argv, product="posterior"):
                 for la in (False, True):
                     for on in (False, True):                  # alternating
                         fps[(on, la)].append(block(on, la))
-            what = "posterior report" if product == "posterior" else "occlusion map"
+            what = {"posterior": "posterior report", "occlusion_map": "occlusion map", "object_map": "object map"}[product]
             out = {"metric": "tracker FPS, %s off / on" % what, "evaluation_count": n, "objects": nb, "particles": max(1, n // nb),
                    "repeats": repeats, "unit": "frames/s", "resolution": [cols, rows],
                    product + "_kernels_device_ms": {"median": float(np.median(ms)), "min": float(np.min(ms)), "max": float(np.max(ms))}}
-            if product == "occlusion_map":
+            if product != "posterior":
                 out["resamplings"] = tr.n_resamplings
+            if product == "object_map":
+                out["raster_kernel_ms_last_call"] = float(s.raster_kernel_ms())
             for (on, la), v in fps.items():
                 out[("on" if on else "off") + ("_look_ahead" if la else "_frame_by_frame")] = {
                     "median": float(np.median(v)), "min": float(np.min(v)), "max": float(np.max(v))}
@@ -117,6 +124,9 @@ def main():
     if "--occlusion-map" in sys.argv:
         argv = [a for a in sys.argv[1:] if a != "--occlusion-map"]
         return posterior_main(argv, product="occlusion_map")
+    if "--object-map" in sys.argv:
+        argv = [a for a in sys.argv[1:] if a != "--object-map"]
+        return posterior_main(argv, product="object_map")
     counts = [int(x) for x in sys.argv[1].split(",")] if len(sys.argv) > 1 else [200, 2000, 20000]
     names = sys.argv[2].split(",") if len(sys.argv) > 2 else ["m1"]     # e.g. m1,m2,m3 = BASELINE config C2
     cols, rows, n_frames = 640, 480, 30
