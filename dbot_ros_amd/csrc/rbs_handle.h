@@ -227,8 +227,11 @@ struct rbs_handle {
     const int4* peer_win[rbs::kMaxDevices][2] = {};
     const int4* peer_reg[rbs::kMaxDevices][2] = {};
     void* peer_mapped[rbs::kMaxDevices][6] = {};    // what hipIpcCloseMemHandle gets back
-    void* d_peer_scratch = nullptr;                 // rbs_peer_resample: cdf [N] + 2 x [tiles] doubles + 2 x [n] ints
+    void* d_peer_scratch = nullptr;                 // rbs_peer_resample: cdf [N] + 2 x [tiles] + 1 doubles + 2 x [n] ints
     size_t peer_scratch_bytes = 0;
+    rbp::PeerPlan peer_last{};                      // ... its last call: the job and its views of the scratch block, the stream it went
+    hipStream_t peer_last_stream = nullptr;         //   to, whether peer_max_kernel ran (N = 0: no call yet; read by the test build's
+    bool peer_last_max = false;                     //   rbs_test_peer_scratch alone)
     const float* snap_occ[rbs::kMaxDevices] = {};   // group: every shard's CURRENT planes / windows as of the start
     const int4* snap_win[rbs::kMaxDevices] = {};    //   of the call being fanned out (shards flip buffers one by one)
     const int4* snap_reg[rbs::kMaxDevices] = {};

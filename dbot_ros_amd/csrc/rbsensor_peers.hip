@@ -42,6 +42,7 @@ struct PeerPlan {
     double* cdf;              // [N] scratch: cumulative weights WITHIN a tile of kTile particles (peer_weights_kernel)
     double* tile_max;         // [tiles] scratch: the largest log-likelihood of a tile (peer_max_kernel)
     double* tile_total;       // [tiles] scratch: the weight of a tile
+    double* max_all;          // [1] scratch: the largest log-likelihood of all (peer_weights_kernel, for peer_search_kernel's step back)
     int* mine;                // [n] scratch: this rank's children's parents (indices into ll_all)
     int* aux;                 // [n] scratch
     int32_t* parent_idx;      // [n]
@@ -118,17 +119,29 @@ __global__ __launch_bounds__(kThreads) void peer_weights_kernel(const PeerPlan Q
     if (i0 + 1 < Q.N) { const double l = Q.ll_all[i0 + 1]; w1 = l == l ? exp((l - m) / Q.temperature) : 0.0; }
     double tile_total;
     const double before = block_exscan(w0 + w1, 0.0, OpAdd(), shd, &tile_total);
-    if (i0 < Q.N)     Q.cdf[i0] = before + w0;
-    if (i0 + 1 < Q.N) Q.cdf[i0 + 1] = before + (w0 + w1);
+    // (two threads' partial sums are the same terms in two associations: where a weight is zero or absorbed by the sum before it, a
+    //  value can come out an ulp BELOW its predecessor.  The search wants them in order, so each is raised to the largest before it;
+    //  a maximum rounds nothing and has no order, so the result is still the same bits on every rank)
+    double c0 = before + w0, c1 = before + (w0 + w1), unused;
+    c0 = OpMax()(block_exscan(c1, 0.0, OpMax(), shd, &unused), c0);
+    c1 = OpMax()(c0, c1);
+    if (i0 < Q.N)     Q.cdf[i0] = c0;
+    if (i0 + 1 < Q.N) Q.cdf[i0 + 1] = c1;
     if (t == 0) Q.tile_total[blockIdx.x] = tile_total;
+    if (t == 0 && blockIdx.x == 0) *Q.max_all = m;
 }
 
 // This rank's children's parents, a child per thread over ceil(n / kThreads) blocks: each block scans the tiles' totals
 // in LDS (cdf value i = (weight of the tiles before i's + cumulative weight inside the tile) / total, formed where it
 // is read, so the cdf is never rewritten) and keeps kSamples evenly spaced cdf values there -- a search narrows to one
 // stretch of `stride` particles in LDS and only its last log2(stride) probes go to memory.  parent =
-// upper_bound(cdf, u), clamped (the last cdf value is 1 up to rounding).  (One block walking the cdf for all of the
-// rank's children was bound by its CU's load path: 190 us of 25 000 children with flat weights.)
+// upper_bound(cdf, u), clamped (the last cdf value is 1 up to rounding), and then stepped back to the last particle at or before it
+// that weighs anything.  The step matters at roundings only: the last cdf value and the total are the same sum in two associations,
+// so a uniform just below 1 can lie at or beyond it, and the clamp alone then hands the child to particle N - 1 whatever it weighs;
+// likewise the cdf is flat over a weightless particle only up to its last bit.  A contained particle (NaN) must never be a parent.
+// The test is the weights kernel's own expression on the gathered log-likelihoods, so every rank still takes the same step.
+// (One block walking the cdf for all of the rank's children was bound by its CU's load path: 190 us of 25 000 children with flat
+// weights.)
 __global__ __launch_bounds__(kThreads) void peer_search_kernel(const PeerPlan Q)
 {
     __shared__ double shd[kThreads / 64];
@@ -178,7 +191,18 @@ __global__ __launch_bounds__(kThreads) void peer_search_kernel(const PeerPlan Q)
         }
         p = lo;
     }
-    const int pc = min(p, N - 1);
+    int pc = min(p, N - 1);
+    {
+        const double m = *Q.max_all;
+        int q = pc;
+        while (q >= 0) {
+            if ((q & (kTile - 1)) == kTile - 1 && !(Q.tile_total[q >> kTileShift] > 0.0)) { q -= kTile; continue; }   // a whole tile of them
+            const double l = Q.ll_all[q];
+            if (l == l && exp((l - m) / Q.temperature) > 0.0) break;
+            --q;
+        }
+        if (q >= 0) pc = q;                                      // (nobody weighs anything: the search's answer stands)
+    }
     Q.mine[k] = pc;
     if (Q.parents_local) Q.parents_local[k] = pc;
 }

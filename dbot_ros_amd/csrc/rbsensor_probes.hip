@@ -20,6 +20,8 @@
 // rbs_test_findfg_* are the same for step 1b's four launch helpers: tests/test_gpu_find_foreground_kernels.py.
 // rbs_test_findr_* are the same for step 6b's launch helpers: tests/test_gpu_find_refinement_kernels.py.
 // rbs_test_findc_evidence is the gate's evidence kernel alone, over a sensor's geometry: tests/test_gpu_find_gate_kernels.py.
+// rbs_test_peer_scratch launches nothing: it hands back the scratch arrays the last rbs_peer_resample call on a handle left
+// behind (rbsensor_peers.hip's per-tile cumulative weights, maxima and totals): tests/test_gpu_peer_kernels.py.
 //
 // rbs_test_prep does the same for the rectangles kernel (rbsensor_kernels.hip prep_particles): it builds a DevParams from host
 // arrays -- no sensor handle, no mesh: the rectangle reads the vertices only -- and launches rbs_prep_kernel,
@@ -825,6 +827,24 @@ int32_t rbs_test_findc_evidence(rbs_handle* h, const rbs_find_gate* g, const flo
     B.fetch(rec, drec, rbf::kEvFields * K);
     B.fetch(cls, dcls, K);
     return B.status();
+}
+
+// ---- resampling across processes (rbsensor_peers.hip): tests/peer_probes.py, tests/test_gpu_peer_kernels.py
+// What the LAST rbs_peer_resample call on h left in the handle's scratch block, after its stream has drained: cdf [N] (cumulative
+// weights within each tile), tile_total [tiles], mine [n] -- and tile_max [tiles] where peer_max_kernel ran (large jobs only), else
+// the caller's array is left alone.  Returns 1 / 0 (RBS_OK): tile_max was / was not written; < 0: an error.  Nothing is launched.
+int32_t rbs_test_peer_scratch(rbs_handle* h, double* cdf, double* tile_max, double* tile_total, int32_t* mine)
+{
+    if (!h || !cdf || !tile_max || !tile_total || !mine || h->peer_last.N < 1 || !h->d_peer_scratch) return RBS_ERR_INVALID_ARGUMENT;
+    const rbp::PeerPlan& Q = h->peer_last;
+    const size_t N = (size_t)Q.N, tiles = (N + rbp::kTile - 1) / rbp::kTile;
+    if (hipSetDevice(h->device) != hipSuccess || hipStreamSynchronize(h->peer_last_stream) != hipSuccess) return RBS_ERR_HIP;
+    rbs::probe::Buffers B;   // (none of its own: the fetches and the status)
+    B.fetch(cdf, Q.cdf, N);
+    B.fetch(tile_total, Q.tile_total, tiles);
+    if (h->peer_last_max) B.fetch(tile_max, Q.tile_max, tiles);
+    B.fetch(mine, Q.mine, (size_t)Q.n);
+    return B.err == hipSuccess ? (h->peer_last_max ? 1 : 0) : RBS_ERR_HIP;
 }
 
 }  // extern "C"

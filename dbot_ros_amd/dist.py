@@ -305,6 +305,11 @@ def global_resample(ll_all, uniforms, temperature=1.0):
     c = torch.cumsum(w, 0)
     c = c / c[-1]
     p = torch.searchsorted(c, uniforms, right=True).clamp_(max=ll_all.numel() - 1)
+    # a child never inherits from a particle that weighs nothing (rbsensor_peers.hip peer_search_kernel): a parallel cumsum is flat
+    # over such a particle only up to its last bit, so step back to the last one at or before p that weighs anything
+    at = torch.arange(w.numel(), device=w.device)
+    last = torch.cummax(torch.where(w > 0, at, torch.full_like(at, -1)), 0).values[p]
+    p = torch.where(last >= 0, last, p)
     return torch.sort(p).values
 
 

@@ -97,7 +97,9 @@ def test_ipc_attach_refuses_mismatched_handles(gpu_lib):
 ])
 def test_peer_resample_matches_tensor_arithmetic(gpu_lib, world, n, min_share, temp, spread):
     """rbs_peer_resample (one call) against dist.global_resample + dist.plan_shard (the same step as tensor
-    arithmetic, here on the CPU): identical parents, identical plan and counts, for every rank of the job."""
+    arithmetic, here on the CPU): identical parents, identical plan and counts, for every rank of the job.
+    (torch.cumsum sums in another order than the kernels: identical parents hold because no random uniform comes within rounding
+    of a cumulative value.  The edges -- ties, tile and route boundaries, planted runs -- live in tests/test_gpu_peer_kernels.py.)"""
     from dbot_ros_amd import dist as rdist
     N = world * n
     rng = np.random.default_rng(world * 1000 + n)
