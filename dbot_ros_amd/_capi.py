@@ -61,7 +61,9 @@ EXPORTS = (
     "rbs_tracker_set_occlusion_map", "rbs_tracker_occlusion_map", "rbs_tracker_occlusion_map_ms",
     "rbs_object_map", "rbs_object_map_ms", "rbs_object_map_info", "rbs_object_segment_default_params", "rbs_object_segment",
     "rbs_tracker_set_object_map", "rbs_tracker_object_map", "rbs_tracker_object_map_ms", "rbs_tracker_poses",
+    "rbs_modes_default_params", "rbs_pose_modes", "rbs_tracker_set_modes", "rbs_tracker_modes", "rbs_tracker_modes_ms",
 )
+RBS_MODES_MAX = 8
 RBS_ASSESS_OUT_OF_VIEW, RBS_ASSESS_OCCLUDED, RBS_ASSESS_SUPPORTED, RBS_ASSESS_LOST = range(4)
 RBS_CONTOUR_NO_RIM, RBS_CONTOUR_UNDECIDED, RBS_CONTOUR_PRESENT, RBS_CONTOUR_ABSENT = range(4)
 RBS_FIND_SEEDS, RBS_FIND_COARSE, RBS_FIND_CANDIDATES, RBS_FIND_SURVIVORS, RBS_FIND_CHILDREN, RBS_FIND_RESULT = range(6)
@@ -84,6 +86,35 @@ class RbsTrackerPosteriorInfo(C.Structure):
         ("resampled", C.c_int32),
         ("frame", C.c_int32),
         ("ess", C.c_double),
+    ]
+
+
+class RbsModesParams(C.Structure):
+    _fields_ = [
+        ("h_t", C.c_double),
+        ("h_r", C.c_double),
+        ("separation", C.c_double),
+        ("k_max", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
+class RbsMode(C.Structure):
+    _fields_ = [
+        ("seed", C.c_int32),
+        ("reserved", C.c_int32),
+        ("density", C.c_double),
+        ("mass", C.c_double),
+        ("core_mass", C.c_double),
+        ("delta", C.c_double * 6),
+    ]
+
+
+class RbsBodyModes(C.Structure):
+    _fields_ = [
+        ("n_modes", C.c_int32),
+        ("reserved", C.c_int32),
+        ("mode", RbsMode * RBS_MODES_MAX),
     ]
 
 
@@ -410,6 +441,16 @@ def load():
     lib.rbs_tracker_posterior.argtypes = [H, C.POINTER(RbsTrackerPosteriorInfo), dp, dp]
     lib.rbs_tracker_posterior_ms.restype = C.c_int32
     lib.rbs_tracker_posterior_ms.argtypes = [H, fp]
+    lib.rbs_modes_default_params.restype = None
+    lib.rbs_modes_default_params.argtypes = [C.POINTER(RbsModesParams)]
+    lib.rbs_pose_modes.restype = C.c_int32
+    lib.rbs_pose_modes.argtypes = [H, dp, dp, C.c_int32, C.POINTER(RbsModesParams), C.POINTER(RbsBodyModes)]
+    lib.rbs_tracker_set_modes.restype = C.c_int32
+    lib.rbs_tracker_set_modes.argtypes = [H, C.POINTER(RbsModesParams)]
+    lib.rbs_tracker_modes.restype = C.c_int32
+    lib.rbs_tracker_modes.argtypes = [H, ip, C.POINTER(RbsBodyModes)]
+    lib.rbs_tracker_modes_ms.restype = C.c_int32
+    lib.rbs_tracker_modes_ms.argtypes = [H, fp]
     lib.rbs_gauss_create.restype = C.c_int32
     lib.rbs_gauss_create.argtypes = [H, C.POINTER(RbsGaussParams), C.POINTER(H)]
     lib.rbs_gauss_destroy.restype = None

@@ -249,6 +249,8 @@ struct rbs_handle {
     // ---- the object map (rbsensor_objmap.hip): its buffers, allocated by the first rbs_object_map / rbs_object_segment /
     // rbs_tracker_set_object_map
     struct rbs_objmap_state* objmap = nullptr;
+    // ---- the posterior modes (rbs_modes_api.h): its buffers, allocated by the first rbs_pose_modes
+    struct rbs_modes_state* modes = nullptr;
     long frames_handed = 0;     // frames handed over since rbs_create (rbs_object_segment refuses a handle that never saw one)
 };
 

@@ -44,6 +44,21 @@ struct rbs_tracker {
     float post_ms = 0.f;
     std::vector<double> post;
     int32_t post_i[4] = {0, 0, 0, 0};
+    // the posterior modes (rbs_tracker_set_modes, rbsensor_modes.hip): off by default, on the posterior report's pattern.  Per
+    // in-flight frame a pinned slot of n_objects rbs_body_modes the frame's last kernel writes and the event recorded behind it;
+    // rbs_tracker_result copies the slot into `modes`.  M: the parameters and the report's own device buffers.
+    bool modes_on = false, modes_valid = false, modes_ready = false;   // modes_ready: every buffer and event below exists
+    rbt::ModesDev M{};
+    double* modes_work = nullptr;   // modes_doubles(n, bodies)
+    int* modes_sel = nullptr;       // modes_ints(bodies)
+    rbs_body_modes* h_modes[2] = {nullptr, nullptr};
+    rbs_body_modes* h_modes_dev[2] = {nullptr, nullptr};
+    hipEvent_t ev_modes[2] = {nullptr, nullptr};
+    hipEvent_t ev_modes0[2] = {nullptr, nullptr};   // in front of the report's first launch: its device time (rbs_tracker_modes_ms)
+    int modes_seq[2] = {0, 0};
+    float modes_ms = 0.f;
+    int32_t modes_frame = 0;
+    std::vector<rbs_body_modes> modes;
     // the occlusion map (rbs_tracker_set_occlusion_map, rbsensor_occmap.hip): off by default.  Per in-flight frame a pinned
     // image the frame's last kernel writes and the event recorded behind it; rbs_tracker_result copies it into `map`.
     bool map_on = false, map_valid = false, map_ready = false;   // map_ready: every buffer and event below exists
@@ -287,6 +302,9 @@ void rbs_tracker_destroy(rbs_tracker* t)
         if (t->h_post[k]) (void)hipHostFree(t->h_post[k]);
         if (t->ev_post[k]) (void)hipEventDestroy(t->ev_post[k]);
         if (t->ev_post0[k]) (void)hipEventDestroy(t->ev_post0[k]);
+        if (t->h_modes[k]) (void)hipHostFree(t->h_modes[k]);
+        if (t->ev_modes[k]) (void)hipEventDestroy(t->ev_modes[k]);
+        if (t->ev_modes0[k]) (void)hipEventDestroy(t->ev_modes0[k]);
         if (t->h_map[k]) (void)hipHostFree(t->h_map[k]);
         if (t->ev_map[k]) (void)hipEventDestroy(t->ev_map[k]);
         if (t->ev_map0[k]) (void)hipEventDestroy(t->ev_map0[k]);
@@ -305,6 +323,7 @@ int32_t rbs_tracker_initialize(rbs_tracker* t, const double* default_state)
     t->recentre_pending = false;
     t->poisoned = false;
     t->post_valid = false;
+    t->modes_valid = false;
     t->map_valid = false;
     t->obj_valid = false;
     if (!t->reps.empty()) {
@@ -573,6 +592,17 @@ static int32_t tracker_submit_impl(rbs_tracker* t, const float* frame, const dou
         RBT_HIP(t, hipGetLastError());
         RBT_HIP(t, hipEventRecord(t->ev_post[slot], s));
     }
+    if (t->modes_on) {
+        // the modes of the same population (T.part_new, T.logw), behind the posterior report's launches where that is on, with a
+        // slot and an event of their own
+        rbt::ModesDev M = t->M;
+        M.out = t->h_modes_dev[slot];
+        RBT_HIP(t, hipEventRecord(t->ev_modes0[slot], s));
+        rbt::launch_modes(M, T, T.part_new, T.D, rbt::kBody, T.logw, recentred ? 0 : 1, s);
+        RBT_HIP(t, hipGetLastError());
+        RBT_HIP(t, hipEventRecord(t->ev_modes[slot], s));
+        t->modes_seq[slot] = (int)(T.frame + 1);
+    }
     if (t->map_on) {
         // the occlusion map of the population this frame leaves behind (T.logw, T.idx: what rbs_tracker_get returns) over the
         // planes the frame's last updating call wrote, behind everything else of the frame and with an event of its own
@@ -658,6 +688,13 @@ int32_t rbs_tracker_result(rbs_tracker* t, double* out_state, int32_t* out_resam
             std::memcpy(t->post_i, t->h_post[slot] + nd, sizeof(t->post_i));
             if (hipEventElapsedTime(&t->post_ms, t->ev_post0[slot], t->ev_post[slot]) != hipSuccess) { (void)hipGetLastError(); t->post_ms = 0.f; }
             t->post_valid = true;
+        }
+        if (t->modes_on) {   // likewise the modes
+            RBT_HIP(t, hipEventSynchronize(t->ev_modes[slot]));
+            std::memcpy(t->modes.data(), t->h_modes[slot], sizeof(rbs_body_modes) * t->modes.size());
+            t->modes_frame = t->modes_seq[slot];
+            if (hipEventElapsedTime(&t->modes_ms, t->ev_modes0[slot], t->ev_modes[slot]) != hipSuccess) { (void)hipGetLastError(); t->modes_ms = 0.f; }
+            t->modes_valid = true;
         }
         if (t->map_on) {   // likewise the map, finished last
             RBT_HIP(t, hipEventSynchronize(t->ev_map[slot]));
@@ -811,6 +848,63 @@ int32_t rbs_tracker_posterior_ms(rbs_tracker* t, float* ms)
     if (!ms) return tfail(t, RBS_ERR_INVALID_ARGUMENT, "tracker_posterior_ms: null output");
     if (!t->post_on || !t->post_valid) return tfail(t, RBS_ERR_INVALID_ARGUMENT, "tracker_posterior_ms: no report has been handed out");
     *ms = t->post_ms;
+    return RBS_OK;
+}
+
+int32_t rbs_tracker_set_modes(rbs_tracker* t, const rbs_modes_params* params)
+{
+    if (!t) return RBS_ERR_INVALID_ARGUMENT;
+    if (!t->reps.empty() || !t->s->shards.empty())
+        return tfail(t, RBS_ERR_UNSUPPORTED, "tracker_set_modes: single-device trackers only");
+    if (t->submitted != t->collected)
+        return tfail(t, RBS_ERR_INVALID_ARGUMENT, "tracker_set_modes: frames are in flight (call rbs_tracker_result)");
+    if (params)
+        if (const char* why = modes::refuse_params(params)) return tfail(t, RBS_ERR_INVALID_ARGUMENT, fmt("tracker_set_modes: %s", why));
+    rbt::TrackerDev& T = t->T;
+    if (params && T.n > rbt::kModesMaxN) return tfail(t, RBS_ERR_UNSUPPORTED, fmt("tracker_set_modes: at most %d particles", rbt::kModesMaxN));
+    if (params && !t->modes_ready) {
+        // every buffer is made once, each only where an earlier attempt that failed half-way has not left it; the report is
+        // switched on only when all of them exist
+        RBT_HIP(t, hipSetDevice(t->s->device));
+        if (!t->modes_work) if (int32_t rc = talloc(t, &t->modes_work, rbt::modes_doubles(T.n, T.parts))) return rc;
+        if (!t->modes_sel) if (int32_t rc = talloc(t, &t->modes_sel, rbt::modes_ints(T.parts))) return rc;
+        t->M.n = T.n;
+        t->M.parts = T.parts;
+        rbt::modes_carve(t->M, t->modes_work, t->modes_sel);
+        t->modes.assign((size_t)T.parts, rbs_body_modes{});
+        for (int k = 0; k < 2; ++k) {
+            if (!t->h_modes[k]) RBT_HIP(t, hipHostMalloc(&t->h_modes[k], sizeof(rbs_body_modes) * (size_t)T.parts, hipHostMallocDefault));
+            if (!t->h_modes_dev[k]) RBT_HIP(t, hipHostGetDevicePointer(reinterpret_cast<void**>(&t->h_modes_dev[k]), t->h_modes[k], 0));
+            if (!t->ev_modes[k]) RBT_HIP(t, hipEventCreate(&t->ev_modes[k]));
+            if (!t->ev_modes0[k]) RBT_HIP(t, hipEventCreate(&t->ev_modes0[k]));
+        }
+        t->modes_ready = true;
+    }
+    if (params) modes::fill(t->M, T.n, T.parts, *params);
+    t->modes_on = params != nullptr;
+    t->modes_valid = false;
+    return RBS_OK;
+}
+
+int32_t rbs_tracker_modes(rbs_tracker* t, int32_t* frame, rbs_body_modes* out)
+{
+    if (!t) return RBS_ERR_INVALID_ARGUMENT;
+    if (t->poisoned || t->s->poisoned)
+        return tfail(t, RBS_ERR_HIP, "tracker_modes: an earlier frame failed half-way (" + (t->s->poisoned ? t->s->poison_msg : t->err) +
+                                         "): call rbs_tracker_initialize");
+    if (!t->modes_on) return tfail(t, RBS_ERR_INVALID_ARGUMENT, "tracker_modes: the report is off (rbs_tracker_set_modes)");
+    if (!t->modes_valid) return tfail(t, RBS_ERR_INVALID_ARGUMENT, "tracker_modes: no frame has been handed out since rbs_tracker_initialize");
+    if (frame) *frame = t->modes_frame;
+    if (out) std::memcpy(out, t->modes.data(), sizeof(rbs_body_modes) * t->modes.size());
+    return RBS_OK;
+}
+
+int32_t rbs_tracker_modes_ms(rbs_tracker* t, float* ms)
+{
+    if (!t) return RBS_ERR_INVALID_ARGUMENT;
+    if (!ms) return tfail(t, RBS_ERR_INVALID_ARGUMENT, "tracker_modes_ms: null output");
+    if (!t->modes_on || !t->modes_valid) return tfail(t, RBS_ERR_INVALID_ARGUMENT, "tracker_modes_ms: no report has been handed out");
+    *ms = t->modes_ms;
     return RBS_OK;
 }
 

@@ -18,11 +18,13 @@
 //   rbs_planes.h       the occlusion planes' storage: materialize, slab_expand / exact_expand, store_plane, fit_or_grow, grow_slabs, drain
 //   rbs_planes_api.h   the slot entry points: rbs_get_occlusion .. rbs_import_window, rbs_stream_join, rbs_get_window
 //   rbs_ipc.h          IpcBlob, rbs_ipc_export, rbs_ipc_attach, rbs_stage_windows, rbs_peer_resample
+//   rbs_modes_api.h    the posterior modes on a sensor handle: rbs_modes_default_params, rbs_pose_modes
 //   rbs_tracker_api.h  the device tracker's host side: struct rbs_tracker, launch_*, rbs_tracker_*
 // This file itself: release / create_impl, several devices, and the remaining extern "C" sensor entry points.
 #include "rbsensor_kernels.hip"
 #include "rbsensor_tracker.hip"
 #include "rbsensor_posterior.hip"
+#include "rbsensor_modes.hip"
 #include "rbsensor_peers.hip"
 #include "rbs_mesh.h"
 
@@ -67,6 +69,8 @@
 #include "rbsensor_occmap.hip"
 // The object map (rbs_object_*): per pixel and body what a population sees, the mean and variance of its depth, the segmentation.
 #include "rbsensor_objmap.hip"
+// The posterior modes (rbs_pose_modes): the handle's buffers and the stateless entry point; kernels in rbsensor_modes.hip.
+#include "rbs_modes_api.h"
 
 namespace {
 
@@ -144,6 +148,7 @@ void release(rbs_handle* h)
     assess_release(h);
     occmap_release(h);
     objmap_release(h);
+    modes_release(h);
     if (h->up_stream) (void)hipStreamSynchronize(h->up_stream);
     for (int k = 0; k < 2; ++k) {
         if (h->h_frames[k]) (void)hipHostFree(h->h_frames[k]);

@@ -13,7 +13,7 @@ import yaml
 
 from .objloader import ObjectResourceIdentifier, SimpleWavefrontObjectModelLoader
 from .sensor import CameraData, ObjectModel, RbSensor, RbSensorBuilder
-from .tracker import DeviceParticleTracker, ObjectTransitionBuilder, ParticleTracker, ParticleTrackerBuilder
+from .tracker import DeviceParticleTracker, ModesParams, ObjectTransitionBuilder, ParticleTracker, ParticleTrackerBuilder
 
 
 def load_rosparams(*yaml_paths):
@@ -26,13 +26,19 @@ def load_rosparams(*yaml_paths):
 
 
 def build_particle_tracker(params, native_camera_matrix, mesh_package_path, device_id=0, rng=None,
-                           device_filter=True, seed=0, posterior=False, occlusion_map=False, object_map=False):
+                           device_filter=True, seed=0, posterior=False, occlusion_map=False, object_map=False, modes=None):
     """params: merged rosparam tree.  Returns (tracker, object_model, camera_data, ori).
     posterior: switch the device tracker's posterior report on (tracker.posterior() after every frame); the optional key
     particle_filter/posterior of the tree does the same (absent: off -- the reference's YAML files parse unchanged).
     occlusion_map: likewise the device tracker's occlusion map (tracker.occlusion_map()), key particle_filter/occlusion_map.
-    object_map: likewise the device tracker's object map (tracker.object_map(), tracker.segment()), key particle_filter/object_map."""
+    object_map: likewise the device tracker's object map (tracker.object_map(), tracker.segment()), key particle_filter/object_map.
+    modes: the device tracker's posterior modes (tracker.modes()): True for the default parameters or a tracker.ModesParams; the
+    optional key particle_filter/modes (true, or a mapping of h_t, h_r, separation, k_max) does the same."""
     pre = params["particle_filter"]
+    if modes is None or modes is False:
+        modes = ModesParams.from_rosparam(params)
+    elif modes is True:
+        modes = ModesParams()
     posterior = bool(posterior) or bool(pre.get("posterior", False))
     occlusion_map = bool(occlusion_map) or bool(pre.get("occlusion_map", False))
     object_map = bool(object_map) or bool(pre.get("object_map", False))
@@ -55,7 +61,7 @@ def build_particle_tracker(params, native_camera_matrix, mesh_package_path, devi
     if device_filter:
         tracker = DeviceParticleTracker(transition, sensor, object_model, params_tracker, rng,
                                         device_rng=rng is None, seed=seed, posterior=posterior, occlusion_map=occlusion_map,
-                                        object_map=object_map)
+                                        object_map=object_map, modes=modes)
     else:
         tracker = ParticleTracker(transition, sensor, object_model, params_tracker, rng)
     return tracker, object_model, camera_data, ori
@@ -144,7 +150,7 @@ def to_eigen_vector(native_image, downsampling_factor):
 
 
 def replay_dataset(params, dataset, mesh_package_path, initial_states=None, device_id=0, seed=0, max_frames=None,
-                   look_ahead=False, posterior=False, occlusion_map=False, object_map=False):
+                   look_ahead=False, posterior=False, occlusion_map=False, object_map=False, modes=False):
     """Run the tracker over a recorded TrackingDataset (dbot_ros_amd.dataset) the way
     the node runs over live topics: K from the bag's camera_info (frame 0, as GetCameraMatrix does,
     R:source/dbot_ros/util/tracking_dataset.cpp:157-164), every depth image sub-sampled by
@@ -160,6 +166,8 @@ def replay_dataset(params, dataset, mesh_package_path, initial_states=None, devi
     posterior: the device's posterior report (tracker.posterior()) is switched on and collected after every estimate.
     occlusion_map: likewise the device's occlusion map (tracker.occlusion_map()).
     object_map: likewise the device's object map (tracker.object_map()): the list of per-frame tracker.ObjectMap, last.
+    modes: likewise the device's posterior modes (tracker.modes(); True or a tracker.ModesParams): the list of per-frame
+    tracker.Modes, behind the others.
     Returns (estimates [frames, parts*12], wall seconds of the tracking loop); with posterior additionally the list of
     per-frame tracker.Posterior reports; with occlusion_map the list of per-frame tracker.OcclusionMap, behind the reports
     when both are asked for.  The YAML keys alone switch the products on but leave the return value as it is."""
@@ -167,7 +175,7 @@ def replay_dataset(params, dataset, mesh_package_path, initial_states=None, devi
     tracker, object_model, camera_data, _ = build_particle_tracker(params, dataset.get_camera_matrix(0),
                                                                    mesh_package_path, device_id=device_id, seed=seed,
                                                                    posterior=posterior, occlusion_map=occlusion_map,
-                                                                   object_map=object_map)
+                                                                   object_map=object_map, modes=modes or None)
     f = int(params["downsampling_factor"])
     try:
         n = dataset.size() if max_frames is None else min(max_frames, dataset.size())
@@ -193,7 +201,7 @@ def replay_dataset(params, dataset, mesh_package_path, initial_states=None, devi
                 raise RuntimeError("replay_dataset: the object finder found no object on frame 0")
             initial_states = [found.states[0]]
         tracker.initialize(initial_states)
-        ests, reports, maps, objmaps = [], [], [], []
+        ests, reports, maps, objmaps, mode_reports = [], [], [], [], []
 
         def collect(est):
             ests.append(est)
@@ -203,6 +211,8 @@ def replay_dataset(params, dataset, mesh_package_path, initial_states=None, devi
                 maps.append(tracker.occlusion_map())
             if object_map:
                 objmaps.append(tracker.object_map())
+            if modes:
+                mode_reports.append(tracker.modes())
         t0 = time.perf_counter()
         if look_ahead and hasattr(tracker, "submit") and frames:
             tracker.submit(frames[0])
@@ -217,7 +227,7 @@ def replay_dataset(params, dataset, mesh_package_path, initial_states=None, devi
     finally:
         tracker.close()
         tracker.sensor.close()
-    extra = ([reports] if posterior else []) + ([maps] if occlusion_map else []) + ([objmaps] if object_map else [])
+    extra = ([reports] if posterior else []) + ([maps] if occlusion_map else []) + ([objmaps] if object_map else []) + ([mode_reports] if modes else [])
     return (np.array(ests), wall, *extra)
 
 

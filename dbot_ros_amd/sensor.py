@@ -419,6 +419,23 @@ class RbSensor:
         out = np.array([[r.rendered, r.occluded, r.sum_q32] for r in rec[:n * self.n_bodies]], dtype=np.int64)
         return out.reshape(n, self.n_bodies, 3)
 
+    def pose_modes(self, deltas, log_weights, params=None):
+        """The modes of a population on host arrays (rbs_pose_modes; include/rbsensor_mi355x.h, "Posterior modes"): deltas
+        [n, n_bodies, 6] (position and rotation-vector delta per body; [n, n_bodies, 12] states are cut to their pose),
+        log_weights [n], params a tracker.ModesParams (None: the defaults).  Returns a tracker.Modes, found on the device."""
+        from . import tracker as trk
+        lw = np.ascontiguousarray(log_weights, dtype=np.float64).ravel()
+        n = int(lw.size)
+        d = np.asarray(deltas, dtype=np.float64)
+        if n == 0 or d.size % (n * self.n_bodies) != 0 or d.size // (n * self.n_bodies) not in (6, 12):
+            raise RbSensorError(_capi.RBS_ERR_INVALID_ARGUMENT, "deltas must be [n, n_bodies, 6] (or 12) with one log-weight per row")
+        d = np.ascontiguousarray(d.reshape(n, self.n_bodies, -1)[:, :, 0:6])
+        rec = (_capi.RbsBodyModes * self.n_bodies)()
+        c = trk.modes_params_c(params or trk.ModesParams())
+        self._check(self._lib.rbs_pose_modes(self._h, d.ctypes.data_as(C.POINTER(C.c_double)), lw.ctypes.data_as(C.POINTER(C.c_double)),
+                                             n, C.byref(c), rec))
+        return trk.modes_from_c(rec)
+
     def object_map(self, poses, members=None, log_weights=None):
         """The object map of a population (rbs_object_map; include/rbsensor_mi355x.h, "Object map"): poses
         [m, n_bodies, 12], members [n] pose indices (None: the identity), log_weights [n] (None: uniform).  Returns

@@ -56,6 +56,141 @@ def posterior_of(particles, log_weights, indices, resampled=False, frame=0):
                      resampled=bool(resampled), n=int(x.shape[0]), frame=int(frame))
 
 
+MODES_MAX = 8
+MODES_E_MIN = 2.0 ** -960     # e_i below it counts as 0 (include/rbsensor_mi355x.h, "Posterior modes")
+
+
+@dataclass
+class ModesParams:
+    """Parameters of the posterior modes (include/rbsensor_mi355x.h, "Posterior modes").  The defaults are starting values,
+    UNMEASURED: a few transition sigmas wide, not tuned on data."""
+    h_t: float = 0.02          # translation bandwidth, metres (> 0)
+    h_r: float = 0.2           # rotation bandwidth, radians (0 < h_r <= 1)
+    separation: float = 2.0    # suppression radius in bandwidths (>= 1)
+    k_max: int = 4             # most modes returned per body (1 .. 8)
+
+    def check(self):
+        if not (self.h_t > 0 and np.isfinite(self.h_t)):
+            raise ValueError("modes: h_t must be positive")
+        if not 0 < self.h_r <= 1:
+            raise ValueError("modes: h_r must lie in (0, 1]")
+        if not (self.separation >= 1 and np.isfinite(self.separation)):
+            raise ValueError("modes: separation must be at least 1")
+        if not (1 <= int(self.k_max) <= MODES_MAX and int(self.k_max) == self.k_max):
+            raise ValueError("modes: k_max outside 1..8")
+        return self
+
+    @classmethod
+    def from_rosparam(cls, tree):
+        """The optional key particle_filter/modes: true (the defaults), or a mapping of any of the four parameters; None
+        where the key is absent or false -- the reference's YAML files parse unchanged, the report off."""
+        v = tree.get("particle_filter", {}).get("modes", None)
+        if v is None or v is False:
+            return None
+        if v is True:
+            return cls()
+        unknown = set(v) - {"h_t", "h_r", "separation", "k_max"}
+        if unknown:
+            raise ValueError(f"particle_filter/modes: unknown keys {sorted(unknown)}")
+        return cls(h_t=float(v.get("h_t", cls.h_t)), h_r=float(v.get("h_r", cls.h_r)), separation=float(v.get("separation", cls.separation)),
+                   k_max=int(v.get("k_max", cls.k_max))).check()
+
+
+@dataclass
+class Mode:
+    """One mode of one body: seed (particle index), density (rho at the seed), mass (share of the belief assigned to the mode),
+    core_mass (... within one bandwidth of the seed), delta [6] (the core's mean position and rotation-vector delta, re-centred
+    MODEL coordinates), pose [6] (the published position and rotation vector of that body were this mode the estimate: the
+    delta composed with the frame's state as the tracker publishes it; None where no state is known)."""
+    seed: int
+    density: float
+    mass: float
+    core_mass: float
+    delta: np.ndarray
+    pose: np.ndarray = None
+
+
+@dataclass
+class Modes:
+    """bodies: per body the list of its Modes in selection order; frame: frames tracked since initialize (0: stateless)."""
+    bodies: list
+    frame: int = 0
+
+
+def _quaternions(r):
+    """[n, 3] rotation vectors -> [n, 4] unit quaternions (w, x, y, z); (1, 0, 0, 0) at r = 0 (pose.rotvec_to_matrix's form)."""
+    angle = np.sqrt(r[:, 0] * r[:, 0] + r[:, 1] * r[:, 1] + r[:, 2] * r[:, 2])
+    half = 0.5 * angle
+    small = angle < 1e-9
+    k = np.where(small, 0.5 - angle * angle / 48.0, np.sin(half) / np.where(small, 1.0, angle))
+    return np.concatenate([np.cos(half)[:, None], r * k[:, None]], axis=1)
+
+
+def modes_of(particles, log_weights, params=None, frame=0, block=512):
+    """The rule of the posterior modes in numpy -- the restatement the device kernels (csrc/rbsensor_modes.hip) are tested
+    against.  particles [n, parts, >= 6] or [n, parts * 12] (or [n, parts * 6]) re-centred deltas, log_weights [n] (-inf: no
+    contribution).  The pair pass is row-blocked (block rows at a time) to bound memory."""
+    P = (params or ModesParams()).check()
+    lw = np.asarray(log_weights, dtype=np.float64).ravel()
+    n = lw.size
+    x = np.asarray(particles, dtype=np.float64)
+    if x.ndim == 2:
+        w = BODY if x.shape[1] % BODY == 0 else 6
+        x = x.reshape(n, x.shape[1] // w, w)
+    with np.errstate(under="ignore"):
+        e = np.exp(lw - lw.max())
+    e = np.where(e < MODES_E_MIN, 0.0, e)
+    S = e.sum()
+    c4, sep2 = 4.0 / (P.h_r * P.h_r), P.separation * P.separation
+
+    def d2(pa, qa, pb, qb):          # [a, 1, .] against [1, b, .] -> [a, b]
+        d = pa - pb
+        c = (qa * qb).sum(-1)
+        return (d * d).sum(-1) + c4 * (1.0 - c * c)
+
+    bodies = []
+    for b in range(x.shape[1]):
+        p, q = x[:, b, 0:3] / P.h_t, _quaternions(x[:, b, 3:6])
+        rho = np.empty(n)
+        # (two-dimensional temporaries, d2's operations component by component, and no matrix product: every row goes through the
+        #  same sequence of operations, so particles with the same pose get the same rho bit for bit and tie by index)
+        for lo in range(0, n, block):
+            pb, qb = p[lo:lo + block], q[lo:lo + block]
+            d, c = np.zeros((len(pb), n)), np.zeros((len(pb), n))
+            for k in range(3):
+                t = pb[:, k, None] - p[None, :, k]
+                d += t * t
+            for k in range(4):
+                c += qb[:, k, None] * q[None, :, k]
+            k = 1.0 - (d + c4 * (1.0 - c * c))
+            rho[lo:lo + block] = (np.maximum(k, 0.0) * e[None]).sum(1) / S
+        cand = e > 0
+        seeds = []
+        while len(seeds) < P.k_max and cand.any():
+            s = int(np.argmax(np.where(cand, rho, -1.0)))       # (argmax: the lowest index on a tie)
+            seeds.append(s)
+            cand &= ~(d2(p, q, p[s][None], q[s][None]) < sep2)
+        D = np.stack([d2(p, q, p[s][None], q[s][None]) for s in seeds], axis=1)
+        near = np.argmin(D, axis=1)                             # (argmin: the earlier mode on a tie)
+        out = []
+        for k, s in enumerate(seeds):
+            member = (near == k) & (e > 0)
+            core = member & (D[:, k] < 1.0)
+            ec = e[core]
+            sign = np.where((q[core] * q[s][None]).sum(-1) < 0.0, -1.0, 1.0)
+            qm = ((ec * sign)[:, None] * q[core]).sum(0) / ec.sum()    # (of order 1 whatever the weights' scale: no underflow below)
+            qm = qm / np.sqrt((qm * qm).sum())
+            if qm[0] < 0.0:
+                qm = -qm
+            vn = np.sqrt((qm[1:] * qm[1:]).sum())
+            rot = qm[1:] * (2.0 * np.arctan2(vn, qm[0]) / vn) if vn > 0.0 else np.zeros(3)
+            pos = (ec[:, None] * p[core]).sum(0) / ec.sum() * P.h_t
+            out.append(Mode(seed=s, density=float(rho[s]), mass=float(e[member].sum() / S), core_mass=float(ec.sum() / S),
+                            delta=np.concatenate([pos, rot])))
+        bodies.append(out)
+    return Modes(bodies=bodies, frame=int(frame))
+
+
 @dataclass
 class OcclusionMap:
     """What a particle tracker believes is occluded after a frame (include/rbsensor_mi355x.h, "Occlusion map"): plane
@@ -389,6 +524,25 @@ class ParticleTracker:
             raise ValueError("posterior: no frame has been tracked since initialize")
         return posterior_of(self.particles, self.log_weights, self.indices, self._resampled, self._frames)
 
+    def modes(self, params=None):
+        """The modes of the population the last frame left behind (modes_of on this tracker's own arrays), each with its
+        published pose."""
+        if self._frames == 0:
+            raise ValueError("modes: no frame has been tracked since initialize")
+        return self._with_poses(modes_of(self.particles, self.log_weights, params, self._frames), self.default)
+
+    def _with_poses(self, modes, default):
+        """Fill Mode.pose: the mode's delta composed with the MODEL state `default` (translations add, rotations multiply from
+        the left) and converted to the published frame as _from_model does."""
+        z = np.asarray(default, dtype=np.float64).reshape(self.parts, BODY)
+        for b, body in enumerate(modes.bodies):
+            for m in body:
+                s = z.copy()
+                s[b, 0:3] += m.delta[0:3]
+                s[b, 3:6] = matrix_to_rotvec(rotvec_to_matrix(m.delta[3:6]) @ rotvec_to_matrix(z[b, 3:6]))
+                m.pose = self._from_model(s.ravel()).reshape(self.parts, BODY)[b, 0:6].copy()
+        return modes
+
     def pose_covariance(self, posterior):
         """[parts, 6, 6]: per body the covariance of the PUBLISHED pose (position, rotation; camera frame, left
         perturbation) -- J C J^T with object_frame_jacobian when center_object_frame moves the published position to
@@ -459,6 +613,21 @@ class ParticleTracker:
         return _assess.assess_last_estimate(self, assessor, frame, self._in_flight > 0)
 
 
+def modes_params_c(params):
+    """A ModesParams as the C-ABI's rbs_modes_params (unchecked: the library refuses what is out of range)."""
+    from . import _capi
+    c = _capi.RbsModesParams()
+    c.h_t, c.h_r, c.separation, c.k_max, c.reserved = float(params.h_t), float(params.h_r), float(params.separation), int(params.k_max), 0
+    return c
+
+
+def modes_from_c(rec, frame=0):
+    """An array of rbs_body_modes -> Modes (poses unfilled)."""
+    return Modes(bodies=[[Mode(seed=int(m.seed), density=float(m.density), mass=float(m.mass), core_mass=float(m.core_mass),
+                               delta=np.array(m.delta[:], dtype=np.float64)) for m in body.mode[:body.n_modes]] for body in rec],
+                 frame=int(frame))
+
+
 def _rotvecs(R):
     """Vectorised matrix -> rotation vector (atan2 form; particle deltas are far from pi)."""
     s = 0.5 * np.stack([R[:, 2, 1] - R[:, 1, 2], R[:, 0, 2] - R[:, 2, 0], R[:, 1, 0] - R[:, 0, 1]], -1)
@@ -480,7 +649,7 @@ class DeviceParticleTracker(ParticleTracker):
     from this object's numpy Generator exactly as in the host tracker."""
 
     def __init__(self, transition, sensor, object_model, params, rng=None, device_rng=False, seed=0, posterior=False,
-                 occlusion_map=False, object_map=False):
+                 occlusion_map=False, object_map=False, modes=None):
         import ctypes as C
         from . import _capi
         super().__init__(transition, sensor, object_model, params, rng)
@@ -504,6 +673,8 @@ class DeviceParticleTracker(ParticleTracker):
             self.set_occlusion_map(True)
         if object_map:
             self.set_object_map(True)
+        if modes is not None and modes is not False:
+            self.set_modes(ModesParams() if modes is True else modes)
 
     def set_posterior(self, enable):
         """Switch the device's posterior report on or off (rbs_tracker_set_posterior; refused with frames in flight)."""
@@ -525,6 +696,30 @@ class DeviceParticleTracker(ParticleTracker):
         """Device time of the last report's kernels in milliseconds (rbs_tracker_posterior_ms)."""
         ms = self._C.c_float()
         self.sensor._check(self._lib.rbs_tracker_posterior_ms(self._t, self._C.byref(ms)))
+        return float(ms.value)
+
+    def set_modes(self, params):
+        """Switch the device's posterior modes on with `params` (a ModesParams; True: the defaults) or off (None / False)
+        (rbs_tracker_set_modes; refused with frames in flight)."""
+        if params is None or params is False:
+            self.sensor._check(self._lib.rbs_tracker_set_modes(self._t, None))
+            return
+        self.sensor._check(self._lib.rbs_tracker_set_modes(self._t, self._C.byref(modes_params_c(ModesParams() if params is True else params))))
+
+    def modes(self):
+        """The Modes of the frame most recently handed out by track() / result() (rbs_tracker_modes), found on the device;
+        needs modes=... (or set_modes()) -- an RbSensorError otherwise.  Each Mode carries its published pose: the delta
+        composed with that frame's state."""
+        C = self._C
+        frame = C.c_int32()
+        rec = (self._capi.RbsBodyModes * self.parts)()
+        self.sensor._check(self._lib.rbs_tracker_modes(self._t, C.byref(frame), rec))
+        return self._with_poses(modes_from_c(rec, int(frame.value)), self.default)
+
+    def modes_ms(self):
+        """Device time of the last modes report's kernels in milliseconds (rbs_tracker_modes_ms)."""
+        ms = self._C.c_float()
+        self.sensor._check(self._lib.rbs_tracker_modes_ms(self._t, self._C.byref(ms)))
         return float(ms.value)
 
     def set_occlusion_map(self, enable):

@@ -529,6 +529,54 @@ public:
         p.frame = info.frame;
         return p;
     }
+    /// The posterior modes of the frame most recently handed out by track() / result() (rbs_tracker_modes): per body the humps
+    /// of the particle cloud in selection order -- the particle a mode was seeded at, the density there, the share of the
+    /// belief assigned to it and to its core, and the core's mean pose delta (position, rotation vector; re-centred MODEL
+    /// coordinates, as the Posterior's mean).
+    struct Mode {
+        int seed = -1;
+        Real density = 0, mass = 0, core_mass = 0;
+        Real delta[6] = {0, 0, 0, 0, 0, 0};
+    };
+    struct Modes {
+        std::vector<std::vector<Mode>> bodies;
+        int frame = 0;
+    };
+    /// The starting parameters (unmeasured: include/rbsensor_mi355x.h, "Posterior modes").
+    static rbs_modes_params default_modes_params()
+    {
+        rbs_modes_params p;
+        rbs_modes_default_params(&p);
+        return p;
+    }
+    /// Switch the report on with these parameters (off by default; refused while frames are in flight) or off.
+    void enable_modes(const rbs_modes_params& p) { check(rbs_tracker_set_modes(t_, &p)); }
+    void enable_modes(bool on = true)
+    {
+        if (on) enable_modes(default_modes_params());
+        else check(rbs_tracker_set_modes(t_, nullptr));
+    }
+    Modes modes() const
+    {
+        std::vector<rbs_body_modes> rec(static_cast<size_t>(parts_));
+        int32_t frame = 0;
+        check(rbs_tracker_modes(t_, &frame, rec.data()));
+        Modes out;
+        out.frame = frame;
+        out.bodies.resize(rec.size());
+        for (size_t b = 0; b < rec.size(); ++b)
+            for (int k = 0; k < rec[b].n_modes && k < RBS_MODES_MAX; ++k) {
+                const rbs_mode& r = rec[b].mode[k];
+                Mode m;
+                m.seed = r.seed;
+                m.density = r.density;
+                m.mass = r.mass;
+                m.core_mass = r.core_mass;
+                for (int c = 0; c < 6; ++c) m.delta[c] = r.delta[c];
+                out.bodies[b].push_back(m);
+            }
+        return out;
+    }
     /// The occlusion map of the frame most recently handed out by track() / result() (rbs_tracker_occlusion_map): what the
     /// filter believes is occluded, the weighted mean of the particles' occlusion planes, rows*cols floats, and the number
     /// of frames tracked since initialize().

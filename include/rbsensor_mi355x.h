@@ -606,6 +606,79 @@ int32_t rbs_tracker_posterior(rbs_tracker* t, rbs_tracker_posterior_info* info, 
  * RBS_ERR_INVALID_ARGUMENT wherever rbs_tracker_posterior has no report. */
 int32_t rbs_tracker_posterior_ms(rbs_tracker* t, float* ms);
 
+/* Posterior modes (opt-in): is the posterior one hump or several, and where are they -- the question a particle filter can
+ * answer and a mean with a covariance cannot.  A box seen from one side, a re-find, an occluder: the cloud splits, its mean is a
+ * pose in neither hump, and its covariance says nothing of where to look.  The modes are found on the device by an all-pairs
+ * weighted kernel density over the particles (n^2 pair terms per body).
+ *
+ * The rule.  Inputs are the posterior report's: the RE-CENTRED deltas x_i rbs_tracker_get returns after the frame and the
+ * log-weights lw_i;  m = max lw,  e_i = exp(lw_i - m), and e_i = 0 where that is below 2^-960 (lw_i = -inf, or 289 orders
+ * of magnitude below the heaviest particle: no belief, and binary64 products of such a weight would be subnormal and lose
+ * the bits the sums' error bounds count on),  S = sum e_i.  Bodies are treated independently
+ * (the filter samples them in blocks of their own, and joint modes in 6 n_objects dimensions are too sparse for a few thousand
+ * particles).  For a body: p_i the particle's position delta, r_i its rotation-vector delta,
+ *   q_i = (cos(|r_i| / 2), sin(|r_i| / 2) r_i / |r_i|)   the unit quaternion, (1, 0, 0, 0) at r_i = 0
+ *   d2(i, j) = |p_i - p_j|^2 / h_t^2  +  4 (1 - (q_i . q_j)^2) / h_r^2
+ *              (4 (1 - c^2) = 4 sin^2(theta / 2) of the relative rotation angle theta: theta^2 to second order, blind to the
+ *              sign of a quaternion, the same for r and its equivalent beyond pi)
+ *   rho_i    = (1 / S) sum_j e_j max(0, 1 - d2(i, j))     compact support: no exp in the pair loop
+ * Selection, at most k_max rounds: the candidates are the particles with e_i > 0 that are not suppressed; the seed s_k is the
+ * candidate of largest rho, the lowest index on a tie; then every i with d2(i, s_k) < separation^2 is suppressed; the rounds
+ * stop when no candidate is left.  Assignment: every particle with e_i > 0 belongs to the seed of smallest d2, the earlier
+ * mode on a tie.  mass_k = (sum of e over the members) / S: the masses sum to 1.  The mode's CORE is its members with
+ * d2(i, s_k) < 1, core_mass_k their share; the mode's position delta is the e-weighted mean of the core's p_i, its rotation the
+ * normalised e-weighted sum of sign(q_i . q_s) q_i over the core (h_r <= 1 keeps |q_i . q_s| > 0.86 there) turned back into a
+ * rotation vector with angle in [0, pi].
+ * Every sum is taken in binary64 in a fixed order that depends on n and the parameters only (no floating-point atomics): two
+ * runs give the same bits, and so do frame by frame and look-ahead.
+ *
+ * Parameters: h_t > 0 (metres), 0 < h_r <= 1 (radians), separation >= 1, 1 <= k_max <= RBS_MODES_MAX.
+ * rbs_modes_default_params fills the starting values -- 0.02 m, 0.2 rad, 2, 4 -- which are UNMEASURED: chosen from the scale
+ * of the transition noise, not tuned on data.
+ * At most 65 536 particles (the pair pass is n^2): RBS_ERR_UNSUPPORTED above. */
+#define RBS_MODES_MAX 8
+typedef struct rbs_modes_params {
+    double h_t;           /* translation bandwidth, metres */
+    double h_r;           /* rotation bandwidth, radians */
+    double separation;    /* suppression radius in bandwidths */
+    int32_t k_max;        /* most modes returned per body */
+    int32_t reserved;     /* 0 */
+} rbs_modes_params;
+typedef struct rbs_mode {
+    int32_t seed;         /* the particle the mode was seeded at (-1: unused entry) */
+    int32_t reserved;
+    double density;       /* rho at the seed */
+    double mass;          /* share of the belief assigned to the mode */
+    double core_mass;     /* ... within one bandwidth of the seed */
+    double delta[6];      /* the core's mean pose: position delta, rotation-vector delta (re-centred, as rbs_tracker_get's) */
+} rbs_mode;
+typedef struct rbs_body_modes {
+    int32_t n_modes;      /* 1 .. k_max */
+    int32_t reserved;
+    rbs_mode mode[RBS_MODES_MAX];   /* in selection order; entries from n_modes on are unused */
+} rbs_body_modes;
+void rbs_modes_default_params(rbs_modes_params* p);
+/* Stateless, on host arrays (the host-side filter, tests): deltas [n][n_objects][6] (position, rotation vector per body),
+ * log_weights [n] (finite or -inf, at least one finite), out [n_objects].  Synchronous.  RBS_ERR_INVALID_ARGUMENT: n < 1, n above
+ * the sensor's max_particles, parameters out of range, a null pointer, a log-weight that is NaN or +inf, all of them -inf, a
+ * delta that is not finite; RBS_ERR_UNSUPPORTED: a handle over several devices, n > 65 536. */
+int32_t rbs_pose_modes(rbs_handle* h, const double* deltas, const double* log_weights, int32_t n, const rbs_modes_params* params,
+                       rbs_body_modes* out);
+/* The device tracker's report, on the pattern of the posterior report: params != NULL switches it on with these parameters
+ * (allocating its buffers the first time), NULL off.  Off -- the default -- a frame enqueues exactly what it did before the
+ * report existed; on, its kernels are launched behind the frame's chain (behind the posterior report's when that is on too; the
+ * two are independent and neither needs the other) into a pinned slot per in-flight frame, with an event of its own.  Frames in
+ * flight: RBS_ERR_INVALID_ARGUMENT; a tracker over several devices or of more than 65 536 particles: RBS_ERR_UNSUPPORTED.  The
+ * filter itself is not touched: estimates and particles are bit for bit those of a tracker with the report off.
+ * rbs_tracker_modes: the report of the frame most recently handed out by rbs_tracker_result / rbs_tracker_track* (with
+ * look-ahead: of frame k after result(k), while k + 1 is in flight); out [n_objects]; frame (may be NULL): frames tracked since
+ * rbs_tracker_initialize.  RBS_ERR_INVALID_ARGUMENT while the report is off, before the first frame, and after
+ * rbs_tracker_initialize until the next result; a poisoned tracker's error otherwise.
+ * rbs_tracker_modes_ms: device time of that report's kernels, first launch to last, in milliseconds. */
+int32_t rbs_tracker_set_modes(rbs_tracker* t, const rbs_modes_params* params);
+int32_t rbs_tracker_modes(rbs_tracker* t, int32_t* frame, rbs_body_modes* out);
+int32_t rbs_tracker_modes_ms(rbs_tracker* t, float* ms);
+
 /* ------------------------------------------------------------------------------------------
  * Robust Gaussian tracker (the reference's second tracker, R:source/dbot_ros/tracker/gaussian_tracker_node.cpp):
  * an unscented-transform Gaussian filter over the object state with pixels as conditionally independent

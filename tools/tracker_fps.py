@@ -16,7 +16,11 @@ three-body scene; --never-resample sets max_kl_divergence so large that nothing 
 
     tracker_fps.py [COUNTS [MESHES]] --object-map [--never-resample] [--repeats R]
 the same for the device tracker's object map (rbs_tracker_set_object_map), with the sensor's raster kernel time of the
-frame's likelihood call beside the map's (rbs_raster_kernel_ms: the kernel that draws the same poses)."""
+frame's likelihood call beside the map's (rbs_raster_kernel_ms: the kernel that draws the same poses).
+
+    tracker_fps.py [COUNTS [MESHES]] --modes [--never-resample] [--repeats R]
+the same for the device tracker's posterior modes (rbs_tracker_set_modes, the default parameters); with the number of modes of
+the last frame's first body."""
 import json
 import os
 import sys
@@ -33,7 +37,7 @@ from dbot_ros_amd.tracker import (DeviceParticleTracker, ObjectTransitionBuilder
 
 
 def posterior_main(argv, product="posterior"):
-    """--posterior, --occlusion-map, --object-map: see the module's docstring."""
+    """--posterior, --occlusion-map, --object-map, --modes: see the module's docstring."""
     repeats = 5
     never = product != "posterior" and "--never-resample" in argv
     argv = [a for a in argv if a != "--never-resample"]
@@ -67,7 +71,8 @@ def posterior_main(argv, product="posterior"):
             tr = DeviceParticleTracker(trans, s, om, tp, device_rng=True, seed=1)
             switch, ms_of, last = {"posterior": (tr.set_posterior, tr.posterior_ms, tr.posterior),
                                    "occlusion_map": (tr.set_occlusion_map, tr.occlusion_map_ms, tr.occlusion_map),
-                                   "object_map": (tr.set_object_map, tr.object_map_ms, tr.object_map)}[product]
+                                   "object_map": (tr.set_object_map, tr.object_map_ms, tr.object_map),
+                                   "modes": (lambda on: tr.set_modes(True if on else None), tr.modes_ms, tr.modes)}[product]
 
             def block(on, look_ahead, collect_ms=None):
                 """The 30 frames from a fresh initialize -> frames/s (the same sequence every time: device RNG, same seed)."""
@@ -100,12 +105,15 @@ def posterior_main(argv, product="posterior"):
                 for la in (False, True):
                     for on in (False, True):                  # alternating
                         fps[(on, la)].append(block(on, la))
-            what = {"posterior": "posterior report", "occlusion_map": "occlusion map", "object_map": "object map"}[product]
+            what = {"posterior": "posterior report", "occlusion_map": "occlusion map", "object_map": "object map",
+                    "modes": "posterior modes"}[product]
             out = {"metric": "tracker FPS, %s off / on" % what, "evaluation_count": n, "objects": nb, "particles": max(1, n // nb),
                    "repeats": repeats, "unit": "frames/s", "resolution": [cols, rows],
                    product + "_kernels_device_ms": {"median": float(np.median(ms)), "min": float(np.min(ms)), "max": float(np.max(ms))}}
             if product != "posterior":
                 out["resamplings"] = tr.n_resamplings
+            if product == "modes":
+                out["modes_of_body_0_last_frame"] = len(last().bodies[0])
             if product == "object_map":
                 out["raster_kernel_ms_last_call"] = float(s.raster_kernel_ms())
             for (on, la), v in fps.items():
@@ -127,6 +135,9 @@ def main():
     if "--object-map" in sys.argv:
         argv = [a for a in sys.argv[1:] if a != "--object-map"]
         return posterior_main(argv, product="object_map")
+    if "--modes" in sys.argv:
+        argv = [a for a in sys.argv[1:] if a != "--modes"]
+        return posterior_main(argv, product="modes")
     counts = [int(x) for x in sys.argv[1].split(",")] if len(sys.argv) > 1 else [200, 2000, 20000]
     names = sys.argv[2].split(",") if len(sys.argv) > 2 else ["m1"]     # e.g. m1,m2,m3 = BASELINE config C2
     cols, rows, n_frames = 640, 480, 30
