@@ -62,7 +62,10 @@ EXPORTS = (
     "rbs_object_map", "rbs_object_map_ms", "rbs_object_map_info", "rbs_object_segment_default_params", "rbs_object_segment",
     "rbs_tracker_set_object_map", "rbs_tracker_object_map", "rbs_tracker_object_map_ms", "rbs_tracker_poses",
     "rbs_modes_default_params", "rbs_pose_modes", "rbs_tracker_set_modes", "rbs_tracker_modes", "rbs_tracker_modes_ms",
+    "rbs_refine_default_params", "rbs_refine_check_params", "rbs_refine_poses", "rbs_refine_get_history", "rbs_refine_kernel_ms",
 )
+RBS_REFINE_MAX_ITERATIONS, RBS_REFINE_CONVERGED, RBS_REFINE_TOO_FEW_PIXELS, RBS_REFINE_DEGENERATE, RBS_REFINE_FROZEN = range(5)
+RBS_REFINE_MAX_ITERS = 32
 RBS_MODES_MAX = 8
 RBS_ASSESS_OUT_OF_VIEW, RBS_ASSESS_OCCLUDED, RBS_ASSESS_SUPPORTED, RBS_ASSESS_LOST = range(4)
 RBS_CONTOUR_NO_RIM, RBS_CONTOUR_UNDECIDED, RBS_CONTOUR_PRESENT, RBS_CONTOUR_ABSENT = range(4)
@@ -225,6 +228,41 @@ class RbsAssessBody(C.Structure):
         ("behind", C.c_int32),
         ("verdict", C.c_int32),
         ("reserved", C.c_int32 * 2),
+    ]
+
+
+class RbsRefineParams(C.Structure):
+    _fields_ = [
+        ("gate_sigmas", C.c_double),
+        ("huber_sigmas", C.c_double),
+        ("damping", C.c_double),
+        ("max_rotation", C.c_double),
+        ("max_translation", C.c_double),
+        ("eps_rotation", C.c_double),
+        ("eps_translation", C.c_double),
+        ("min_pixels", C.c_int32),
+        ("iters", C.c_int32),
+    ]
+
+
+class RbsRefineBody(C.Structure):
+    _fields_ = [
+        ("status", C.c_int32),
+        ("iterations", C.c_int32),
+        ("count_first", C.c_int32),
+        ("count_last", C.c_int32),
+        ("rms_first", C.c_double),
+        ("rms_last", C.c_double),
+    ]
+
+
+class RbsRefineHistory(C.Structure):
+    _fields_ = [
+        ("pose", C.c_double * 12),
+        ("sums", C.c_double * 28),
+        ("delta", C.c_double * 6),
+        ("count", C.c_int32),
+        ("status", C.c_int32),
     ]
 
 
@@ -562,6 +600,16 @@ def load():
     lib.rbs_contour_verdict.argtypes = [C.POINTER(RbsContourParams), C.POINTER(RbsContourBody), ip]
     lib.rbs_contour_kernel_ms.restype = C.c_int32
     lib.rbs_contour_kernel_ms.argtypes = [H, fp]
+    lib.rbs_refine_default_params.restype = None
+    lib.rbs_refine_default_params.argtypes = [C.POINTER(RbsRefineParams)]
+    lib.rbs_refine_check_params.restype = C.c_int32
+    lib.rbs_refine_check_params.argtypes = [C.POINTER(RbsRefineParams)]
+    lib.rbs_refine_poses.restype = C.c_int32
+    lib.rbs_refine_poses.argtypes = [H, C.POINTER(RbsRefineParams), fp, dp, C.c_int32, dp, C.POINTER(RbsRefineBody)]
+    lib.rbs_refine_get_history.restype = C.c_int32
+    lib.rbs_refine_get_history.argtypes = [H, C.c_int32, C.c_int32, C.c_int32, C.POINTER(RbsRefineHistory)]
+    lib.rbs_refine_kernel_ms.restype = C.c_int32
+    lib.rbs_refine_kernel_ms.argtypes = [H, fp]
     lib.rbs_occlusion_mean.restype = C.c_int32
     lib.rbs_occlusion_mean.argtypes = [H, ip, dp, C.c_int32, fp]
     lib.rbs_occlusion_mean_ms.restype = C.c_int32

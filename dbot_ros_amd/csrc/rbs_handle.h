@@ -251,6 +251,8 @@ struct rbs_handle {
     struct rbs_objmap_state* objmap = nullptr;
     // ---- the posterior modes (rbs_modes_api.h): its buffers, allocated by the first rbs_pose_modes
     struct rbs_modes_state* modes = nullptr;
+    // ---- the pose refiner (rbs_refine_api.h): its planes, partial sums and staging, allocated by the first rbs_refine_poses
+    struct rbs_refine_state* refine = nullptr;
     long frames_handed = 0;     // frames handed over since rbs_create (rbs_object_segment refuses a handle that never saw one)
 };
 

@@ -71,6 +71,9 @@
 #include "rbsensor_objmap.hip"
 // The posterior modes (rbs_pose_modes): the handle's buffers and the stateless entry point; kernels in rbsensor_modes.hip.
 #include "rbs_modes_api.h"
+// The pose refiner (rbs_refine_*): projective point-to-plane Gauss-Newton on the assess rule's planes; kernels, then the host side.
+#include "rbsensor_refine.hip"
+#include "rbs_refine_api.h"
 
 namespace {
 
@@ -149,6 +152,7 @@ void release(rbs_handle* h)
     occmap_release(h);
     objmap_release(h);
     modes_release(h);
+    refine_release(h);
     if (h->up_stream) (void)hipStreamSynchronize(h->up_stream);
     for (int k = 0; k < 2; ++k) {
         if (h->h_frames[k]) (void)hipHostFree(h->h_frames[k]);

@@ -28,6 +28,9 @@ class FindResult:
     assessment: Optional[object] = None   # find(assess=PoseAssessor): the assess.Assessment of the K poses against the frame
     confirmed: Optional[int] = None       # ... and the first pose whose verdict is SUPPORTED (-1: none)
     classes: Optional[np.ndarray] = None  # the gate on: [K] int32, 0 = the pose is confirmed (SUPPORTED and PRESENT); None: the stage off
+    refined: Optional[np.ndarray] = None  # find(refine=PoseRefiner): [K', 12] the first K' = min(K, 64) poses refined against the frame
+    refined_states: Optional[np.ndarray] = None   # ... as tracker states [K', 12], like `states`
+    refinement: Optional[object] = None   # ... and the refine.Refinement of those poses
 
 
 # the dominant plane of the last find (step 1b): 1 / z = a u + b v + c over the coarse pixels (u, v)
@@ -152,6 +155,9 @@ class ObjectFinder:
         gate = None
         # the optional `scene:` mapping, a SceneFinder.Parameters (several objects: node.build_scene_finder); None: its defaults
         scene = None
+        # the optional `refine:` key (node.py: the poses a replay starts from are refined by node.build_pose_refiner's PoseRefiner);
+        # a plain attribute as well: the finder itself never reads it -- find(refine=...) is the switch
+        refine = False
 
         @classmethod
         def from_rosparam(cls, tree):
@@ -168,6 +174,8 @@ class ObjectFinder:
                 p.gate = ObjectFinder.Gate.from_mapping(m.pop("gate"))
             if "scene" in m:
                 p.scene = SceneFinder.Parameters.from_mapping(m.pop("scene"))
+            if "refine" in m:
+                p.refine = bool(m.pop("refine"))
             for k in ("nms_angle", "sigma_angle"):
                 if k + "_deg" in m:
                     m[k] = math.radians(float(m.pop(k + "_deg")))
@@ -235,12 +243,24 @@ class ObjectFinder:
         if rc != 0:
             raise RbSensorError(rc, self._lib.rbs_find_last_error(self._f).decode())
 
-    def find(self, frame=None, k=None, assess=None):
+    def _states_of(self, poses):
+        states = np.zeros((len(poses), 12))
+        c = self.centers[0]
+        for i in range(len(poses)):
+            R = poses[i, :9].reshape(3, 3)
+            states[i, 0:3] = poses[i, 9:12] - R @ c
+            states[i, 3:6] = matrix_to_rotvec(R)
+        return states
+
+    def find(self, frame=None, k=None, assess=None, refine=None):
         """frame: rows*cols depth (metres, NaN = no reading) at the sensor's resolution, or None for
         the sensor's current observation.  Returns up to k (default n_survivors) poses, best first.
         assess: a PoseAssessor over the same sensor -- the returned poses are judged against the same frame
         (FindResult.assessment) and `confirmed` names the first one that is SUPPORTED (with the assessor's contour rule
-        on: the first of Assessment.confirmed_mask()); `found` is unchanged."""
+        on: the first of Assessment.confirmed_mask()); `found` is unchanged.
+        refine: a PoseRefiner over the same sensor -- the returned poses are refined against the same frame
+        (FindResult.refined, refined_states, refinement) and `assess` judges the refined ones; poses, states and scores
+        stay the finder's own."""
         k = int(self.params.n_survivors if k is None else k)
         poses = np.zeros((max(k, 1), 12))
         scores = np.zeros(max(k, 1))
@@ -255,20 +275,19 @@ class ObjectFinder:
                                            poses.ctypes.data_as(dp), scores.ctypes.data_as(dp), C.byref(n), C.byref(found)))
         K = int(n.value)
         poses, scores = poses[:K].copy(), scores[:K].copy()
-        states = np.zeros((K, 12))
-        c = self.centers[0]
-        for i in range(K):
-            R = poses[i, :9].reshape(3, 3)
-            states[i, 0:3] = poses[i, 9:12] - R @ c
-            states[i, 3:6] = matrix_to_rotvec(R)
-        res = FindResult(bool(found.value), states, poses, scores)
+        res = FindResult(bool(found.value), self._states_of(poses), poses, scores)
         if self.gate is not None:
             res.classes = self.evidence(_capi.RBS_FIND_RESULT)[1][:K]
+        judged = poses
+        if refine is not None and K > 0:
+            refined, res.refinement = refine.refine(poses[:min(K, 64)], img)
+            res.refined = judged = refined.reshape(-1, 12)
+            res.refined_states = self._states_of(res.refined)
         if assess is not None:
             from .assess import SUPPORTED
             res.confirmed = -1
             if K > 0:
-                res.assessment = assess.assess(poses[:min(K, 64)], img)
+                res.assessment = assess.assess(judged[:min(K, 64)], img)
                 hits = np.nonzero(res.assessment.verdicts[:, 0] == SUPPORTED)[0]
                 if res.assessment.contour_verdicts is not None:   # the assessor's contour rule is on: the silhouette must be PRESENT too
                     hits = np.nonzero(res.assessment.confirmed_mask())[0]
@@ -394,6 +413,9 @@ class SceneFindResult:
     joint_score: float    # the B-body log-likelihood of `poses` on the frame (NaN: a body has no pose)
     assessment: Optional[object] = None   # find(assess=PoseAssessor): the assess.Assessment of the B poses against the frame
     confirmed: Optional[np.ndarray] = None   # ... and [B] bool: the body is searched and confirmed (None: no assessor, or a body without a pose)
+    refined: Optional[np.ndarray] = None     # find(refine=PoseRefiner): [B, 12] the poses refined against the frame (None: no refiner, or a body without a pose)
+    refined_state: Optional[np.ndarray] = None   # ... as one tracker state [B*12], like `state`
+    refinement: Optional[object] = None      # ... and the refine.Refinement of that one pose
 
     @property
     def all_found(self):
@@ -554,12 +576,16 @@ class SceneFinder:
         t = s[:, 0:3] + np.einsum("bij,bj->bi", R, self.centers)
         return pack_Rt(R, t).reshape(self.parts, 12)
 
-    def find(self, frame=None, search=None, given=None, assess=None, given_poses=None):
+    def find(self, frame=None, search=None, given=None, assess=None, given_poses=None, refine=None):
         """frame: rows*cols depth at the sensor's resolution (None: the sensor's current observation).  search: the bodies
         to place (None: all; indices or a bit mask).  The others' poses: given, a tracker state [B*12] in the caller's mesh
         frames (a tracker's estimate), or given_poses [B, 12] in the sensor's mesh frames, which come back bit for bit.
         assess: a PoseAssessor over the same sensor -- the B poses are judged against the same frame and `confirmed` names
-        the searched bodies that read SUPPORTED (with the contour rule on: and PRESENT)."""
+        the searched bodies that read SUPPORTED (with the contour rule on: and PRESENT).
+        refine: a PoseRefiner over the same sensor -- the B poses are refined together against the same frame
+        (SceneFindResult.refined, refined_state, refinement; the bodies not searched are refined with the others inside the
+        call, which `refinement` reports, but keep their given poses bit for bit in `refined`) and
+        `assess` judges the refined ones; poses, states and scores stay the finder's own."""
         mask = self.mask_of(search)
         B = self.parts
         gp = None
@@ -581,17 +607,30 @@ class SceneFinder:
                                                  poses.ctypes.data_as(dp), scores.ctypes.data_as(dp), C.byref(found), C.byref(joint)))
         searched = np.array([bool(mask >> b & 1) for b in range(B)])
         fnd = np.array([bool(found.value >> b & 1) for b in range(B)]) | ~searched
-        states = np.full((B, 12), np.nan)
-        for b in range(B):
-            if np.isfinite(poses[b]).all():
-                R = poses[b, :9].reshape(3, 3)
-                states[b] = 0.0
-                states[b, 0:3] = poses[b, 9:12] - R @ self.centers[b]
-                states[b, 3:6] = matrix_to_rotvec(R)
+        def states_of(poses):
+            states = np.full((B, 12), np.nan)
+            for b in range(B):
+                if np.isfinite(poses[b]).all():
+                    R = poses[b, :9].reshape(3, 3)
+                    states[b] = 0.0
+                    states[b, 0:3] = poses[b, 9:12] - R @ self.centers[b]
+                    states[b, 3:6] = matrix_to_rotvec(R)
+            return states
+
+        states = states_of(poses)
         res = SceneFindResult(fnd, searched, states.ravel().copy(), states, poses, scores, float(joint.value))
+        judged = poses
+        if refine is not None and np.isfinite(poses).all():
+            refined, res.refinement = refine.refine(poses[None], img)
+            res.refined = judged = refined.reshape(B, 12)
+            # the refiner moves every body of a pose: inside the call the given bodies are refined too, so the searched bodies'
+            # ownership is taken against neighbours that move with them, and `refinement` reports status, counts and rms of
+            # every body as it moved there.  Only the searched bodies take their refined pose; the given ones are put back.
+            res.refined[~searched] = poses[~searched]
+            res.refined_state = states_of(res.refined).ravel().copy()
         if assess is not None and np.isfinite(poses).all():
             from .assess import SUPPORTED
-            res.assessment = assess.assess(poses[None], img)
+            res.assessment = assess.assess(judged[None], img)
             ok = np.asarray(res.assessment.verdicts).reshape(-1)[:B] == SUPPORTED
             if res.assessment.contour_verdicts is not None:
                 from .assess import CONTOUR_PRESENT

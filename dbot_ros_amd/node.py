@@ -141,6 +141,20 @@ def build_scene_finder(params, native_camera_matrix, mesh_package_path, device_i
                         refinement=finder_params.refinement, gate=finder_params.gate), object_model, camera_data)
 
 
+def _finder_refines(params):
+    """`object_finder/refine` of the tree (absent: false)."""
+    return bool(dict((params or {}).get("object_finder") or {}).get("refine", False))
+
+
+def build_pose_refiner(params, sensor):
+    """The pose refiner (dbot_ros_amd/refine.py) over `sensor`, its parameters from the optional `pose_refiner:` mapping of the
+    tree (PoseRefiner.Parameters' fields, every one an unmeasured starting value; unknown keys: ValueError).  It is used where
+    `object_finder/refine: true` (the pose a replay starts from) or `supervisor/refine: true` (every find of a supervised
+    replay) asks for it; without those keys nothing refines."""
+    from .refine import PoseRefiner
+    return PoseRefiner(sensor, PoseRefiner.Parameters.from_mapping((params or {}).get("pose_refiner")))
+
+
 def to_eigen_vector(native_image, downsampling_factor):
     """ri::to_eigen_vector (R:source/dbot_ros/util/ros_interface.h:152-168) on the host."""
     img = np.asarray(native_image)
@@ -184,22 +198,22 @@ def replay_dataset(params, dataset, mesh_package_path, initial_states=None, devi
             finder, _, _ = build_scene_finder(params, dataset.get_camera_matrix(0), mesh_package_path, device_id=device_id,
                                               sensor=tracker.sensor)
             try:
-                found = finder.find(frames[0])
+                found = finder.find(frames[0], refine=build_pose_refiner(params, tracker.sensor) if _finder_refines(params) else None)
             finally:
                 finder.close()
             if not found.all_found:
                 raise RuntimeError("replay_dataset: the scene finder did not find every object on frame 0")
-            initial_states = [found.state]
+            initial_states = [found.state if found.refined_state is None else found.refined_state]
         elif initial_states is None:
             finder, _, _ = build_object_finder(params, dataset.get_camera_matrix(0), mesh_package_path, device_id=device_id,
                                                sensor=tracker.sensor)
             try:
-                found = finder.find(frames[0])
+                found = finder.find(frames[0], refine=build_pose_refiner(params, tracker.sensor) if _finder_refines(params) else None)
             finally:
                 finder.close()
             if not found.found:
                 raise RuntimeError("replay_dataset: the object finder found no object on frame 0")
-            initial_states = [found.states[0]]
+            initial_states = [found.states[0] if found.refined_states is None else found.refined_states[0]]
         tracker.initialize(initial_states)
         ests, reports, maps, objmaps, mode_reports = [], [], [], [], []
 
@@ -232,7 +246,7 @@ def replay_dataset(params, dataset, mesh_package_path, initial_states=None, devi
 
 
 def replay_dataset_supervised(params, dataset, mesh_package_path, initial_states=None, device_id=0, seed=0, max_frames=None,
-                              look_ahead=False):
+                              look_ahead=False, refine=None):
     """replay_dataset with the judgement the reference leaves to a person
     (R:source/dbot_ros/tracker/object_tracker_controller_service_node.cpp:180-195): every estimate is assessed against
     its frame (dbot_ros_amd/assess.py) and a TrackSupervisor (dbot_ros_amd/supervisor.py) re-finds an object the tracker
@@ -243,16 +257,20 @@ def replay_dataset_supervised(params, dataset, mesh_package_path, initial_states
     contour verdict is ABSENT makes the frame count as lost).  initial_states=None: the object is found on frame 0 and the find must be CONFIRMED -- the first returned pose
     that reads SUPPORTED starts the tracker; none: RuntimeError.  Several objects: a scene finder (build_scene_finder) finds all of
     them on frame 0 -- every body must be confirmed -- and re-finds the bodies that count as lost, given the others' estimates
-    (TrackSupervisor's find_bodies).  Returns (estimates [frames, parts*12], verdicts [frames, parts], events [frames] of
+    (TrackSupervisor's find_bodies).  refine: True, or `supervisor/refine: true` in the tree, refines every found pose
+    against its frame (build_pose_refiner: the `pose_refiner:` mapping) before the assessor confirms it, on frame 0 and at
+    every re-find; the tracker starts from the refined state.  None / absent: every find is what it was without.
+    Returns (estimates [frames, parts*12], verdicts [frames, parts], events [frames] of
     None / "lost" / "reacquired" / "find_failed")."""
     from .assess import PoseAssessor
     from .supervisor import TrackSupervisor
     if look_ahead:
         raise ValueError("replay_dataset_supervised runs frame by frame: look_ahead is not supported")
     m = dict((params or {}).get("supervisor") or {})
-    unknown = sorted(set(m) - {"lost_frames", "occluded_frames", "assess", "contour", "contour_lost"})
+    unknown = sorted(set(m) - {"lost_frames", "occluded_frames", "assess", "contour", "contour_lost", "refine"})
     if unknown:
-        raise ValueError(f"supervisor/{unknown[0]}: unknown key (one of ['assess', 'contour', 'contour_lost', 'lost_frames', 'occluded_frames'])")
+        raise ValueError(f"supervisor/{unknown[0]}: unknown key (one of ['assess', 'contour', 'contour_lost', 'lost_frames', 'occluded_frames', 'refine'])")
+    refine = bool(m.get("refine", False)) if refine is None else bool(refine)
     assess_params = PoseAssessor.Parameters.from_mapping(m.get("assess"))
     contour_params = PoseAssessor.ContourParameters.from_mapping(m["contour"]) if "contour" in m else None
     tracker, object_model, camera_data, _ = build_particle_tracker(params, dataset.get_camera_matrix(0),
@@ -263,6 +281,7 @@ def replay_dataset_supervised(params, dataset, mesh_package_path, initial_states
         n = dataset.size() if max_frames is None else min(max_frames, dataset.size())
         frames = [dataset.frame_vector(i, f) for i in range(n)]
         assessor = PoseAssessor(tracker.sensor, assess_params, contour_params)
+        refiner = build_pose_refiner(params, tracker.sensor) if refine else None
         find = find_bodies = None
         if tracker.parts > 1:
             finder, _, _ = build_scene_finder(params, dataset.get_camera_matrix(0), mesh_package_path, device_id=device_id,
@@ -270,15 +289,18 @@ def replay_dataset_supervised(params, dataset, mesh_package_path, initial_states
 
             def find_bodies(frame, lost, estimate):
                 search = np.nonzero(lost)[0]
-                r = finder.find(frame, search=search, given=None if len(search) == tracker.parts else estimate, assess=assessor)
-                return r.state if r.confirmed is not None and bool(r.confirmed[search].all()) else None
+                r = finder.find(frame, search=search, given=None if len(search) == tracker.parts else estimate, assess=assessor,
+                                refine=refiner)
+                state = r.state if r.refined_state is None else r.refined_state
+                return state if r.confirmed is not None and bool(r.confirmed[search].all()) else None
         if tracker.parts == 1:
             finder, _, _ = build_object_finder(params, dataset.get_camera_matrix(0), mesh_package_path, device_id=device_id,
                                                sensor=tracker.sensor)
 
             def find(frame):
-                r = finder.find(frame, assess=assessor)
-                return r.states[r.confirmed] if r.confirmed is not None and r.confirmed >= 0 else None
+                r = finder.find(frame, assess=assessor, refine=refiner)
+                states = r.states if r.refined_states is None else r.refined_states
+                return states[r.confirmed] if r.confirmed is not None and r.confirmed >= 0 else None
         if initial_states is None:
             state = find(frames[0]) if find is not None else find_bodies(frames[0], np.ones(tracker.parts, dtype=bool), None)
             if state is None:

@@ -74,6 +74,17 @@ def states_to_Rt(states, n_bodies):
     return pack_Rt(rotvec_to_matrix(s[..., 3:6]), s[..., 0:3])
 
 
+def Rt_to_state(tracker, poses):
+    """Absolute pose [parts, 12] (R row-major | t, the sensor's centred mesh frame) -> tracker State [parts * 12] in the
+    caller's mesh frame, velocities zero: the inverse of assess.state_poses, through the tracker's own model-to-state rule."""
+    P = np.asarray(poses, dtype=np.float64).reshape(tracker.parts, 12)
+    s = np.zeros((tracker.parts, STATE_DIM))
+    for b in range(tracker.parts):
+        s[b, 0:3] = P[b, 9:12]
+        s[b, 3:6] = matrix_to_rotvec(P[b, :9].reshape(3, 3))
+    return tracker._from_model(s.ravel())
+
+
 def compose_with_default(deltas, default_state, n_bodies):
     """delta (+) default pose: deltas [n, n_bodies*12], default [n_bodies*12]
     -> absolute poses [n, n_bodies, 12]."""

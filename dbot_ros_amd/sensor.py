@@ -598,6 +598,12 @@ class RbSensor:
         self._check(fn(self._h, int(slot), C.byref(p)))
         return p.value
 
+    def refine_poses(self, poses, frame=None, params=None):
+        """poses [n, n_bodies, 12] refined against `frame` (None: the current observation) by rbs_refine_poses ->
+        (poses [n, n_bodies, 12], refine.Refinement).  params: a refine.PoseRefiner.Parameters (None: the library's defaults)."""
+        from .refine import PoseRefiner
+        return PoseRefiner(self, params).refine(poses, frame)
+
     def render_depth(self, pose):
         pose = np.ascontiguousarray(pose, dtype=np.float64).reshape(self.n_bodies * 12)
         out = np.empty(self.rows * self.cols, dtype=np.float32)

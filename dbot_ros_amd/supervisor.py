@@ -31,10 +31,16 @@ class TrackSupervisor:
     make the frame count as lost (LOST, OCCLUDED for too long, or -- with contour_lost -- a silhouette that reads ABSENT);
     only those are to be searched, the others keep the estimate's poses.  The found state is confirmed on the searched
     bodies alone: each SUPPORTED (and PRESENT with the contour rule on); the others' verdicts do not count.  `find` and its
-    one-object limit stay as they are; both at once: ValueError."""
+    one-object limit stay as they are; both at once: ValueError.
+    refine    None, or a PoseRefiner over the tracker's sensor (.refine_state(tracker, state, frame) -> (State, record)): a
+    found state is refined against the frame before it is confirmed, and the refined state is what the assessor judges
+    and what re-initialises the tracker (`last_refinement`: its record).  With find_bodies every body is refined in the one
+    call -- the refiner moves all bodies of a pose, so the searched bodies' ownership is taken against neighbours that
+    move with them, and `last_refinement` reports every body -- but only the searched bodies take their refined pose: the
+    others go on from the state find_bodies returned, bit for bit.  None: every step is what it was without."""
 
     def __init__(self, tracker, assessor, find=None, lost_frames=3, occluded_frames=0, look_ahead=False, contour_lost=False,
-                 find_bodies=None):
+                 find_bodies=None, refine=None):
         if look_ahead:
             raise ValueError("TrackSupervisor drives the tracker frame by frame: a verdict decides what the next frame starts from")
         if int(lost_frames) < 1 or int(occluded_frames) < 0:
@@ -46,6 +52,8 @@ class TrackSupervisor:
         if find is not None and find_bodies is not None:
             raise ValueError("TrackSupervisor: find and find_bodies are alternatives")
         self.find_bodies = find_bodies
+        self.refine = refine
+        self.last_refinement = None                         # the record of the last refined re-found state
         self.lost_frames, self.occluded_frames = int(lost_frames), int(occluded_frames)
         self.contour_lost = bool(contour_lost)
         if self.contour_lost and getattr(assessor, "contour", None) is None:
@@ -91,6 +99,13 @@ class TrackSupervisor:
         if state is None:
             return est, verdicts, "find_failed"
         state = np.asarray(state, dtype=np.float64).reshape(-1)
+        if self.refine is not None:
+            given = state
+            state, self.last_refinement = self.refine.refine_state(self.tracker, state, frame)
+            state = np.array(state, dtype=np.float64).reshape(-1)
+            if self.find_bodies is not None:   # only the searched bodies take the refined pose: the others keep theirs, bit for bit
+                keep = np.repeat(~lost_bodies, len(state) // self.parts)
+                state[keep] = given[keep]
         found = self.assessor.assess_state(self.tracker, state, frame)
         if self.find is not None:
             ok = bool((np.asarray(found.verdicts).reshape(-1) == SUPPORTED).all())

@@ -612,6 +612,18 @@ class ParticleTracker:
                 assessor = self._assessor = _assess.PoseAssessor(self.sensor)
         return _assess.assess_last_estimate(self, assessor, frame, self._in_flight > 0)
 
+    def refine(self, frame=None, refiner=None):
+        """The last estimate refined against `frame` (None: the sensor's current observation) -> (State,
+        refine.Refinement of one pose).  refiner: a PoseRefiner over the same sensor (None: one with the default
+        parameters, kept).  The filter is not touched: the next frame's estimate is what it would have been.  With
+        frames in flight the frame must be given: ValueError otherwise."""
+        from . import refine as _refine
+        if refiner is None:
+            refiner = getattr(self, "_refiner", None)
+            if refiner is None:
+                refiner = self._refiner = _refine.PoseRefiner(self.sensor)
+        return _refine.refine_last_estimate(self, refiner, frame, self._in_flight > 0)
+
 
 def modes_params_c(params):
     """A ModesParams as the C-ABI's rbs_modes_params (unchecked: the library refuses what is out of range)."""

@@ -1370,6 +1370,112 @@ int32_t rbs_tracker_object_map(rbs_tracker* t, int32_t* frame, float* cover, flo
 int32_t rbs_tracker_object_map_ms(rbs_tracker* t, float* ms);
 int32_t rbs_tracker_poses(rbs_tracker* t, double* out);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Poses refined against one depth frame (rbsensor_refine.hip, rbs_refine_api.h).
+ *
+ * Between "a pose that is roughly right" (the finder's, a tracker's mean) and "the pose on the surface the frame shows"
+ * stands a local, deterministic step: projective point-to-plane ICP, solved as damped Gauss-Newton.  Everything below is
+ * binary64 with + - x / sqrt and comparisons in the order written (no contraction), sums in a fixed order and integer
+ * counts; the only library functions are the sin and cos of rbd::rotvec_to_matrix.  A numpy restatement
+ * (tests/refine_twin.py) takes every decision bit for bit.
+ *
+ * A call takes n absolute poses [n][n_objects][12] (R row-major | t, as for rbs_assess_poses), one frame and an iteration
+ * count.  One iteration, for pose k (cx, cy, fx, fy: the camera matrix; ms, sf: model_sigma, sigma_factor of rbs_config):
+ *   1. planes   d_b(j) of every body b of the pose and its rectangle: the assess rule's planes (body b rendered alone);
+ *               owner(j) and its depth: the assess rule's owner.
+ *   2. usable   pixel i = (x, y) is usable for body b when 1 <= x <= cols - 2 and 1 <= y <= rows - 2; b owns i and its
+ *               four neighbours (x - 1, y), (x + 1, y), (x, y - 1), (x, y + 1); the frame's y_i is finite; and
+ *               |e| <= gate_sigmas x sigma with D = (double)d_b(i), e = (double)y_i - D, sigma = ms + sf x (D x D).
+ *   3. points   rx(x) = ((double)x - cx) / fx, ry(y) = ((double)y - cy) / fy, the ray rho = (rx, ry, 1); the model point of
+ *               pixel j is m(j) = (D_j x rx_j, D_j x ry_j, D_j).  a = m(x + 1, y) - m(x - 1, y), c = m(x, y + 1) - m(x, y - 1),
+ *               N = a cross c = (a1 c2 - a2 c1, a2 c0 - a0 c2, a0 c1 - a1 c0).  If (N0 m0 + N1 m1) + N2 m2 > 0 at m = m(i),
+ *               N = -N (decided on the un-normalised N: the normal faces the camera; (a cross c) . m equals
+ *               D (D_r + D_l) (D_d + D_u) / (fx fy) up to rounding, so on rendered planes the flip is always taken, and as
+ *               every term below holds n twice it changes no bit of any sum).  s = sqrt((N0 N0 + N1 N1) + N2 N2);
+ *               a pixel with !(s > 0) is skipped; n = N / s, component by component.
+ *   4. terms    h = 1 if |e| <= huber_sigmas x sigma, else (huber_sigmas x sigma) / |e|;  w = h / (sigma x sigma);
+ *               r = e x ((n0 rx + n1 ry) + n2): n . (p - m(i)) for the observed point p = y_i rho on the same ray;
+ *               q = m(i) - t_b;  J = (q cross n ; n) = (q1 n2 - q2 n1, q2 n0 - q0 n2, q0 n1 - q1 n0, n0, n1, n2): rotation first.
+ *   5. sums     over the usable pixels of (k, b), 28 of them in this order: the 21 upper entries of H = sum (w J_a) J_b
+ *               row by row ((0,0) (0,1) .. (0,5) (1,1) .. (5,5)), g_a = sum (w J_a) r, q = sum (w r) r; and the integer
+ *               count.  The rectangle's pixels in row-major order p = 0, 1, .. are dealt to P parts of 256 threads: thread
+ *               t of part j adds p = 256 j + t, + 256 P, + 512 P, .. in ascending order; P = min(16, ceil(pixels / 1024)), a
+ *               rule of the rectangle alone.  A part's 256 sums fold per wave by the shuffle tree (offsets 32, 16, .. 1),
+ *               then over the four waves in ascending order; the parts fold in ascending order.  No floating-point atomics:
+ *               the same inputs give the same bits on every run and in every batch.
+ *   6. solve    count < min_pixels: RBS_REFINE_TOO_FEW_PIXELS, the body does not move in this iteration and is evaluated
+ *               again in the next one (ownership may change as other bodies move).  Otherwise A = H, A_aa = H_aa +
+ *               damping x H_aa; lower Cholesky by rows (L_ab = (A_ab - sum_{c<b} L_ac L_bc) / L_bb, the pivot p = A_aa - sum
+ *               L_ac L_ac, L_aa = sqrt(p)); a pivot that is not > 0 or not finite: RBS_REFINE_DEGENERATE, the body does not
+ *               move and is frozen.  y_a = (g_a - sum_{c<a} L_ac y_c) / L_aa ascending, delta_a = (y_a - sum_{c>a} L_ca
+ *               delta_c) / L_aa descending, sums ascending in c; delta = (omega, v).  |omega| = sqrt((o0 o0 + o1 o1) + o2 o2)
+ *               > max_rotation: omega = omega x (max_rotation / |omega|); v likewise with max_translation.
+ *               R <- rbd::rotvec_to_matrix(omega) R (matmul3), t <- t + v.  When the clamped |omega| < eps_rotation and
+ *               |v| < eps_translation the update is still applied, and the body is RBS_REFINE_CONVERGED and frozen.  A frozen
+ *               body is still rendered, for the owner rule.
+ *   7. after `iters` iterations an unfrozen body is RBS_REFINE_MAX_ITERATIONS when its last iteration moved it, and
+ *      RBS_REFINE_TOO_FEW_PIXELS when its last iteration had too few pixels.
+ * Bodies of one pose are solved independently within an iteration, each from the planes of the poses that entered it.
+ *
+ * The record per (pose, body): status, the iterations evaluated (a frozen body: up to and including the one that froze
+ * it), and count and rms = sqrt(q / count) (0 when count is 0) of the first and of the last evaluated iteration.
+ *
+ * A call does not touch the sensor's state (as rbs_assess_poses), nor the assessor's planes: it runs on the sensor's
+ * stream into buffers of its own (n x n_objects planes, allocated by the first call, grow-only, freed by rbs_destroy).
+ * All iterations are enqueued without a host round trip -- a frozen body skips by a device flag -- and the call ends
+ * with one copy and one synchronisation.  frame == NULL: the sensor's current observation, with rbs_assess_poses' wait.
+ * Limits: n >= 1, n x n_objects <= 64, every pose entry finite, the parameters within their ranges (all checked on the
+ * host before any launch), single-device handles (RBS_ERR_UNSUPPORTED otherwise).
+ *
+ * Every default below is an unmeasured starting value: none was tuned on data (DESIGN.md Appendix Q says what was
+ * measured with them). */
+enum { RBS_REFINE_MAX_ITERATIONS = 0, RBS_REFINE_CONVERGED = 1, RBS_REFINE_TOO_FEW_PIXELS = 2, RBS_REFINE_DEGENERATE = 3,
+       RBS_REFINE_FROZEN = 4 /* history only: the body was frozen before this iteration */ };
+#define RBS_REFINE_MAX_ITERS 32
+
+typedef struct rbs_refine_params {   /* 64 bytes */
+    double gate_sigmas;       /* 10 (finite, > 0): unmeasured starting value                                        */
+    double huber_sigmas;      /* 3 (finite, > 0): unmeasured starting value                                         */
+    double damping;           /* 1e-3 (finite, >= 0; 0: plain Gauss-Newton): unmeasured starting value              */
+    double max_rotation;      /* 0.2 rad per iteration (finite, > 0): unmeasured starting value                     */
+    double max_translation;   /* 0.02 m per iteration (finite, > 0): unmeasured starting value                      */
+    double eps_rotation;      /* 1e-3 rad (finite, >= 0): unmeasured starting value                                 */
+    double eps_translation;   /* 1e-4 m (finite, >= 0): unmeasured starting value                                   */
+    int32_t min_pixels;       /* 16 (>= 1): unmeasured starting value                                               */
+    int32_t iters;            /* 10 (1 .. RBS_REFINE_MAX_ITERS): unmeasured starting value                          */
+} rbs_refine_params;
+
+typedef struct rbs_refine_body {   /* 32 bytes */
+    int32_t status;                /* RBS_REFINE_MAX_ITERATIONS .. RBS_REFINE_DEGENERATE                            */
+    int32_t iterations;            /* iterations evaluated                                                          */
+    int32_t count_first, count_last;   /* usable pixels of the first / last evaluated iteration                     */
+    double rms_first, rms_last;    /* sqrt(q / count) of those (whitened: in sigmas)                                */
+} rbs_refine_body;
+
+typedef struct rbs_refine_history {   /* 376 bytes: one iteration of one (pose, body) */
+    double pose[12];               /* the pose that entered the iteration                                           */
+    double sums[28];               /* H upper (21), g (6), q; zeros for RBS_REFINE_FROZEN                           */
+    double delta[6];               /* (omega, v) applied, after the clamp; zeros when the body did not move         */
+    int32_t count;
+    int32_t status;                /* of this iteration: RBS_REFINE_MAX_ITERATIONS = moved and not converged        */
+} rbs_refine_history;
+
+/* The defaults above, stated once. */
+void rbs_refine_default_params(rbs_refine_params* p);
+/* RBS_OK when rbs_refine_poses would accept the parameters, RBS_ERR_INVALID_ARGUMENT otherwise (NULL: the defaults, RBS_OK):
+ * host only, no device. */
+int32_t rbs_refine_check_params(const rbs_refine_params* params);
+/* n poses refined against one frame.  params: NULL = the defaults; frame: rows*cols floats (NULL: the sensor's current
+ * observation); poses_in, poses_out [n][n_objects][12] (may be the same array); records_out [n][n_objects] or NULL. */
+int32_t rbs_refine_poses(rbs_handle* h, const rbs_refine_params* params, const float* frame, const double* poses_in, int32_t n,
+                         double* poses_out, rbs_refine_body* records_out);
+/* Inspection: iteration `iteration` of body b of pose k of the last call.  Before the first call, or for a bad index:
+ * RBS_ERR_INVALID_ARGUMENT. */
+int32_t rbs_refine_get_history(rbs_handle* h, int32_t k, int32_t b, int32_t iteration, rbs_refine_history* out);
+/* Device time of the last call's kernels in ms (HIP events), summed over its iterations: [0] render, [1] accumulate,
+ * [2] solve. */
+int32_t rbs_refine_kernel_ms(rbs_handle* h, float* out3);
+
 #ifdef __cplusplus
 }
 #endif
